@@ -2,6 +2,7 @@
 """bench.py -- grid-point log-likelihood evals/s of the likelihood grid search.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|c5|f2|f3] [--kernel auto]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -25,8 +26,8 @@ Weak scaling (default): with N ranks the c axis has N times as many values over 
 range and the flat index range is block-partitioned, one contiguous block of the
 single-GPU size per rank.  --scaling strong: ONE fixed grid, c3 refined to c128 x e128 x q1 16 x q 16 =
 4.2 M points (~20 ms on one GPU), cut into N contiguous blocks balanced by sum(T - 1)
-(SURVEY.md 8(e)); the line then carries the ranks' kernel times (imbalance) and the cost of
-the exchange.  With N > 1 the default (weak) invocation ALSO runs that strong-scaling grid in the same
+(SURVEY.md 8(e)); the line then carries the ranks' kernel times (imbalance) and, with --full, the cost
+of the exchange.  With N > 1 and --full the weak invocation ALSO runs that strong-scaling grid in the same
 process group and reports it under variants.strong (per-rank kernel times, imbalance, RCCL exchange cost,
 speed-up over the one-GPU time recorded in profiles/): the driver issues one command per N, and the
 north-star's ">= 6x at 8 GPUs" is a strong-scaling statement.
@@ -36,6 +37,16 @@ bytes are copied back.
 
 Before the W warm-up steps a fixed, uncounted spin-up of 25 steps lets the device's clocks settle.
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the line's headline needs: set-up, spin-up and warm-up, the K timed steps, the
+outputs (--dump-outputs) and the line.  --full adds everything else the benchmark measures: the warm
+time-to-argmin searches, the CPU baselines, the other single-GPU configurations as child runs (variants.*),
+with N > 1 the strong-scaling grid and the cost of the exchange alone, and the side legs of c5 and f2.
+--dump-outputs DIR: after the timed steps, what the last step computed as DIR/<name>.npy (float64) --
+the grid workloads write `argmin` ([min -LL, flat index]) and, of rank 0's block, the finite log-likelihoods
+(`loglikelihoods`) with their flat indices (`loglikelihood_index`): every point not listed has LL -inf (zero
+likelihood; NaN for a degenerate point), which stays out of the files so that they hold finite numbers only.
+The inputs are fixed (histograms in tests/golden/, axes from the workload), so two builds compare file by file.
 """
 import argparse
 import json
@@ -341,8 +352,12 @@ def bench_kmer(args):
     # What bounds either path is the rate at which the memory side retires scattered atomics -- MEASURED here, on this
     # device, over an array the size of the one the run's atomics fall into (no constant from an earlier round): the
     # partitioned path pays one returning add per RECORD (a cursor per bucket), the table one load + add per OCCURRENCE.
+    # A run of its own: with --full only.
     atomic_slots = partition["buckets"] if partitioned else counts.slots * 2
-    atomics_per_s = kh.scatter_rate(atomic_slots, ops=1 << 28)
+    atomics_per_s = kh.scatter_rate(atomic_slots, ops=1 << 28) if args.full else None
+
+    def frac(rate):
+        return rate / atomics_per_s if atomics_per_s else None
     if partitioned:
         records = partition["records"]
         scatter_s = 1e-3 * partition["ms"]["scatter"]
@@ -352,7 +367,7 @@ def bench_kmer(args):
         dominant = {"kernel": "kmer_tile_kernel<false> (pass 1: records to their buckets)", "kernel_ms_avg": 1e3 * scatter_s,
                     "algorithmic_bytes_per_launch": alg_bytes, "achieved": alg_bytes / scatter_s / 1e9,
                     "atomics": {"per_launch": records, "achieved_per_s": records / scatter_s,
-                                "roof_per_s_measured": atomics_per_s, "frac": records / scatter_s / atomics_per_s,
+                                "roof_per_s_measured": atomics_per_s, "frac": frac(records / scatter_s),
                                 "roof_slots": atomic_slots},
                     "passes_ms": partition["ms"],
                     "note": "bound by the memory side's scattered-atomic rate (one returning add per record, 64-byte "
@@ -362,7 +377,7 @@ def bench_kmer(args):
         dominant = {"kernel": "kmer_count_fixed_kernel", "kernel_ms_avg": 1e3 * kernel_s,
                     "algorithmic_bytes_per_launch": alg_bytes, "achieved": alg_bytes / kernel_s / 1e9,
                     "atomics": {"per_launch": n_kmers, "achieved_per_s": n_kmers / kernel_s,
-                                "roof_per_s_measured": atomics_per_s, "frac": n_kmers / kernel_s / atomics_per_s,
+                                "roof_per_s_measured": atomics_per_s, "frac": frac(n_kmers / kernel_s),
                                 "roof_slots": atomic_slots},
                     "note": "scattered 8-byte load/CAS + 8-byte atomic add (same line) per k-mer occurrence"}
     out = {
@@ -381,10 +396,10 @@ def bench_kmer(args):
         "roofline": dict({"bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                           "frac": dominant["achieved"] / HBM_PEAK_GBPS, "traffic": None}, **dominant),
     }
-    if not args.compact:
+    if args.full and not args.compact:
         counts.clear(stream)  # (from_file counts through the table: an ordinary counter again)
         out["config"]["from_file"] = kmer_from_file(reads, n_reads, read_len, k, counts)
-    if args.cpu_budget > 0:
+    if args.full and args.cpu_budget > 0:
         from oracle import kmer_oracle as ko
         n_s = 5000 if args.compact else 20000
         sample = [bytes(reads[i * read_len:(i + 1) * read_len].cpu().numpy()).decode() for i in range(n_s)]
@@ -438,7 +453,7 @@ def bench_thin(args):
                      "traffic": None, "kernel": "thin_partial_kernel", "kernel_ms_avg": kernel_ms,
                      "algorithmic_flops_per_launch": flops},
     }
-    if args.cpu_budget > 0:
+    if args.full and args.cpu_budget > 0:
         from oracle import hist_oracle as ho
         n_s = len(keys)  # every bin: 5e7 terms, the reference's O(i) long-double recurrence per bin
         t0 = time.perf_counter()
@@ -463,17 +478,13 @@ def bench_refine(args):
     random.seed(20240521)
     starts = initial_grid([25.0, 0.02, 0.6, 0.5, 0.1], count=20, bounds=est.bounds)
     m.compute_loglikelihood(*starts[0])  # module load, handle creation
-    steps = max(1, min(args.steps, 3))
+    steps = args.steps
     t0 = time.perf_counter()
     for _ in range(steps):
         results = [est._optimize(s) for s in starts]  # the default schedule: one start after the other
     batched_s = (time.perf_counter() - t0) / steps
     evals = sum(6 * r.nfev for r in results)
     best = min(results, key=lambda r: r.fun)
-    t0 = time.perf_counter()
-    lock = _LockStep(est.negll_points, len(starts))
-    locked = lock.map(est._optimize, starts)
-    lock_s = time.perf_counter() - t0
     out = {
         "metric": "likelihood evaluations/s inside the 20-start L-BFGS-B refinement (repeat model, 10k-bin hist)",
         "value": evals / batched_s, "unit": "evals/s", "n_gpus": 1, "steps": steps, "warmup": 1,
@@ -485,11 +496,17 @@ def bench_refine(args):
                              "numbers beyond that",
                    "evaluations": evals, "launches": sum(r.nfev for r in results),
                    "best_negll": float(best.fun), "best_x": [float(v) for v in best.x]},
-        "lock_step": {"ms_per_step": 1e3 * lock_s, "launch_rounds": lock.rounds, "points_per_round": lock.points / lock.rounds,
-                      "identical_results": all(np.array_equal(a.x, b.x) for a, b in zip(results, locked)),
-                      "note": "all 20 starts as threads, one launch per round"},
     }
-    if args.cpu_budget > 0:
+    if args.full:
+        t0 = time.perf_counter()
+        lock = _LockStep(est.negll_points, len(starts))
+        locked = lock.map(est._optimize, starts)
+        lock_s = time.perf_counter() - t0
+        out["lock_step"] = {"ms_per_step": 1e3 * lock_s, "launch_rounds": lock.rounds,
+                            "points_per_round": lock.points / lock.rounds,
+                            "identical_results": all(np.array_equal(a.x, b.x) for a, b in zip(results, locked)),
+                            "note": "all 20 starts as threads, one launch per round"}
+    if args.full and args.cpu_budget > 0:
         # the reference's pattern on the same GPU kernels: a subset of the starts, one evaluation per call
         sub = starts[:4]
         plain = CoverageEstimator(m, batched=False)
@@ -594,7 +611,7 @@ def strong_variant(cls, hist, args, world, rank, local_rank, xdev, on_device, st
 
 
 def other_configs(args):
-    """The default (driver-timed) run carries every single-GPU configuration of BASELINE.json, not only C3: config 2
+    """The --full run carries every single-GPU configuration of BASELINE.json, not only C3: config 2
     (basic model, 10^6 points), config 5 (k-mer histogram; 10 Gbp when >= 200 GB of HBM are free, else 1 Gbp), the
     reference's consumer of batched evaluations (optimize_grid) and configs 3 and 2 on the histograms the reference's own
     pipeline would hand the model (trimmed, with a tail: `tail`, `c2_tail`), each run as a CHILD process of this one -- its own
@@ -613,7 +630,7 @@ def other_configs(args):
     for name, extra in runs:
         t0 = time.perf_counter()
         try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--compact"] + extra, capture_output=True,
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--compact", "--full"] + extra, capture_output=True,
                                text=True, timeout=240)
             line = [l for l in p.stdout.splitlines() if l.startswith("{")]
             if p.returncode != 0 or not line:
@@ -664,7 +681,7 @@ def bench_optimize_grid(args):
         est = CoverageEstimator(m)
         est.likelihood_f(guess)  # module load, handle creation
         walls, last = [], None
-        for rep in range(max(1, min(args.steps, 5)) + 1):
+        for rep in range(args.steps + 1):
             est.timings = []
             t0 = time.perf_counter()
             og_trace = []
@@ -716,11 +733,21 @@ def main():
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal: every rank uses device 0 (needs --backend gloo)")
     ap.add_argument("--compact", action="store_true",
-                    help="(set by the default run for its child runs) leave out the legs that only feed profiles/: c5's "
+                    help="(set by the --full run for its child runs) leave out the legs that only feed profiles/: c5's "
                          "from-file leg, c3's tail variant and the children themselves")
     ap.add_argument("--no-variants", action="store_true",
                     help="c3, one GPU: do not run the other single-GPU configurations (c2, c5, og) as child processes")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not only the headline: warm time-to-argmin, CPU baselines, the other "
+                         "configurations (variants), the strong-scaling grid with N > 1, c5's and f2's side legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="grid workloads: write the last timed step's outputs as DIR/<name>.npy (float64): the arg-min, "
+                         "the finite log-likelihoods and their flat indices")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload in ("c5", "f2", "f3", "og"):
+        ap.error("--dump-outputs is implemented for the grid workloads (c1, c2, c3, c2t, c3t)")
     if args.workload == "c5":
         return bench_kmer(args)
     if args.workload == "f3":
@@ -826,6 +853,13 @@ def main():
     kernel_ms, launches = grid.kernel_ms()
     grid.profile(False)
     terms, flops, kernel_name = grid.work()
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        ll = grid.loglikelihoods()
+        kept = np.flatnonzero(np.isfinite(ll))
+        np.save(os.path.join(args.dump_outputs, "loglikelihoods.npy"), ll[kept])
+        np.save(os.path.join(args.dump_outputs, "loglikelihood_index.npy"), (block[0] + kept).astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "argmin.npy"), np.array([gmin, gidx], dtype=np.float64))
     # (measured AFTER the timed region since round 4: between the warm-up and the timed steps its ten searches, with
     # their host-side gaps, let the device's clocks sag, and the 20 timed steps then ran 3-5 % under the sustained rate
     # -- profiles/r04_clock_ramp.txt: 0.718 ms a step for the first 20 steps from idle, 0.685 from 14 ms on)
@@ -857,19 +891,24 @@ def main():
         return t4 - t0, {"model_handle": 1e3 * (t2 - t0), "grid_handle_and_plan": 1e3 * (t3 - t2),
                          "launch_kernels_readback": 1e3 * (t4 - t3)}
 
-    runs_dict = sorted((warm_search(hist) for _ in range(5)), key=lambda r: r[0])
-    runs_arr = sorted((warm_search(hist_arrays) for _ in range(5)), key=lambda r: r[0])
-    time_to_argmin_warm = runs_arr[2][0]
-    time_to_argmin_split = runs_arr[2][1]
-    time_to_argmin_warm_dict = runs_dict[2][0]
+    time_to_argmin = {"first_call_incl_module_load": 1e3 * time_to_argmin_first}
+    if args.full:
+        runs_dict = sorted((warm_search(hist) for _ in range(5)), key=lambda r: r[0])
+        runs_arr = sorted((warm_search(hist_arrays) for _ in range(5)), key=lambda r: r[0])
+        time_to_argmin.update({"warm": 1e3 * runs_arr[2][0], "warm_split": runs_arr[2][1],
+                               "warm_histogram_as_dict": 1e3 * runs_dict[2][0],
+                               "what": "host axes + histogram (arrays; or the reference's dict) -> model handle, grid "
+                                       "handle + plan, kernels, 16-byte read-back; median of 5"})
 
-    # N > 1: every rank's likelihood-kernel time (imbalance of the partition) and the price of the exchange alone
+    # N > 1: every rank's likelihood-kernel time (imbalance of the partition) and, with --full, the price of the
+    # exchange alone
     per_rank_kernel_ms, exchange_us = None, None
     if world > 1:
         mine = torch.tensor([kernel_ms / max(launches, 1)], dtype=torch.float64, device=xdev)
         every = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)
         per_rank_kernel_ms = [float(t.item()) for t in every]
+    if world > 1 and args.full:
         dist.barrier()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -879,9 +918,9 @@ def main():
         exchange_us = 1e6 * (time.perf_counter() - t1) / 20
     variants = None
     if rank == 0 and world == 1 and args.workload == "c3" and args.scaling == "weak" and not args.compact \
-            and not args.no_variants:
+            and not args.no_variants and args.full:
         variants = other_configs(args)
-    if world > 1 and args.workload == "c3" and args.scaling == "weak":  # (every rank takes part)
+    if world > 1 and args.workload == "c3" and args.scaling == "weak" and args.full:  # (every rank takes part)
         variants = {"strong": strong_variant(cls, hist, args, world, rank, local_rank, xdev, on_device, stream)}
 
     if rank == 0:
@@ -927,11 +966,7 @@ def main():
                              "device, 16 bytes copied back)",
             },
             "argmin": argmin_record(args.workload, gmin, gidx),
-            "time_to_argmin_ms": {"first_call_incl_module_load": 1e3 * time_to_argmin_first,
-                                  "warm": 1e3 * time_to_argmin_warm, "warm_split": time_to_argmin_split,
-                                  "warm_histogram_as_dict": 1e3 * time_to_argmin_warm_dict,
-                                  "what": "host axes + histogram (arrays; or the reference's dict) -> model handle, grid "
-                                          "handle + plan, kernels, 16-byte read-back; median of 5"},
+            "time_to_argmin_ms": time_to_argmin,
             "roofline": {
                 "bound": "mfma", "pipe": "fp64 VALU + fp64 MFMA: ONE shared fp64 datapath (tools/microbench_mix.hip); "
                                          "78.6 TFLOP/s is both the fp64 vector and the dense fp64 MFMA peak of MI355X",
@@ -970,7 +1005,7 @@ def main():
             out["roofline"]["executed_from"] = {"file": "profiles/pmc_traffic.json", "source_sha16": profile_sha,
                                                 "this_library_source_sha16": here,
                                                 "stale": profile_sha is not None and profile_sha != here}
-        if kernel_name == "ll_factored" and world == 1 and model.tail == 0:
+        if kernel_name == "ll_factored" and world == 1 and model.tail == 0 and args.full:
             # The same kernel time on ROUND 1's flop count of K-factored (one multiply-add per (key, column, o < T)
             # in the contraction; since round 2 the steps below a q-tile's smallest cut-off are summed once per key --
             # DESIGN.md 4): for comparison with the 0.37 of round 1 only, `frac` above is the honest one.
@@ -995,7 +1030,7 @@ def main():
                     "`value` is the WEAK-scaling step (the c axis grows N-fold: per-GPU work fixed, what the driver's "
                     "efficiency column measures); variants.strong is the north-star question -- one fixed 4.2 M-point "
                     "grid divided among the N GPUs -- answered in the same run")
-        if world == 1 and args.cpu_budget > 0:
+        if world == 1 and args.full and args.cpu_budget > 0:
             out["cpu_baseline"] = cpu_baseline(kind, hist, axes, args.cpu_budget, tail=tail)
         print(json.dumps(out), flush=True)
 

@@ -14,7 +14,7 @@ One session-local alias is needed: covest/models.py:10 does
 copied.  Interpreter-dependent semantics are recorded in every fixture's "env".
 
 Usage:  python tests/golden/make_golden.py [section ...]
-Sections: tp basic repeats threshold hists c1 c2 c2classes c2trim c2argmin c3 c3tail c3trim c3argmin gridtrace overflow   (default: all)
+Sections: tp tpbits basic repeats threshold hists c1 c2 c2classes c2trim c2argmin c3 c3tail c3trim c3argmin gridtrace overflow   (default: all)
 (c3argmin reads c3_candidates_gpu.json: flat indices written on the GPU box by tools/dump_c3_candidates.py;
  c2classes reads c2_classes_gpu.json: flat indices written on the GPU box by tools/dump_c2_classes.py)
 """
@@ -126,6 +126,20 @@ def section_tp():
         j = int(math.exp(rnd.uniform(0, math.log(9000)))) + 0
         rows.append([l, max(1, j), truncated_poisson(l, max(1, j))])
     dump("tp_table.json", {"what": "covest_poisson.truncated_poisson(l, j)", "rows": rows})
+
+
+def section_tpbits():
+    """The inputs of tests/test_oracle_vs_ref.py (random.Random(11) draws, then the 200 / 400 / 1e-8 boundaries)."""
+    rnd = random.Random(11)
+    rows = []
+    for _ in range(3000):
+        l = math.exp(rnd.uniform(math.log(1e-10), math.log(2e4)))
+        j = int(math.exp(rnd.uniform(0, math.log(12000))))
+        rows.append([l, j, truncated_poisson(l, j)])
+    edges = [[l, j, truncated_poisson(l, j)]
+             for l in (199.99999999, 200.0, 200.00000001, 400.0, 400.000000001, 1e-8, 1.0000001e-8) for j in (1, 5, 300)]
+    dump("tp_bitwise.json", {"what": "covest_poisson.truncated_poisson(l, j), compared bit for bit",
+                             "rows": rows, "edges": edges})
 
 
 # ----------------------------------------------------------------------------- (2) basic
@@ -752,7 +766,7 @@ def section_overflow():
 
 
 def main():
-    wanted = sys.argv[1:] or ["tp", "basic", "repeats", "threshold", "hists", "c1", "c2", "c2classes", "c2trim", "c2argmin", "c3", "c3tail",
+    wanted = sys.argv[1:] or ["tp", "tpbits", "basic", "repeats", "threshold", "hists", "c1", "c2", "c2classes", "c2trim", "c2argmin", "c3", "c3tail",
                               "c3trim", "c3argmin", "gridtrace", "overflow"]
     pool = multiprocessing.Pool(int(os.environ.get("COVEST_GOLDEN_PROCS", "8")))
     for name in wanted:

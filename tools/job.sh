@@ -1,6 +1,6 @@
 out=gpurun_out/r5fin2
 mkdir -p $out
-timeout -k 10 600 python3 bench.py > $out/bench_default.json 2> $out/bench_default.err || echo "default bench failed"
+timeout -k 10 600 python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err || echo "default bench failed"
 for w in c3 c2 c3t c2t c1; do timeout -k 10 200 python3 bench.py --workload $w --no-variants > $out/bench_$w.json 2> $out/bench_$w.err || echo "bench $w failed"; done
 python3 -c "
 import json
