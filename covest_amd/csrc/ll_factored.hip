@@ -138,11 +138,13 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     constexpr int LOG_DEG = PLAIN ? 3 : 5;     // (point lists keep the 2e-16 log: refinements difference their values;
                                                // dense grids: 6e-13 absolute and the exponent's bias taken off per sum)
     const int LD = LDC ? LDC : plan.ld; // G row stride in doubles: 4 dwords (mod 64) -> conflict-free A reads
-    extern __shared__ double Gs[]; // [n_buf][kTileBins][LD]; reused for the final per-q combine
+    constexpr int NE = FactoredLds::entries_of(NT); // [waves][slots][16] entries: one per (wave, slot, weight vector)
+    const FactoredLds lay{NT, plan.n_buf, LD, SPO}; // every offset into Gs (tiles.h)
+    extern __shared__ double Gs[]; // G's buffers; reused for the final per-q combine
     __shared__ __attribute__((aligned(16))) double log_tab[kLogTableDoubles];
     // rows handed back (direct_point.h), per accumulator slot and weight vector: first unit, last unit + 1 (0: none;
     // a unit = the 16 rows of a half tile: index 2 * tile + half).  One writer per entry: the lane with kq == 0.
-    __shared__ unsigned sub_rec[NW * MU * 16 * 2];
+    __shared__ unsigned sub_rec[NE * 2];
     // per row of the key tile being logged and of the next one: {h_j, p_clamp in the row's units (0: no count -- such
     // a row is never "low")}, and the row's scale where p_j itself is needed.  Every unit reads the 4 rows of its lanes
     // from here (LDS, addressed by the unit's half) instead of selecting between two register sets per row.
@@ -151,6 +153,10 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     // {(1-q)^16, -, (1-q)^4, (1-q)^(-4 nsh)} of every slot with shared steps (tiles.h): wave-uniform, read back as LDS broadcasts
     __shared__ __attribute__((aligned(16))) double rho_tab[PLAIN ? NW * MU * 4 : 4];
     __shared__ double lconst_s; // the constant the rows' scales add to every point's sum (tiles.h item_lconst)
+    static_assert(MU == kMaxUnits, "the LDS layout counts kMaxUnits slots a wave");
+    // (+ 15 bytes of alignment in front of each array at most)
+    static_assert(sizeof(log_tab) + sizeof(sub_rec) + sizeof(rowc) + sizeof(rows) + sizeof(rho_tab) + sizeof(lconst_s) + 6 * 15 <=
+                      kFactoredStaticLds, "the planners' LDS budget (tiles.h) must hold the kernel's static LDS");
 
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
@@ -201,8 +207,8 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     if (PLAIN && tid < NW * MU * 4)
         rho_tab[tid] = rho_v;
 #pragma unroll
-    for (int u = 0; u < (NW * MU * 16 + NT - 1) / NT; ++u)
-        if (tid + u * NT < NW * MU * 16) {
+    for (int u = 0; u < (NE + NT - 1) / NT; ++u)
+        if (tid + u * NT < NE) {
             sub_rec[2 * (tid + u * NT)] = 0xFFFFFFFFu;
             sub_rec[2 * (tid + u * NT) + 1] = 0;
         }
@@ -214,7 +220,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     // pows were 420 dependent instructions that every wave of the workgroup waited for at the barrier below; the strict
     // re-evaluation of the rows handed back, argmin.hip, forms the same products)
     if (tid < 8 * n_pass)
-        Gs[tid] = error_class_rate_mul(m, par[0], par[1], tid, m.n_err);
+        Gs[lay.rates() + tid] = error_class_rate_mul(m, par[0], par[1], tid, m.n_err);
     if (wave == NW - 1) { // the items' constants: one load per lane and 64 items, added in a fixed order
         double lc = 0.0 + lc_first; // (the first 64 items' were asked for above)
         for (int t = t_begin + lane + kWave; t < t_end; t += kWave)
@@ -241,12 +247,12 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     double lam[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s)
-        lam[s] = Gs[8 * my_pass + s];
+        lam[s] = Gs[lay.rates() + 8 * my_pass + s];
     double n_total = -1.0;
     if (n_pass > 1) { // the mixture weights a_os are normalised over ALL classes: covest/models.py:225-233
         n_total = 0.0;
         for (int s = 0; s < 8 * n_pass; ++s)
-            n_total += m.comb[s] * (1.0 - exp_neg_rn((double)o_mine * Gs[s]));
+            n_total += m.comb[s] * (1.0 - exp_neg_rn((double)o_mine * Gs[lay.rates() + s]));
     }
     __syncthreads();
     StreamSet<8> st;
@@ -279,12 +285,12 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     dgx_2 = (long long)clock64(); // the streams' constants (builder waves)
 #endif
     const bool lane_in_row = tid < LD - 2; // columns of G that exist (waves past them build nothing)
-    if (tid < 64)
-        Gs[(size_t)plan.n_buf * kTileBins * LD + tid] = 0.0; // the slack behind the buffers (see launch)
+    if (tid < FactoredLds::kSlack)
+        Gs[lay.slack() + tid] = 0.0; // the slack behind the buffers
     // the two pad columns of every row are read by masked steps too: keep them finite
-    if (tid < plan.n_buf * kTileBins) {
-        Gs[(size_t)tid * LD + LD - 2] = 0.0;
-        Gs[(size_t)tid * LD + LD - 1] = 0.0;
+    if (tid < lay.rows()) {
+        Gs[lay.pad(tid)] = 0.0;
+        Gs[lay.pad(tid) + 1] = 0.0;
     }
 
     // ---- phase-B/C state: this wave's (q-tile, half) units ----
@@ -703,7 +709,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
         const int pb = dbuf ? p + 1 : p;
         if (SPO && pb == t_end) {
             if (wave_builds && lane_in_row) { // S[o] (x 2^-kBasicShift: exact) as the two rows of one more "item"
-                double *dst = Gs + (dbuf ? (pb & 1) * kTileBins * LD : 0) + tid;
+                double *dst = Gs + lay.buf(pb) + tid;
                 dst[0] = so.hi * 0x1p-540;
                 dst[LD] = so.lo * 0x1p-540;
             }
@@ -718,19 +724,16 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                 if (last_first && pb == t_begin + 1)
                     st.gone = 0u;
                 build_item(tile_at(pb), pb == t_begin || (last_first && (pb == t_begin + 1 || pb == last_item + 1)),
-                           Gs + (dbuf ? (pb & 1) * kTileBins * LD : 0));
+                           Gs + lay.buf(pb));
             }
         }
         STAMP(dg_a)
         if (!dbuf)
             __syncthreads();
         const bool sp_item = SPO && p == t_end; // (wave-uniform) the last position: S x b
-        // (SPO) where the units leave their shares of sp_j: [2][NW][MU][16] doubles in the buffer that is NOT contracted in
-        // the last interval (one buffer only: behind the two rows of S -- rows whose products nobody uses)
-        double *const sp_parts = dbuf ? Gs + ((t_end + 1) & 1) * kTileBins * LD + NW * MU * 16 : Gs + 2 * LD + NW * MU * 16;
         if (p >= t_begin && !(SPO && !sp_item && tv.item_sum[tile_at(p)] != 0)) { // (SPO: a sum item was phase A only)
             const int t = tile_at(p); // the tile this interval contracts and logs
-            const double *cur = Gs + (dbuf ? (p & 1) * kTileBins * LD : 0);
+            const double *cur = Gs + lay.buf(p);
             // ================= phase B: P' = G' x b on the matrix pipe =================
             d4 acc[MU];
             const d4 zero4 = (d4){0.0, 0.0, 0.0, 0.0};
@@ -785,7 +788,8 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                 // the heads WITHOUT branches: a head that does not exist is read from the zeroed slack behind the buffers
                 // (one select on the address), so that the three loads, the slot's constants above and the first trip's
                 // eight are in flight together -- one LDS round trip at the top of a slot instead of three or four
-                const double *zp = Gs + (size_t)plan.n_buf * kTileBins * LD;
+                // (the layout made afresh from the plan: `lay`'s n_buf, held from the top of the kernel, cost the walk spilled scalars)
+                const double *zp = Gs + FactoredLds{NT, plan.n_buf, LD, SPO}.slack();
                 double h0 = *(rem > 0 ? top : zp), h1 = *(rem > 1 ? top + 4 : zp), h2 = *(rem > 2 ? top + 8 : zp), h3 = 0.0;
                 {
                     // The trips' reads are written out as ds_read_b64: left alone the compiler pairs them into
@@ -894,10 +898,11 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                 if (SPO && sp_item) {
                     // rows 0 and 1 are S (hi, lo): register 0 of the lanes with kq = 0 and kq = 1 holds this column's
                     // sum_o b_o S_hi[o] and sum_o b_o S_lo[o].  Straight to where the last step below looks for them
-                    // (sp_parts: LDS nobody reads any more) -- held in registers until then they would be carried through
-                    // every interval of the walk.  A dead unit writes its zeros: its sum is -inf whatever sp_j is.
+                    // (the SPO parts, tiles.h FactoredLds: out of the last interval's way) -- held in registers until then
+                    // they would be carried through every interval of the walk.  A dead unit writes its zeros: its sum is
+                    // -inf whatever sp_j is.
                     if (qslot[k] >= 0 && !cont[k] && uhalf[k] == 0 && lane < 32)
-                        sp_parts[(kq * NW * MU + wave * MU + k) * 16 + col] = acc[k][0];
+                        Gs[lay.spo_parts(t_end) + kq * NE + (wave * MU + k) * 16 + col] = acc[k][0];
                     continue;
                 }
                 if (TAIL && !SPO && item_is_sum) { // rows are sums over count-less tiles (scaled ones): they only enter sp_j
@@ -1047,13 +1052,13 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     // before: the walk's register allocation hangs on the shape of this epilogue, and the tail-less kernel measured
     // 0.6384 and 0.6500 against 0.6354 ms with two forms of the early fetch (the trimmed C3 with its tail: 0.3817 and
     // 0.3851 against 0.3861) -- profiles/r05_c3_ab_result_entries_early.txt.
-    constexpr int kEntries = (NW * MU * 16 + NT - 1) / NT;
+    constexpr int kEntries = (NE + NT - 1) / NT;
     constexpr bool kEntriesEarly = TAIL;
     int en_qt[kEntries], en_half[kEntries], en_cont[kEntries], en_pair[kEntries], en_qo[kEntries];
     auto fetch_entries = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < kEntries; ++u) {
-            const int e = min(tid + u * NT, NW * MU * 16 - 1);
+            const int e = min(tid + u * NT, NE - 1);
             const int at = wave_block(e / (MU * 16)) * MU + (e / 16) % MU;
             en_qt[u] = plan.unit_tile[at];
             en_half[u] = plan.unit_half[at];
@@ -1066,11 +1071,15 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     };
     if (kEntriesEarly)
         fetch_entries();
-    double *part_ll = Gs;                               // [NW][MU][16]
-    // compensated sp_j parts (SPO: where the last contraction left them -- behind part_ll if that is buffer 0)
-    double *part_hi = !SPO ? Gs + (size_t)NW * MU * 16
-                           : (plan.n_buf == 2 ? Gs + ((t_end + 1) & 1) * kTileBins * LD : Gs + 2 * LD) + NW * MU * 16;
-    double *part_lo = part_hi + (size_t)NW * MU * 16;
+    // compensated sp_j parts (SPO: where the last contraction left them).  (The layout made afresh here, its row stride
+    // pinned by the empty asm: the choice of the SPO parts' place, hoisted into the walk, cost it 25 spilled registers.)
+    int ld_end = LD;
+    if (SPO && LDC == 0)
+        asm volatile("" : "+s"(ld_end));
+    const FactoredLds lay_end{NT, plan.n_buf, ld_end, SPO};
+    double *part_ll = Gs + lay_end.part_ll();
+    double *part_hi = Gs + lay_end.part_hi(t_end);
+    double *part_lo = Gs + lay_end.part_lo(t_end);
     // (the slots' first weights are in the registers: they do not depend on the key tile, and every interval that used
     // them up fetched them again behind its logs -- until round 5 they were loaded once more here, a round trip to the
     // cache in front of every workgroup's results.  A NaN column is a NaN in them)
@@ -1166,10 +1175,10 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     if (kEntriesEarly) {
 #pragma unroll
         for (int u = 0; u < kEntries; ++u)
-            if (tid + u * NT < NW * MU * 16)
+            if (tid + u * NT < NE)
                 finish_entry(tid + u * NT, en_qt[u], en_half[u], en_cont[u], en_pair[u], en_qo[u]);
     } else {
-        for (int e = tid; e < NW * MU * 16; e += NT) {
+        for (int e = tid; e < NE; e += NT) {
             const int at = wave_block(e / (MU * 16)) * MU + (e / 16) % MU;
             // (the entry's four words fetched together: behind `||` each waited for the one before)
             const int qt = plan.unit_tile[at], e_half = plan.unit_half[at], e_cont = plan.unit_cont[at];
@@ -1321,11 +1330,10 @@ hipError_t launch_ll_factored_variant(const DevModel &m, const TileView &tv, con
                                       double *out_ll, const SubList &sub_list, hipStream_t stream)
 {
     constexpr int HU = kHalfUnits;
-    // + 64 zeroed doubles: the last piece of a unit may run a few (masked, weight 0) steps past the end
-    // of a G row; what it reads there must be finite
-    // (the per-q combine at the end reuses the buffer for three [waves][slots][16] arrays)
-    const size_t lds = std::max((size_t)plan.n_buf * kTileBins * plan.ld + 64, (size_t)3 * (NT / kWave) * 2 * HU * 16) *
-                       sizeof(double);
+    const FactoredLds lay{NT, plan.n_buf, plan.ld, PLAIN && TAIL}; // (tiles.h)
+    if (!lay.fits())
+        return hipErrorInvalidValue;
+    const size_t lds = (size_t)lay.total() * sizeof(double);
     // the dynamic-LDS ceiling is a per-device attribute of the kernel: raise it once per device
     static size_t configured[64] = {0};
     static std::mutex configured_lock; // two model handles may be used from two host threads
@@ -1380,6 +1388,45 @@ extern template hipError_t launch_ll_factored_variant<512, false, true, kLdWide>
 extern template hipError_t launch_ll_factored_variant<512, true, true, kLdWide>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
 
 namespace {
+
+// The layout of tiles.h FactoredLds over the shapes the planners make (row strides 34 .. 546, both workgroup sizes, one
+// and two buffers, with and without SPO, both parities of the walk's length): every area inside the allocation, the SPO
+// parts clear of what the last interval still reads -- the buffer it contracts (one buffer: the two rows of S in it) --
+// and of the slack, part_ll clear of part_hi / part_lo, and the allocation within the CU's LDS wherever the planners
+// choose that n_buf.
+constexpr bool lds_overlap(int a0, int a1, int b0, int b1) { return a0 < b1 && b0 < a1; }
+constexpr bool factored_lds_sound()
+{
+    for (int nt = 256; nt <= 512; nt += 256)
+        for (int n_buf = 1; n_buf <= 2; ++n_buf)
+            for (int k = 1; k <= 17; ++k)
+                for (int spo = 0; spo <= 1; ++spo)
+                    for (int t_end = 1; t_end <= 2; ++t_end) {
+                        const FactoredLds l{nt, n_buf, kTileBins * k + 2, spo != 0};
+                        const int ne = l.entries(), total = l.total();
+                        if (l.buf(n_buf - 1) + kTileBins * l.ld > l.slack() || l.slack() + FactoredLds::kSlack > total ||
+                            l.rates() + FactoredLds::kRates > total || l.pad(l.rows() - 1) + 2 > l.slack())
+                            return false;
+                        if (l.part_ll() + ne > total || l.part_hi(t_end) + ne > total || l.part_lo(t_end) + ne > total ||
+                            lds_overlap(l.part_ll(), l.part_ll() + ne, l.part_hi(t_end), l.part_lo(t_end) + ne))
+                            return false;
+                        if (spo) {
+                            const int s0 = l.spo_parts(t_end), s1 = s0 + 2 * ne, live = l.buf(t_end);
+                            if (s1 > total || lds_overlap(s0, s1, l.slack(), l.slack() + FactoredLds::kSlack) ||
+                                lds_overlap(s0, s1, live, live + (n_buf == 2 ? kTileBins : 2) * l.ld))
+                                return false;
+                            const int other = l.buf(t_end + 1);
+                            if (n_buf == 2 && s0 < l.slack() && (s0 < other || s1 > other + kTileBins * l.ld))
+                                return false;
+                        }
+                        if (factored_n_buf(l.ld) == n_buf && !l.fits())
+                            return false;
+                    }
+    return true;
+}
+static_assert(factored_lds_sound(), "K-factored's LDS layout (tiles.h FactoredLds)");
+// the headline shape (C3: 512 threads, plain, no tail, kLdWide) allocates two buffers and the slack, as it always has
+static_assert(FactoredLds{512, 2, kLdWide, false}.total() == 2 * kTileBins * kLdWide + FactoredLds::kSlack, "C3's LDS");
 
 template <int NT>
 hipError_t launch_nt(const DevModel &m, const TileView &tv, const FactoredPlan &plan, double *out_ll,

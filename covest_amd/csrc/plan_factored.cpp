@@ -89,8 +89,8 @@ int build_plan_part(covest_grid *g, const double *const *axes, const std::vector
     const int pass_stride = ((max_o + 3) / 4) * 4; // a pass begins on an MFMA step
     const int n_columns = n_pass == 1 ? max_o : n_pass * pass_stride;
     // ---- deal (q-tile, half) units to the waves of a workgroup (tiles.h) ----
-    const int ld = ((n_columns + 31) / 32) * 32 + 2;
-    const int n_buf = (2 * (size_t)kTileBins * ld + 64) * sizeof(double) + 13440 <= 160 * 1024 ? 2 : 1; // (+ the kernel's static LDS: log table, hand-back records, row constants)
+    const int ld = factored_ld(n_columns);
+    const int n_buf = factored_n_buf(ld);
     const int n_units = 2 * n_qtiles;
     const int hu = kHalfUnits; // (768 threads with 2 slots per half, 3 waves/SIMD, was measured: +1 %)
     const int mu = 2 * hu;
@@ -350,8 +350,8 @@ int build_plan_part(covest_grid *g, const double *const *axes, const std::vector
     pl.ld = ld;
     pl.n_buf = n_buf;
 #ifdef COVEST_DIAG
-    if (std::getenv("COVEST_FACTORED_NBUF"))
-        pl.n_buf = std::atoi(std::getenv("COVEST_FACTORED_NBUF"));
+    if (std::getenv("COVEST_FACTORED_NBUF")) // (one buffer, or two where they fit)
+        pl.n_buf = std::max(1, std::min(n_buf, std::atoi(std::getenv("COVEST_FACTORED_NBUF"))));
 #endif
     int32_t *ub = ibase + 2 * n_slots;
     pl.unit_tile = ub;
@@ -572,8 +572,8 @@ int build_list_plan(covest_model *m, int64_t n, const double *params, const std:
     int t_max = 1; // largest LOCAL threshold: copy numbers of an item are o_base + 1 .. o_base + t_local - 1
     for (int64_t i = 0; i < n; ++i)
         t_max = std::max(t_max, std::min(513, (int)t_list[(size_t)i] - o_base_of(i)));
-    const int ld = ((t_max - 1 + 31) / 32) * 32 + 2;
-    const int n_buf = (2 * (size_t)kTileBins * ld + 64) * sizeof(double) + 13440 <= 160 * 1024 ? 2 : 1; // (+ the kernel's static LDS: log table, hand-back records, row constants)
+    const int ld = factored_ld(t_max - 1);
+    const int n_buf = factored_n_buf(ld);
     const size_t n_slots = (size_t)n * 16, n_blocks = 1 + 2 * (size_t)n, n_unit = n_blocks * MU;
     std::vector<double> axes(2 * (size_t)n), r4(n_slots, 0.0), piece_w(n_unit * 64 * 2, 0.0);
     std::vector<int32_t> q_t(n_slots, 0), q_orig(n_slots, -1), unit_tile(n_unit, -1), unit_half(n_unit, 0),

@@ -228,6 +228,62 @@ struct FactoredPlan {
     int32_t skip_phases;           // (env COVEST_FACTORED_SKIP) bit 0/1/2 skips phase A/B/C, bit 3 the shared steps; results are wrong
 };
 
+// K-factored's LDS (ll_factored.hip): the one definition the planners (n_buf), the launcher (the allocation) and the
+// kernel (every offset into its dynamic LDS) read.  The kernel's static __shared__ arrays (log table, hand-back
+// records, row constants, shared-step constants) take at most kFactoredStaticLds bytes: the kernel asserts it.
+constexpr int kLdsBytes = 160 * 1024;       // LDS of a CU, all of it one workgroup's at most
+constexpr int kFactoredStaticLds = 13440;   // bytes
+
+// G's row stride for `columns` columns: whole MFMA-friendly rows plus two pad columns (= 4 dwords mod 64: the
+// A fragments' ds_read_b64 are conflict-free)
+constexpr __host__ __device__ int factored_ld(int columns) { return (columns + kTileBins - 1) / kTileBins * kTileBins + 2; }
+
+// The dynamic LDS of a workgroup of nt threads, in doubles from its start:
+//   buffers   n_buf x [kTileBins rows][ld] of G, the rows' two pad columns kept finite (zeroed)
+//   slack     kSlack zeroed doubles behind the buffers: the last piece of a unit may run a few masked (weight 0) steps
+//             past the end of a row, and the shared steps read a head that does not exist from here
+//   rates     the prologue's error-class rates (8 a pass, at most 4 passes), read before any buffer is written
+//   SPO parts [2][entries] (SPO: a plain grid with a tail) the units' shares of sp_j, written in the last interval (it
+//             contracts S) and read by the combine: in the buffer that interval does NOT contract, behind part_ll -- with
+//             one buffer, behind the two rows of S, whose products are the only ones used -- wherever that holds them,
+//             else behind the slack
+//   combine   part_ll [entries] at 0 and part_hi / part_lo [entries] each behind it (SPO: the SPO parts), after the walk
+// entries = waves x accumulator slots x 16 weight vectors.  t_end: the items of the walk (the last interval's position).
+struct FactoredLds {
+    int nt, n_buf, ld;
+    bool spo;
+    static constexpr int kSlack = 64;
+    static constexpr int kRates = 32;
+    __host__ __device__ static constexpr int entries_of(int nt) { return nt / 64 * kMaxUnits * 16; }
+    __host__ __device__ constexpr int entries() const { return entries_of(nt); }
+    __host__ __device__ constexpr int rows() const { return n_buf * kTileBins; } // of all buffers together
+    __host__ __device__ constexpr int buf(int b) const { return n_buf == 2 ? (b & 1) * kTileBins * ld : 0; }
+    __host__ __device__ constexpr int pad(int row) const { return row * ld + ld - 2; } // a row's two pad columns
+    __host__ __device__ constexpr int slack() const { return n_buf * kTileBins * ld; }
+    __host__ __device__ constexpr int rates() const { return 0; }
+    __host__ __device__ constexpr bool spo_inside() const
+    {
+        return kTileBins * ld >= (n_buf == 2 ? 0 : 2 * ld) + 3 * entries();
+    }
+    __host__ __device__ constexpr int spo_parts(int t_end) const
+    {
+        return !spo_inside() ? slack() + kSlack : n_buf == 2 ? buf(t_end + 1) + entries() : 2 * ld + entries();
+    }
+    __host__ __device__ constexpr int part_ll() const { return 0; }
+    __host__ __device__ constexpr int part_hi(int t_end) const { return spo ? spo_parts(t_end) : entries(); }
+    __host__ __device__ constexpr int part_lo(int t_end) const { return part_hi(t_end) + entries(); }
+    __host__ __device__ constexpr int total() const
+    {
+        const int a = slack() + kSlack, b = 3 * entries(), c = spo && !spo_inside() ? slack() + kSlack + 2 * entries() : 0;
+        return a > b ? (a > c ? a : c) : (b > c ? b : c);
+    }
+    __host__ __device__ constexpr bool fits() const { return total() * (int)sizeof(double) + kFactoredStaticLds <= kLdsBytes; }
+};
+
+// 2 when G may be double-buffered at row stride ld: in the largest workgroup's layout, SPO parts included, so that
+// every variant fits
+constexpr __host__ __device__ int factored_n_buf(int ld) { return FactoredLds{512, 2, ld, true}.fits() ? 2 : 1; }
+
 #ifdef COVEST_DIAG
 #define COVEST_SKIP_PHASE(plan, bits) (((plan).skip_phases & (bits)) != 0)
 #else

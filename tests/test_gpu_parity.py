@@ -980,6 +980,55 @@ def test_round5_tail_paths_on_awkward_shapes(hip_lib, oracle):
             m.close()
 
 
+def test_factored_spo_parts_at_small_row_strides(hip_lib, oracle):
+    """K-factored's SPO parts (a plain grid with a tail: the units' shares of sp_j, tiles.h FactoredLds) at the row
+    strides where the buffer the last interval does not contract cannot hold them: ld = 34 with 512 threads (216 weight
+    vectors) and with 256 (16).  192 (c, e) pairs: one workgroup takes all of a (c, e)'s units (plan_factored.cpp
+    want_blocks), so that every wave's entries are used.  Histograms on keys 1 .. 32 t, t = 1 .. 4, so that the walk ends
+    in either buffer; the c axis reaches -inf where the keys allow it (t >= 3).  K-factored against K-direct on the whole grid: IEEE specials
+    in the same places, finite values at 1e-10 (or within the graded tail slack where the tail term is ill-conditioned),
+    the same arg-min."""
+    from covest_amd import DenseGrid, RepeatsModel
+
+    def falling(keys, top):
+        return {int(j): max(1, int(top * math.exp(-0.07 * i))) for i, j in enumerate(keys)}
+
+    tail = 5
+    cs, es = np.exp(np.linspace(np.log(0.01), np.log(30.0), 16)), np.linspace(0.01, 0.12, 12)
+    q_axes = {"216 vectors": [np.linspace(0.0, 1.0, 6), np.linspace(0.0, 1.0, 6), np.linspace(0.5, 0.95, 6)],
+              "16 vectors": [np.array([0.2, 0.7]), np.array([0.3, 0.9]), np.linspace(0.5, 0.95, 4)]}
+    n_neginf = 0
+    for t in (1, 2, 3, 4):
+        hist = falling(range(1, 32 * t + 1), 20000)
+        m = RepeatsModel(21, 100, hist, tail, max_error=8)
+        om = oracle.OracleModel("repeats", 21, 100, hist, tail, max_error=8)
+        for qname, qs in q_axes.items():
+            name = "SPO parts, %d keys, %s" % (32 * t, qname)
+            grid = DenseGrid(m, [cs, es] + qs)
+            grid.evaluate(kernel="factored")
+            assert grid.work()[2] == "ll_factored", name
+            fast, best = grid.loglikelihoods(), grid.argmin()
+            grid.evaluate(kernel="direct")
+            ref = grid.loglikelihoods()
+            assert np.array_equal(np.isneginf(fast), np.isneginf(ref)) and np.array_equal(np.isnan(fast), np.isnan(ref)), name
+            fin = np.isfinite(ref)
+            assert fin.any(), name
+            n_neginf += int(np.isneginf(ref).sum())
+            # the graded tail slack (from the oracle's sp_j) only for the points beyond 1e-10
+            off = [int(i) for i in np.flatnonzero(fin) if rel_err(float(fast[i]), float(ref[i])) > 1e-10]
+            slack = [0.0] * grid.total
+            if off:
+                pts = np.array([grid.point(i) for i in off])
+                for i, s in zip(off, _tail_noise(om, pts, ref[off], tail)):
+                    slack[i] = s
+            _check(fast, ref, name + " vs direct", tol=1e-10, slack=slack)
+            k_ref = int(np.argmin(np.where(np.isnan(ref), np.inf, -ref)))
+            assert best[1] == k_ref or rel_err(float(fast[best[1]]), float(ref[k_ref])) <= TOL, name
+            grid.close()
+        m.close()
+    assert n_neginf > 0  # the grids do hold -inf points
+
+
 def test_selection_scan_on_the_device(hip_lib):
     """covest_grid_eval_scan / covest_grid_scan (include/covest_amd.h): the records the device lists are exactly where
     the reference's selection loop (covest/grid.py:65-70) changes its state, for any starting minimum -- replayed, the
