@@ -28,6 +28,7 @@ EXPORTS = (
     "covest_grid_ll_device",
     "covest_grid_ll_host",
     "covest_grid_work", "covest_grid_profile", "covest_grid_kernel_ms", "covest_grid_diag",
+    "covest_grid_launch_record", "covest_model_launch_record", "covest_compiled_variants",
     "covest_kmer_create", "covest_kmer_destroy", "covest_kmer_reserve", "covest_kmer_add",
     "covest_kmer_add_device", "covest_kmer_histogram", "covest_kmer_slots", "covest_kmer_clear",
     "covest_kmer_count_reads_device", "covest_kmer_partition_info", "covest_kmer_partition_ms", "covest_kmer_memory_limit",
@@ -197,6 +198,12 @@ def lib():
                                               i64, dp, ctypes.c_int32, dp]
     L.covest_grid_diag.restype = i64
     L.covest_grid_diag.argtypes = [vp, ctypes.POINTER(i64), i64]
+    L.covest_grid_launch_record.restype = i64
+    L.covest_grid_launch_record.argtypes = [vp, ctypes.c_char_p, i64]
+    L.covest_model_launch_record.restype = i64
+    L.covest_model_launch_record.argtypes = [vp, ctypes.c_char_p, i64]
+    L.covest_compiled_variants.restype = i64
+    L.covest_compiled_variants.argtypes = [ctypes.c_char_p, i64]
     _lib = L
     return L
 
@@ -247,6 +254,34 @@ def check(status, what):
     if status != 0:
         msg = lib().covest_last_error()
         raise CovestHipError("%s failed (%d): %s" % (what, status, (msg or b"").decode()))
+
+
+def _text(query, what):
+    """The text a covest_*_record / covest_compiled_variants call returns (asked for its length first)."""
+    n = query(None, 0)
+    if n < 0:
+        check(n, what)
+    buf = ctypes.create_string_buffer(n + 1)
+    check(0 if query(buf, n + 1) == n else COVEST_E_INVALID, what)
+    return buf.value.decode()
+
+
+def parse_launch_record(text):
+    """A launch record (include/covest_amd.h) as {"launches": {instantiation: launches}, "plans": [{field: int}]}."""
+    launches, plans = {}, []
+    for line in text.splitlines():
+        kind, _, rest = line.partition(" ")
+        if kind == "launch":
+            name, count = rest.rsplit(" ", 1)
+            launches[name] = launches.get(name, 0) + int(count)
+        elif kind == "plan":
+            plans.append({k: int(v) for k, v in (f.split("=") for f in rest.split())})
+    return {"launches": launches, "plans": plans}
+
+
+def compiled_variants():
+    """Every instantiation of the likelihood kernels linked into the library (covest_compiled_variants)."""
+    return _text(lambda b, c: lib().covest_compiled_variants(b, c), "covest_compiled_variants").split()
 
 
 def device_count():

@@ -317,6 +317,7 @@ static int grid_eval(covest_grid *g, int32_t kernel, void *stream, bool scan, do
     int rc = dev_guard.status();
     if (rc != COVEST_OK)
         return rc;
+    LaunchRecordScope record(g->record);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t n = g->flat_end - g->flat_begin;
     if (g->upload_pending && st != nullptr && g->upload_ev)
@@ -433,6 +434,13 @@ int covest_grid_scan(covest_grid *g, int32_t cap, int64_t *index, double *negll,
     }
     *n_records = take;
     return COVEST_OK;
+}
+
+int64_t covest_grid_launch_record(const covest_grid *g, char *buf, int64_t cap)
+{
+    if (!g || cap < 0 || (cap > 0 && !buf))
+        return fail(COVEST_E_INVALID, "covest_grid_launch_record: bad argument");
+    return launch_record_text(g->record, buf, cap);
 }
 
 int covest_grid_argmin(covest_grid *g, double *min_negll, int64_t *argmin_flat)

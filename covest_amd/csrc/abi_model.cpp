@@ -216,6 +216,7 @@ static hipError_t launch_factored_grid(covest_grid *g, double *out, const SubLis
 {
     const covest_model *m = g->model;
     if (g->has_short_part) {
+        record_factored_plan(g->plan, g->n_shared_tiles, false);
         hipError_t e = launch_ll_factored(m->dm, m->tv, g->plan, out, sub, st);
         if (e != hipSuccess)
             return e;
@@ -231,6 +232,8 @@ static hipError_t launch_factored_grid(covest_grid *g, double *out, const SubLis
         hipError_t e = g->long_partial.reserve((size_t)(batch * per_ce));
         if (e != hipSuccess)
             return e;
+        for (const covest_grid::Part &part : g->long_parts)
+            record_factored_plan(part.plan, 0, true);
         for (int64_t first = ce_begin; first < ce_end; first += batch) {
             const int64_t last = std::min(ce_end, first + batch);
             for (covest_grid::Part &part : g->long_parts) {
@@ -382,6 +385,7 @@ int covest_eval_points(covest_model *m, int64_t n, const double *params, double 
     int rc = dev_guard.status();
     if (rc != COVEST_OK)
         return rc;
+    LaunchRecordScope record(m->record);
     const int P = m->n_par;
     // A SMALL list (what scipy's refinement issues: a point and its P finite-difference neighbours) moves nothing through
     // the copy engine (round 5): its parameters are read, and its values written, IN PLACE in page-locked host memory
@@ -470,6 +474,7 @@ int covest_eval_points(covest_model *m, int64_t n, const double *params, double 
             m->ws_result.flags = hipHostMallocPortable | hipHostMallocMapped;
             HIP_TRY(m->ws_result.reserve(n_parts * 4 * sizeof(double)));
             pl.partial = m->ws_result.as<double>();
+            record_factored_plan(pl, 0, false);
             HIP_TRY(launch_ll_factored(m->dm, m->tv, pl, m->ws_out.as<double>(), queue, nullptr));
             HIP_TRY(hipStreamSynchronize(nullptr));
             const double *got = m->ws_result.as<double>();
@@ -540,6 +545,7 @@ int covest_eval_points(covest_model *m, int64_t n, const double *params, double 
             pl.list_mode = 2;
             pl.item_obase = reinterpret_cast<const int32_t *>(ib);
             pl.partial = m->ws_partial.as<double>();
+            record_factored_plan(pl, 0, false);
             HIP_TRY(launch_ll_factored(m->dm, m->tv, pl, m->ws_out.as<double>(), queue, nullptr));
             HIP_TRY(launch_ll_finish_partials(m->dm, m->tv, pl.partial, reinterpret_cast<const int32_t *>(ib + items_bytes),
                                               reinterpret_cast<const double *>(ib + int_bytes),
@@ -576,6 +582,14 @@ int covest_eval_points(covest_model *m, int64_t n, const double *params, double 
         HIP_TRY(hipMemcpy(out_ll, out_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     }
     return COVEST_OK;
+}
+
+int64_t covest_model_launch_record(covest_model *m, char *buf, int64_t cap)
+{
+    if (!m || cap < 0 || (cap > 0 && !buf))
+        return fail(COVEST_E_INVALID, "covest_model_launch_record: bad argument");
+    std::lock_guard<std::mutex> guard(m->lock);
+    return launch_record_text(m->record, buf, cap);
 }
 
 int covest_reference_overflow(const covest_model *m, int64_t n, const double *params, uint8_t *flags)

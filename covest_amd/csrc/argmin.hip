@@ -590,6 +590,11 @@ __global__ __launch_bounds__(kSmallThreads) void argmin_scan_small(const double 
 
 } // namespace
 
+// the instantiations of this file's dispatchers, by name (the launch record, covest_compiled_variants)
+const char *const kFixVariantNames[kFixVariants] = {"fix_basic_packed<8>",  "fix_basic_packed<16>", "fix_basic_packed<24>",
+                                                    "fix_basic_packed<32>", "fix_list<2,1>",        "fix_list<5,1>"};
+const char *const kArgminVariantNames[kArgminVariants] = {"argmin_small", "argmin_stage1+2", "argmin_scan_small"};
+
 hipError_t launch_argmin_scan(const double *ll, int64_t n, int64_t flat_begin, double start, ArgminResult *result,
                               ArgminResult *host_mirror, ScanRecords *scan, unsigned *queue_count, hipStream_t stream)
 {
@@ -607,6 +612,7 @@ hipError_t launch_argmin_scan(const double *ll, int64_t n, int64_t flat_begin, d
             return e;
         raised[dev] = true;
     }
+    record_launch(kArgminVariantNames[2]);
     hipLaunchKernelGGL(argmin_scan_small, dim3(1), dim3(kSmallThreads), lds, stream, ll, n, flat_begin, start, result, host_mirror, scan,
                        queue_count);
     return hipGetLastError();
@@ -626,18 +632,22 @@ hipError_t launch_ll_fix_list(const DevModel &m, const TileView &tv, const Point
             hipLaunchKernelGGL(kern, dim3(packed_blocks), block, 0, stream, m, tv.n_tiles, tv.n_items, tv.dbl_base, tv.int_base, src,
                                ll, list);
         };
+        record_launch(kFixVariantNames[m.n_err == 8 ? 0 : m.n_err == 16 ? 1 : m.n_err == 24 ? 2 : 3]); // (the switch below)
         switch (m.n_err) {
         case 8: go(ll_fix_basic_packed_kernel<8>); break;
         case 16: go(ll_fix_basic_packed_kernel<16>); break;
         case 24: go(ll_fix_basic_packed_kernel<24>); break;
         default: go(ll_fix_basic_packed_kernel<32>); break;
         }
-    } else if (m.kind == 0)
+    } else if (m.kind == 0) {
+        record_launch(kFixVariantNames[4]);
         hipLaunchKernelGGL((ll_fix_list_kernel<2, 1>), grid, block, 0, stream, m, tv.n_tiles, tv.n_items, tv.dbl_base,
                            tv.int_base, src, ll, list);
-    else
+    } else {
+        record_launch(kFixVariantNames[5]);
         hipLaunchKernelGGL((ll_fix_list_kernel<5, 1>), grid, block, 0, stream, m, tv.n_tiles, tv.n_items, tv.dbl_base,
                            tv.int_base, src, ll, list);
+    }
     return hipGetLastError();
 }
 
@@ -645,6 +655,7 @@ hipError_t launch_argmin(const double *ll, int64_t n, int64_t flat_begin, double
                          ArgminResult *result, ArgminResult *host_mirror, unsigned *queue_count, hipStream_t stream)
 {
     if (n <= kArgminSmall) {
+        record_launch(kArgminVariantNames[0]);
         hipLaunchKernelGGL(argmin_small, dim3(1), dim3(kSmallThreads), 0, stream, ll, n, flat_begin, result, host_mirror, queue_count);
         return hipGetLastError();
     }
@@ -653,6 +664,7 @@ hipError_t launch_argmin(const double *ll, int64_t n, int64_t flat_begin, double
     // (measured and not kept, round 4: both stages in ONE launch -- every workgroup stores its candidate, adds to a
     // counter behind a fence, the workgroup whose add came last reduces the candidates -- is 20-27 us SLOWER a step than
     // the second launch it saves: 1 024 agent-scope fences cost more than a 4 us launch)
+    record_launch(kArgminVariantNames[1]);
     hipLaunchKernelGGL(argmin_stage1, dim3(blocks), dim3(256), 0, stream, ll, n, partial_val, partial_idx);
     hipLaunchKernelGGL(argmin_stage2, dim3(1), dim3(256), 0, stream, partial_val, partial_idx, blocks, flat_begin, result,
                        host_mirror, queue_count);

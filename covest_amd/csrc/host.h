@@ -238,6 +238,7 @@ struct covest_model {
     HostBuf ws_stage; // staging of a point list's tables (build_list_plan)
     HostBuf ws_result; // page-locked, device-mapped: what a point-list launch leaves for the host (list mode 1's parts)
     DevBuf ws_sub_index, ws_sub_word, ws_sub_ctl; // the queue of handed-back points of a point-list launch (direct_point.h)
+    LaunchRecord record; // what the last covest_eval_points launched (covest_model_launch_record)
     std::mutex lock;
 };
 
@@ -265,12 +266,14 @@ struct covest_grid {
     };
     std::vector<Part> long_parts;
     int32_t n_long_tiles = 0;
+    int32_t n_shared_tiles = 0; // q-tiles of the short part with shared steps (tiles.h; the launch record)
     std::vector<int32_t> long_q_orig_host;
     DevBuf long_q_orig, long_partial;
     int t_max = 2; // largest threshold_o of the (q1, q2, q) product
     double q_sum_t_minus_1 = 0.0; // sum over the Q weight vectors of (threshold_o - 1)
     double contract_flops_per_row = 0.0; // K-factored: useful flops of the contraction per row (build_factored_plan)
     double sum_t_minus_1 = 0.0; // sum over the block's points of (threshold_o - 1)
+    LaunchRecord record; // what the last covest_grid_eval launched (covest_grid_launch_record)
     const char *last_kernel = "none";
     int last_kernel_id = 0;
     hipStream_t last_stream = nullptr;
@@ -334,6 +337,8 @@ int threshold_for_point(const covest_model *m, const double *par);
 void lgamma_ensure(int64_t j_max);
 double lgamma_at(int64_t j); // (after lgamma_ensure(j) or larger)
 double lgamma_of_factorial(int64_t j);
+
+int64_t launch_record_text(const LaunchRecord &r, char *buf, int64_t cap); // (kernels.h)
 
 // ---- tiles_host.cpp
 constexpr int64_t kListModeMaxPoints = 4096; // longer point lists are throughput work: K-direct

@@ -292,9 +292,93 @@ double lgamma_of_factorial(int64_t j)
     return lgamma_at(j);
 }
 
+// ---- the launch record (kernels.h)
+namespace {
+thread_local LaunchRecord *tls_record = nullptr;
+} // namespace
+
+LaunchRecordScope::LaunchRecordScope(LaunchRecord &r) : prev(tls_record)
+{
+    r.clear();
+    tls_record = &r;
+}
+LaunchRecordScope::~LaunchRecordScope() { tls_record = prev; }
+
+void record_launch(const char *name, int64_t launches)
+{
+    LaunchRecord *r = tls_record;
+    if (!r || launches <= 0)
+        return;
+    for (int i = 0; i < r->n_entries; ++i)
+        if (r->entries[i].name == name) { // (the names are the tables' own pointers)
+            r->entries[i].launches += launches;
+            return;
+        }
+    if (r->n_entries < (int)(sizeof r->entries / sizeof r->entries[0]))
+        r->entries[r->n_entries++] = LaunchRecord::Entry{name, launches};
+}
+
+void record_factored_plan(const FactoredPlan &plan, int shared_tiles, bool long_part)
+{
+    LaunchRecord *r = tls_record;
+    if (!r || r->n_plans >= (int)(sizeof r->plans / sizeof r->plans[0]))
+        return;
+    r->plans[r->n_plans++] = LaunchRecord::Plan{plan.n_threads, plan.n_buf,  plan.ld,        plan.n_qblocks,
+                                                shared_tiles,   plan.n_pass, plan.list_mode, long_part};
+}
+
+// "launch <name> <count>" and "plan <key>=<value> ..." lines; the whole text's length is returned, at most cap - 1
+// characters of it are written to buf, behind them a NUL
+int64_t launch_record_text(const LaunchRecord &r, char *buf, int64_t cap)
+{
+    std::string t;
+    char line[256];
+    for (int i = 0; i < r.n_entries; ++i) {
+        std::snprintf(line, sizeof line, "launch %s %lld\n", r.entries[i].name, (long long)r.entries[i].launches);
+        t += line;
+    }
+    for (int i = 0; i < r.n_plans; ++i) {
+        const LaunchRecord::Plan &p = r.plans[i];
+        std::snprintf(line, sizeof line,
+                      "plan n_threads=%d n_buf=%d ld=%d n_qblocks=%d shared_tiles=%d long=%d n_pass=%d list_mode=%d\n",
+                      p.n_threads, p.n_buf, p.ld, p.n_qblocks, p.shared_tiles, p.long_part ? 1 : 0, p.n_pass, p.list_mode);
+        t += line;
+    }
+    if (buf && cap > 0) {
+        const size_t n = std::min<size_t>(t.size(), (size_t)(cap - 1));
+        std::memcpy(buf, t.data(), n);
+        buf[n] = '\0';
+    }
+    return (int64_t)t.size();
+}
+
 } // namespace covest
 
 extern "C" {
+
+int64_t covest_compiled_variants(char *buf, int64_t cap)
+{
+    if (cap < 0 || (cap > 0 && !buf))
+        return fail(COVEST_E_INVALID, "covest_compiled_variants: bad argument");
+    std::string t;
+    auto add = [&](const char *const *names, int n) {
+        for (int i = 0; i < n; ++i) {
+            t += names[i];
+            t += '\n';
+        }
+    };
+    add(kFactoredVariantNames, kFactoredVariants);
+    add(kFactoredFinishNames, 2);
+    add(kBasicVariantNames, kBasicVariants);
+    add(kFixVariantNames, kFixVariants);
+    add(kArgminVariantNames, kArgminVariants);
+    if (buf && cap > 0) {
+        const size_t n = std::min<size_t>(t.size(), (size_t)(cap - 1));
+        std::memcpy(buf, t.data(), n);
+        buf[n] = '\0';
+    }
+    return (int64_t)t.size();
+}
 
 int covest_abi_version(void) { return COVEST_ABI_VERSION; }
 

@@ -9,6 +9,41 @@
 
 namespace covest {
 
+// ---- The launch record (covest_grid_launch_record, covest_model_launch_record): what an evaluation launched ----
+// Host bookkeeping only.  A launcher notes the instantiation it picked and how many launches it took into the record
+// of the evaluation in progress on the calling thread (LaunchRecordScope; none: nothing is noted).  Nothing is read from
+// the device and nothing waits for it.  The names come from the tables beside the instantiation lists (kVariantNames of
+// ll_factored.hip, ll_basic.hip and argmin.hip); covest_compiled_variants lists those tables.
+struct LaunchRecord {
+    struct Entry {
+        const char *name;
+        int64_t launches;
+    };
+    struct Plan { // a K-factored work description as the host built it (tiles.h FactoredPlan)
+        int32_t n_threads, n_buf, ld, n_qblocks, shared_tiles, n_pass, list_mode;
+        bool long_part; // a chunk of the long weight vectors (list_mode 3)
+    };
+    Entry entries[16];
+    int n_entries = 0;
+    Plan plans[8];
+    int n_plans = 0; // (plans beyond the room: counted, not kept)
+    void clear() { n_entries = n_plans = 0; }
+};
+void record_launch(const char *name, int64_t launches = 1);
+void record_factored_plan(const FactoredPlan &plan, int shared_tiles, bool long_part);
+struct LaunchRecordScope { // notes go to `r` (cleared) until the scope ends
+    explicit LaunchRecordScope(LaunchRecord &r);
+    ~LaunchRecordScope();
+    LaunchRecord *prev;
+};
+// The instantiations linked in, by family; a launcher records kXxxVariantNames[its index].
+constexpr int kFactoredVariants = 10, kBasicVariants = 8, kFixVariants = 6, kArgminVariants = 3;
+extern const char *const kFactoredVariantNames[kFactoredVariants]; // ll_factored.hip
+extern const char *const kFactoredFinishNames[2];                   // ll_factored.hip: ll_finish_dense, ll_finish_partials
+extern const char *const kBasicVariantNames[kBasicVariants];       // ll_basic.hip
+extern const char *const kFixVariantNames[kFixVariants];           // argmin.hip
+extern const char *const kArgminVariantNames[kArgminVariants];     // argmin.hip
+
 // K-direct: one wavefront per grid point, one exp per pmf term (ll_direct.hip).
 // out_ll[n]; when out_p != nullptr (n must be 1) also writes p_j for every bin
 // of `m.bins`.

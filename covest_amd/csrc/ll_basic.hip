@@ -467,6 +467,9 @@ extern template void launch_ll_basic_variant<24, false>(COVEST_BASIC_ARGS);
 extern template void launch_ll_basic_variant<24, true>(COVEST_BASIC_ARGS);
 extern template void launch_ll_basic_variant<32, false>(COVEST_BASIC_ARGS);
 extern template void launch_ll_basic_variant<32, true>(COVEST_BASIC_ARGS);
+// their names, in the order of COVEST_BASIC_VARIANT (the launch record, covest_compiled_variants)
+const char *const kBasicVariantNames[kBasicVariants] = {"ll_basic<8>",  "ll_basic<8,tail>",  "ll_basic<16>", "ll_basic<16,tail>",
+                                                        "ll_basic<24>", "ll_basic<24,tail>", "ll_basic<32>", "ll_basic<32,tail>"};
 
 namespace {
 template <int S>
@@ -502,6 +505,7 @@ hipError_t launch_ll_basic(const DevModel &m, const TileView &tv, const PointSou
         else
             part.params = src.params + first * 2;
         const bool tail = m.tail != 0.0;
+        record_launch(kBasicVariantNames[2 * (s_pad / 8 - 1) + (tail ? 1 : 0)]);
         if (s_pad == 16)
             launch_s<16>(tail, grid, stream, m, tv, part, cnt, out_ll + first, sl);
         else if (s_pad == 24)

@@ -71,6 +71,7 @@ hipError_t launch_ll_direct(const DevModel &m, const PointSource &src, int64_t n
             part.t_list = src.t_list ? src.t_list + first : nullptr;
         }
         double *out = out_ll + first;
+        record_launch(ref_overflow && !out_p ? "ll_direct_ref" : "ll_direct"); // (the yardstick: not in the variant tables)
         if (ref_overflow && !out_p) { // COVEST_KERNEL_DIRECT_REF (direct_point.h REF_OVF)
             if (m.kind == 0)
                 hipLaunchKernelGGL((ll_direct_kernel<2, false, true>), grid, block, 0, stream, m, part, cnt, out, out_p);

@@ -1322,6 +1322,9 @@ __global__ __launch_bounds__(kWave) void ll_finish_dense(const DevModel m, const
 
 } // namespace
 
+// HIP wraps a grid of more than 2^32 threads silently: at most 2^22 workgroups per launch ((c, e) rows per launch)
+inline int64_t factored_rows_per_launch(const FactoredPlan &plan) { return std::max<int64_t>(1, ((int64_t)1 << 22) / plan.n_qblocks); }
+
 // One instantiation per translation unit (COVEST_FACTORED_VARIANT, see the end of this file): the HIP runtime
 // loads a translation unit's code object when one of its kernels is first launched, and a process that evaluates a
 // plain dense grid should not pay for the seven other variants (75-98 KB of code each).
@@ -1348,8 +1351,7 @@ hipError_t launch_ll_factored_variant(const DevModel &m, const TileView &tv, con
             return e;
         configured[dev] = lds;
     }
-    // HIP wraps a grid of more than 2^32 threads silently: at most 2^22 workgroups per launch
-    const int64_t per_launch = std::max<int64_t>(1, ((int64_t)1 << 22) / plan.n_qblocks);
+    const int64_t per_launch = factored_rows_per_launch(plan);
     for (int64_t first = plan.ce_begin; first < plan.ce_end; first += per_launch) {
         FactoredPlan part = plan;
         part.ce_begin = first;
@@ -1386,6 +1388,13 @@ extern template hipError_t launch_ll_factored_variant<512, true, false>(const De
 extern template hipError_t launch_ll_factored_variant<512, true, true>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
 extern template hipError_t launch_ll_factored_variant<512, false, true, kLdWide>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
 extern template hipError_t launch_ll_factored_variant<512, true, true, kLdWide>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
+// their names, in the order of COVEST_FACTORED_VARIANT (the launch record, covest_compiled_variants)
+const char *const kFactoredVariantNames[kFactoredVariants] = {
+    "ll_factored<256>", "ll_factored<256,plain>", "ll_factored<256,tail>", "ll_factored<256,tail,plain>",
+    "ll_factored<512>", "ll_factored<512,plain>", "ll_factored<512,tail>", "ll_factored<512,tail,plain>",
+    "ll_factored<512,plain,ld290>", "ll_factored<512,tail,plain,ld290>"};
+const char *const kFactoredFinishNames[2] = {"ll_finish_dense", "ll_finish_partials"};
+static_assert(kLdWide == 290, "kFactoredVariantNames spell the row stride of kLdWide");
 
 namespace {
 
@@ -1433,6 +1442,13 @@ hipError_t launch_nt(const DevModel &m, const TileView &tv, const FactoredPlan &
                      const SubList &sub_list, hipStream_t stream)
 {
     const bool plain = plan.list_mode == 0 && plan.n_pass == 1;
+    {
+        const bool tail = m.tail != 0.0;
+        const int v = NT == 512 && plain && plan.ld == kLdWide ? 8 + (tail ? 1 : 0)
+                                                                : (NT == 512 ? 4 : 0) + (tail ? 2 : 0) + (plain ? 1 : 0);
+        const int64_t rows = plan.ce_end - plan.ce_begin, per_launch = factored_rows_per_launch(plan);
+        record_launch(kFactoredVariantNames[v], (rows + per_launch - 1) / per_launch);
+    }
     if (NT == 512 && plain && plan.ld == kLdWide) // the widest double-buffered shape: its row stride at compile time
         return m.tail != 0.0 ? launch_ll_factored_variant<512, true, true, kLdWide>(m, tv, plan, out_ll, sub_list, stream)
                              : launch_ll_factored_variant<512, false, true, kLdWide>(m, tv, plan, out_ll, sub_list, stream);
@@ -1451,6 +1467,7 @@ hipError_t launch_ll_finish_partials(const DevModel &m, const TileView &tv, cons
 {
     if (n_points <= 0)
         return hipSuccess;
+    record_launch(kFactoredFinishNames[1]);
     hipLaunchKernelGGL(ll_finish_partials, dim3((unsigned)n_points), dim3(kWave), 0, stream, m, tv.n_tiles, tv.n_items, tv.dbl_base,
                        tv.int_base, partial, first_item, point_par, point_T, out_ll);
     return hipGetLastError();
@@ -1464,6 +1481,7 @@ hipError_t launch_ll_finish_dense(const DevModel &m, const TileView &tv, const P
     const int64_t per_launch = std::max<int64_t>(1, ((int64_t)1 << 24) / n_cols);
     for (int64_t first = 0; first < n_ce; first += per_launch) {
         const int64_t cnt = std::min(per_launch, n_ce - first);
+        record_launch(kFactoredFinishNames[0]);
         hipLaunchKernelGGL(ll_finish_dense, dim3((unsigned)(cnt * n_cols)), dim3(kWave), 0, stream, m, tv.n_tiles, tv.n_items,
                            tv.dbl_base, tv.int_base, src, partial + first * n_cols * (int64_t)tv.n_items * kTileBins,
                            ce_first + first, n_cols, q_orig, n_q, flat_end, out_ll);

@@ -538,6 +538,9 @@ int build_factored_plan(covest_grid *g, const double *const *axes, const int64_t
                           hipMemcpyHostToDevice));
     }
     g->has_short_part = n_long_tiles < qo.n_qtiles;
+    g->n_shared_tiles = 0;
+    for (int32_t t = n_long_tiles; t < qo.n_qtiles; ++t)
+        g->n_shared_tiles += qo.tile_nsh[(size_t)t] > 0 ? 1 : 0;
     if (g->has_short_part) {
         const int rc = build_plan_part(g, axes, t_table, qo, n_long_tiles, qo.n_qtiles, 0, chunk, n_pass, 0, g->plan_buf,
                                        g->plan, nullptr);

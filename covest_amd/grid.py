@@ -269,6 +269,13 @@ class DenseGrid:
                                                  ctypes.byref(name)), "covest_grid_work")
         return t.value, f.value, (name.value or b"").decode()
 
+    def launch_record(self):
+        """What the last evaluate() launched: {"launches": {instantiation: launches}, "plans": [K-factored plans]}
+        (covest_grid_launch_record; host bookkeeping, nothing waits for the device)."""
+        L = _capi.lib()
+        return _capi.parse_launch_record(_capi._text(lambda b, c: L.covest_grid_launch_record(self._handle, b, c),
+                                                     "covest_grid_launch_record"))
+
     def profile(self, enable=True):
         """Bracket every likelihood launch with hipEvents (see kernel_ms)."""
         _capi.check(_capi.lib().covest_grid_profile(self._handle, 1 if enable else 0),

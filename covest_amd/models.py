@@ -262,6 +262,13 @@ class BasicModel:
                         "covest_eval_points")
         return out
 
+    def launch_record(self):
+        """What the last loglikelihood_points() launched: {"launches": {instantiation: launches}, "plans": [K-factored
+        plans]} (covest_model_launch_record; host bookkeeping, nothing waits for the device)."""
+        L = _capi.lib()
+        return _capi.parse_launch_record(_capi._text(lambda b, c: L.covest_model_launch_record(self.handle, b, c),
+                                                     "covest_model_launch_record"))
+
     def reference_overflows(self, points):
         """Where the REFERENCE's own evaluation would overflow to inf / NaN (its long-double pmf product is
         formed before it is scaled, c_src/covest_poissonmodule.c:19-24) while this library returns the finite

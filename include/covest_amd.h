@@ -191,6 +191,21 @@ int covest_grid_ll_host(covest_grid *g, double *out_ll);
  * and the name of the kernel that ran. */
 int covest_grid_work(const covest_grid *g, double *pmf_terms, double *flops, const char **kernel);
 
+/* What the last evaluation launched, for tests: covest_grid_launch_record covers the last covest_grid_eval(_scan) of
+ * the handle, covest_model_launch_record the last covest_eval_points of the model.  Text, one line each:
+ *   "launch <instantiation> <launches>"   e.g. "launch ll_factored<512,tail,plain,ld290> 1"
+ *   "plan n_threads=.. n_buf=.. ld=.. n_qblocks=.. shared_tiles=.. long=0|1 n_pass=.. list_mode=.."
+ *     (a K-factored work description: shared_tiles = q-tiles with shared steps, long = a chunk of the long
+ *     weight vectors).
+ * covest_compiled_variants lists every instantiation of the likelihood kernels linked into the library, one name a
+ * line, from the tables the dispatchers record from (K-direct, the yardstick, is recorded as "ll_direct" or
+ * "ll_direct_ref" and not listed).  All three are host bookkeeping: nothing is read from the device.  They write at
+ * most cap - 1 characters and a NUL to buf (cap 0: nothing) and return the length of the whole text, or a negative
+ * error. */
+int64_t covest_grid_launch_record(const covest_grid *g, char *buf, int64_t cap);
+int64_t covest_model_launch_record(covest_model *m, char *buf, int64_t cap);
+int64_t covest_compiled_variants(char *buf, int64_t cap);
+
 /* Device-side timing of the likelihood kernel alone (not the arg-min pass), for
  * roofline reporting: with profiling enabled every covest_grid_eval brackets its
  * likelihood launch with hipEvents on the launch stream; covest_grid_kernel_ms
