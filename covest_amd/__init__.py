@@ -9,3 +9,4 @@ from .grid import DenseGrid, dense_grid_argmin, optimize_grid, initial_grid  # n
 from .hist_steps import (load_histogram, save_histogram, process_histogram, sample_histogram,  # noqa: F401,E402
                          compute_coverage_apx)
 from .report import print_output  # noqa: F401,E402
+from .profile import profile_negll, likelihood_interval, coverage_interval  # noqa: F401,E402

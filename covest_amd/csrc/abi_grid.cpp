@@ -202,6 +202,8 @@ static void grid_release(covest_grid *g)
     }
     g->arena.release();
     g->plan_buf.release();
+    g->axis_buf.release();
+    g->axis_host.release();
     for (covest_grid::Part &part : g->long_parts)
         part.buf.release();
     g->long_parts.clear();
@@ -457,6 +459,52 @@ int covest_grid_argmin(covest_grid *g, double *min_negll, int64_t *argmin_flat)
     const ArgminResult r = *g->result_host; // (the arg-min kernel's own store: covest_grid_eval)
     *min_negll = r.min_negll;
     *argmin_flat = r.index < 0 ? -1 : g->flat_begin + r.index;
+    return COVEST_OK;
+}
+
+int covest_grid_axis_min(covest_grid *g, uint32_t keep_mask, int64_t n_cells, double *min_negll, int64_t *argmin_flat)
+{
+    if (!g || !min_negll || !argmin_flat)
+        return fail(COVEST_E_INVALID, "covest_grid_axis_min: null argument");
+    if (!g->evaluated)
+        return fail(COVEST_E_INVALID, "covest_grid_axis_min: covest_grid_eval has not run");
+    covest_model *m = g->model;
+    if (keep_mask >> m->n_par)
+        return fail(COVEST_E_INVALID, "covest_grid_axis_min: keep_mask names an axis the grid does not have");
+    int64_t cells = 1;
+    for (int d = 0; d < m->n_par; ++d)
+        if ((keep_mask >> d) & 1)
+            cells *= g->len[d];
+    if (n_cells != cells)
+        return fail(COVEST_E_INVALID, "covest_grid_axis_min: n_cells is not the product of the kept axes' lengths");
+    std::lock_guard<std::mutex> guard(m->lock);
+    DeviceGuard dev_guard(m->device);
+    int rc = dev_guard.status();
+    if (rc != COVEST_OK)
+        return rc;
+    AxisMinPlan p;
+    if (!axis_min_plan(g->len, m->n_par, keep_mask, g->flat_begin, g->flat_end, &p))
+        return fail(COVEST_E_INVALID, "covest_grid_axis_min: the axes do not fit a plan");
+    // [min -LL | index] per cell, then the same per (slice, cell) where a cell's points are walked in slices
+    const size_t nc = (size_t)n_cells, n_part = p.n_slices > 1 ? nc * (size_t)p.n_slices : 0;
+    HIP_TRY(g->axis_buf.reserve(16 * (nc + n_part)));
+    double *out_v = g->axis_buf.as<double>();
+    int64_t *out_i = reinterpret_cast<int64_t *>(out_v + nc);
+    double *part_v = reinterpret_cast<double *>(out_i + nc);
+    int64_t *part_i = reinterpret_cast<int64_t *>(part_v + n_part);
+    hipStream_t st = g->last_stream; // (behind the evaluation it reduces)
+    HIP_TRY(launch_axis_min(p, g->ll.as<double>(), part_v, part_i, out_v, out_i, st));
+    if (16 * nc <= ((size_t)1 << 20)) { // one copy into page-locked memory (a pageable target costs a staging per call)
+        HIP_TRY(g->axis_host.reserve(16 * nc));
+        HIP_TRY(hipMemcpyAsync(g->axis_host.ptr, out_v, 16 * nc, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::memcpy(min_negll, g->axis_host.ptr, 8 * nc);
+        std::memcpy(argmin_flat, static_cast<char *>(g->axis_host.ptr) + 8 * nc, 8 * nc);
+    } else {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpy(min_negll, out_v, 8 * nc, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(argmin_flat, out_i, 8 * nc, hipMemcpyDeviceToHost));
+    }
     return COVEST_OK;
 }
 

@@ -14,6 +14,7 @@
 
 #include <algorithm>
 
+#include "cand.h"
 #include "direct_point.h"
 #include "fastmath.h"
 #include "kernels.h"
@@ -22,30 +23,6 @@
 namespace covest {
 
 namespace {
-
-struct Cand {
-    double v;
-    int64_t i;
-};
-
-__device__ __forceinline__ Cand better(Cand a, Cand b)
-{
-    // b replaces a iff b is strictly smaller, or equal with a lower index
-    const bool take = (b.v < a.v) || (b.v == a.v && b.i < a.i);
-    return take ? b : a;
-}
-
-__device__ __forceinline__ Cand wave_best(Cand c)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        Cand o;
-        o.v = __shfl_xor(c.v, off, kWave);
-        o.i = __shfl_xor(c.i, off, kWave);
-        c = better(c, o);
-    }
-    return c;
-}
 
 __device__ __forceinline__ Cand block_best(Cand c)
 {

@@ -249,6 +249,8 @@ struct covest_grid {
     PointSource src{};
     // one allocation (grown on demand, kept across covest_grid_reset) behind the fixed-purpose views below
     DevBuf arena, plan_buf;
+    DevBuf axis_buf;    // covest_grid_axis_min: the per-cell pairs and the (cell, slice) candidates behind them
+    HostBuf axis_host;  // ... and the page-locked block a small result is copied back through
     struct View {
         void *ptr = nullptr;
         template <class T> T *as() const { return static_cast<T *>(ptr); }

@@ -114,6 +114,29 @@ struct ScanRecords {
 hipError_t launch_argmin_scan(const double *ll, int64_t n, int64_t flat_begin, double start, ArgminResult *result,
                               ArgminResult *host_mirror, ScanRecords *scan, unsigned *queue_count, hipStream_t stream);
 
+// ---- K-axis-min (axis_min.hip): the same selection per cell of the product of the KEPT axes of a grid ----
+// The launch description, built on the host by axis_min_plan.  Axes of length 1 dropped and adjacent axes of one side
+// merged, the grid is at most three kept and three reduced groups that alternate; a point's flat index is
+// sum coord * kstride over the kept groups plus sum coord * rstride over the reduced ones.
+struct AxisMinPlan {
+    int32_t n_kept, n_red;         // groups on either side (0..3)
+    int32_t last_kept, first_kept; // the fastest / the slowest group is a kept one
+    int64_t klen[3], kstride[3];   // kept groups in the axes' order: length, stride in the flat index
+    int64_t rlen[3], rstride[3];   // reduced groups
+    int64_t n_cells, n_red_total;  // product of the kept / the reduced lengths
+    int64_t flat_begin, flat_end;  // the block the LL buffer holds (index flat - flat_begin)
+    int64_t lead_lo, lead_hi;      // coordinates of the slowest group the block touches (lo > hi: none)
+    int64_t r_begin, r_end;        // row-major numbers of the reduced coordinates a cell walks
+    int64_t n_slices, per_slice;   // ... in n_slices runs of per_slice: one candidate per (cell, slice)
+};
+// keep_mask: bit d set = axis d is kept.  false: more groups than a plan holds (not with kMaxParams axes).
+bool axis_min_plan(const int64_t *len, int n_axes, uint32_t keep_mask, int64_t flat_begin, int64_t flat_end, AxisMinPlan *out);
+// out_val/out_idx[n_cells]: min -LL and the GLOBAL flat index of the lowest-index point attaining it, (+inf, -1)
+// where no point of the block in the cell is < +inf.  partial_val/partial_idx need n_cells * n_slices entries when
+// n_slices > 1 (else unused).  One launch, two with slices; not entered in the launch record.
+hipError_t launch_axis_min(const AxisMinPlan &p, const double *ll, double *partial_val, int64_t *partial_idx, double *out_val,
+                           int64_t *out_idx, hipStream_t stream);
+
 // ---- K-kmer: k-mer abundance histogram (kmer_count.hip), SURVEY 8(f) row F1 ----
 // Open-addressing table in HBM, slots = 2^log2_slots, one 16-byte entry per slot: {key, count}
 // (key all-ones = empty).  Key and count share a cache line on purpose: a k-mer costs ONE scattered

@@ -132,6 +132,50 @@ def distributed_argmin(local_min, local_idx, group=None, device=None, pair=None)
     return best, int(arg)
 
 
+# --------------------------------------------------------------------------- per-axis minima
+def resolve_keep(params, keep):
+    """The axes named in `keep` -- numbers or parameter names (`params`: model.params), in any order -- as
+    (keep_mask, sorted axis numbers): bit i of the mask set = axis i is kept.  ValueError on a name or number the
+    model does not have and on an axis named twice."""
+    params = tuple(params)
+    picked = []
+    for k in keep:
+        if isinstance(k, str):
+            if k not in params:
+                raise ValueError("keep: %r is not a parameter of the model %r" % (k, params))
+            i = params.index(k)
+        else:
+            i = int(k)
+            if i != k or not 0 <= i < len(params):
+                raise ValueError("keep: axis %r is not one of 0..%d" % (k, len(params) - 1))
+        if i in picked:
+            raise ValueError("keep: axis %d (%s) is named twice" % (i, params[i]))
+        picked.append(i)
+    picked.sort()
+    return sum(1 << i for i in picked), picked
+
+
+def merge_axis_minima(parts):
+    """The per-cell pairs of several blocks of ONE grid (DenseGrid.axis_minima with the same `keep`) combined with
+    the selection rule per cell: the smaller value, then the lower global flat index; an index of -1 ("this block
+    has nothing below +inf in the cell") loses to anything, and a NaN never wins.  Returns (negll, flat_index)."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_axis_minima: no parts")
+    best = np.array(parts[0][0], dtype=np.float64, copy=True)
+    arg = np.array(parts[0][1], dtype=np.int64, copy=True)
+    dead = (arg < 0) | np.isnan(best)
+    best[dead], arg[dead] = math.inf, -1
+    for val, idx in parts[1:]:
+        val, idx = np.asarray(val, dtype=np.float64), np.asarray(idx, dtype=np.int64)
+        if val.shape != best.shape or idx.shape != best.shape:
+            raise ValueError("merge_axis_minima: the parts differ in shape")
+        with np.errstate(invalid="ignore"):
+            take = (idx >= 0) & ((val < best) | ((val == best) & ((arg < 0) | (idx < arg))))
+        best[take], arg[take] = val[take], idx[take]
+    return best, arg
+
+
 # --------------------------------------------------------------------------- dense grid
 class DenseGrid:
     """A block of a dense parameter grid on one GPU (covest_grid* of the C ABI).
@@ -237,6 +281,20 @@ class DenseGrid:
         _capi.check(_capi.lib().covest_grid_argmin(self._handle, ctypes.byref(v), ctypes.byref(i)),
                     "covest_grid_argmin")
         return v.value, i.value
+
+    def axis_minima(self, keep):
+        """The last evaluate() reduced over the axes NOT in `keep` (axis numbers or parameter names), on the device
+        (covest_grid_axis_min): (negll, flat_index), float64 and int64 arrays shaped like the kept axes -- per cell
+        the minimum of -LL over this block's points in it and the global flat index of the lowest-index point
+        attaining it, (+inf, -1) where the block has nothing below +inf there.  keep=() is argmin()."""
+        mask, picked = resolve_keep(self.model.params, keep)
+        shape = tuple(self.shape[i] for i in picked)
+        val = np.empty(shape, dtype=np.float64)
+        idx = np.empty(shape, dtype=np.int64)
+        _capi.check(_capi.lib().covest_grid_axis_min(self._handle, mask, val.size, val.ctypes.data_as(_DP),
+                                                     idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
+                    "covest_grid_axis_min")
+        return val, idx
 
     def loglikelihoods(self):
         """LL of every point of the block (host ndarray, flat order)."""
@@ -375,6 +433,10 @@ class DeviceBlocks:
     def argmin(self):
         """(min -LL, global flat index): every block's pair, scanned in block order with the reference's rule."""
         return scan_min_pairs([g.argmin() for g in self.grids])
+
+    def axis_minima(self, keep):
+        """DenseGrid.axis_minima of the whole grid: every block's pairs, merged per cell (merge_axis_minima)."""
+        return merge_axis_minima([g.axis_minima(keep) for g in self.grids])
 
     def point(self, flat_index):
         return self.grids[0].point(flat_index)

@@ -26,7 +26,9 @@ def _finite_int(x):
 
 def print_output(hist_orig, model, success, sample_factor, estimated=None, guess=None, orig=None,
                  reads_size=None, silent=False, orig_sample_factor=1, starting_points=1,
-                 use_grid_search=False):
+                 use_grid_search=False, intervals=None):
+    """`intervals`: the dict covest_amd.profile.coverage_interval returns; the record then carries the likelihood-ratio
+    interval of the coverage, of the genome size and its level.  Without it the record is the reference's, key for key."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -65,6 +67,11 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
             record['provided_loglikelihood'] = model.compute_loglikelihood(*_none_filled(orig, estimated))
         except ValueError:
             pass
+    if intervals is not None:
+        record['coverage_interval'] = list(intervals['coverage_interval'])
+        record['genome_size_interval'] = (None if intervals.get('genome_size_interval') is None
+                                          else list(intervals['genome_size_interval']))
+        record['interval_level'] = float(intervals['level'])
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

@@ -160,6 +160,18 @@ int covest_grid_eval(covest_grid *g, int32_t kernel, void *stream);
  * < +inf. */
 int covest_grid_argmin(covest_grid *g, double *min_negll, int64_t *argmin_flat);
 
+/* The same selection PER CELL of the product of the axes named in keep_mask (bit d set = axis d is kept), over the
+ * other axes, of the last evaluation: for every cell -- row-major in the kept axes' original order, n_cells = the
+ * product of their lengths -- min -LL over the points of the handle's block that fall in the cell and the GLOBAL flat
+ * index of the lowest-index point attaining it; (+inf, -1) where no point of the block in the cell is < +inf, cells
+ * the block does not touch included.  keep_mask 0 is covest_grid_argmin's pair; all axes kept is -LL itself.  Waits
+ * for the last covest_grid_eval, reduces on its stream and copies the pairs to the HOST arrays (n_cells entries
+ * each); the LL buffer, the arg-min pair and the scan's records stay as they are, and any number of masks may be
+ * asked of one evaluation.  COVEST_E_INVALID: no evaluation on this handle since it was created or reset, a mask bit
+ * at or above n_axes, n_cells not that product.  The pairs of the blocks of one grid combine with the same rule
+ * (covest_amd.grid.merge_axis_minima). */
+int covest_grid_axis_min(covest_grid *g, uint32_t keep_mask, int64_t n_cells, double *min_negll, int64_t *argmin_flat);
+
 /* covest_grid_eval and, in the same arg-min launch, the SELECTION SCAN of covest/grid.py:65-70 started from the
  * minimum the caller holds (`start_min`: what optimize_grid's `min_val` is when an iteration begins, :49,67-69):
  *     if sgn * val < min_val: diff += min_val - val; min_val = sgn * val; min_args = args
