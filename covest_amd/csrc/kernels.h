@@ -137,6 +137,15 @@ bool axis_min_plan(const int64_t *len, int n_axes, uint32_t keep_mask, int64_t f
 hipError_t launch_axis_min(const AxisMinPlan &p, const double *ll, double *partial_val, int64_t *partial_idx, double *out_val,
                            int64_t *out_idx, hipStream_t stream);
 
+// ---- K-grad (ll_grad.hip): value and analytic gradient of a point list ----
+// One workgroup per (point, segment of ll_grad_segments(m) key segments) leaves compensated partial sums in `partial`
+// (ll_grad_partial_bytes(m, n) bytes); a second launch adds a point's segments in ascending order and applies the tail
+// term.  out_ll[n], out_grad[n][P]; src is a point list.  Two launches (per 16384 points); not entered in the launch record.
+int ll_grad_segments(const DevModel &m);
+size_t ll_grad_partial_bytes(const DevModel &m, int64_t n);
+hipError_t launch_ll_grad(const DevModel &m, const PointSource &src, int64_t n, double *partial, double *out_ll,
+                          double *out_grad, hipStream_t stream);
+
 // ---- K-kmer: k-mer abundance histogram (kmer_count.hip), SURVEY 8(f) row F1 ----
 // Open-addressing table in HBM, slots = 2^log2_slots, one 16-byte entry per slot: {key, count}
 // (key all-ones = empty).  Key and count share a cache line on purpose: a k-mer costs ONE scattered

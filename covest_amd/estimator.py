@@ -22,6 +22,11 @@ requests merged into one launch per round (`_LockStep`, opt-in: see `_best_of`).
 first against a recorder to learn the points, then against the batch's values, so the gradient -- and
 with it every iterate -- is bit-identical to what `minimize(..., jac=None)` computes from the same
 likelihood values.  The kernels are deterministic per point, whatever else shares the launch.
+
+`gradient="analytic"` (opt-in) takes the gradient from the device instead (`model.loglikelihood_gradient_points`, one
+evaluation, the closed form of DESIGN.md section 6e): where such a refinement stops does not hang on the last bits of
+the values, as the differenced gradient's noise of order 0.1 a component makes the default flow's.  It does not
+reproduce the reference's iterates; the default, `"fd"`, is the route that does.
 """
 import threading
 import itertools
@@ -95,7 +100,14 @@ def _fd_fast_matches_scipy(lo, hi, h0):
 class CoverageEstimator:
     ERROR_RATE = 1  # index of the parameter that err_scale applies to
 
-    def __init__(self, model, err_scale=1, fix=None, batched=True, lock_step=False, reference_specials=False):
+    def __init__(self, model, err_scale=1, fix=None, batched=True, lock_step=False, reference_specials=False,
+                 gradient="fd"):
+        if gradient not in ("fd", "analytic"):
+            raise ValueError('gradient must be "fd" or "analytic"')
+        if gradient == "analytic" and (reference_specials or not batched):
+            # (the reference's overflow values have no gradient, and batched=False is the reference's own call pattern)
+            raise ValueError('gradient="analytic" goes with neither reference_specials=True nor batched=False')
+        self.gradient = gradient
         self.model = model
         # True: where the reference's long-double pmf product overflows (c_src/covest_poissonmodule.c:19-24) the
         # objective is what the REFERENCE returns there -- -(+inf) or NaN -- instead of the finite value the formula
@@ -211,6 +223,22 @@ class CoverageEstimator:
         specials = self.reference_specials if reference_specials is None else bool(reference_specials)
         return self._with_reference_specials(pts, out) if specials else out
 
+    def negll_gradient_points(self, xs):
+        """likelihood_f and its analytic gradient IN OPTIMISER SPACE for several optimiser-space vectors, one launch:
+        ndarray (n, 1 + P), row = [-LL, d(-LL)/dx ...].  The error-rate component is divided by err_scale (x carries
+        err_scale * e); the components of `fix`-ed parameters are 0."""
+        pts = np.array([self._model_args(x) for x in xs], dtype=np.float64)
+        ll, grad = self.model.loglikelihood_gradient_points(pts)
+        out = np.empty((len(pts), 1 + pts.shape[1]), dtype=np.float64)
+        out[:, 0] = -np.asarray(ll, dtype=np.float64)
+        out[:, 1:] = -np.asarray(grad, dtype=np.float64)
+        out[:, 1 + self.ERROR_RATE] /= self.err_scale
+        if self.fix is not None:
+            for i, f in enumerate(self.fix):
+                if f is not None:
+                    out[:, 1 + i] = 0.0
+        return out
+
     def _with_reference_specials(self, pts, negll):
         """-LL with the reference's own result substituted where its pmf product overflows: the points the host
         test flags (model.reference_overflows: the largest rate against the largest key) go through
@@ -266,6 +294,15 @@ class CoverageEstimator:
         if not self.batched:
             return minimize(self.likelihood_f, start, method=constants.OPTIMIZATION_METHOD,
                             bounds=self.bounds, options={'disp': False})
+        if self.gradient == "analytic":
+            evaluate = evaluate or self.negll_gradient_points
+
+            def value_and_gradient(x):
+                row = np.asarray(evaluate([np.asarray(x, dtype=np.float64)]), dtype=np.float64)[0]
+                return float(row[0]), np.array(row[1:])
+
+            return minimize(value_and_gradient, start, jac=True, method=constants.OPTIMIZATION_METHOD,
+                            bounds=self.bounds, options={'disp': False})
         evaluate = evaluate or self.negll_points
         return minimize(lambda x: self._value_and_gradient(x, evaluate), start, jac=True,
                         method=constants.OPTIMIZATION_METHOD, bounds=self.bounds, options={'disp': False})
@@ -279,7 +316,8 @@ class CoverageEstimator:
         more than the launches they save); it pays when an evaluation is expensive (huge threshold_o)."""
         starts = list(starts)
         if self.batched and self.lock_step and len(starts) > 1:
-            results = _LockStep(self.negll_points, len(starts)).map(self._optimize, starts)
+            batch = self.negll_gradient_points if self.gradient == "analytic" else self.negll_points
+            results = _LockStep(batch, len(starts)).map(self._optimize, starts)
         else:
             results = [self._optimize(s) for s in starts]
         best = None
@@ -333,7 +371,7 @@ class _LockStep:
             values = np.asarray(self._evaluate_batch(merged))
         except BaseException as exc:  # hand the failure to every waiter
             self._failure = exc
-            values = np.full(len(merged), np.nan)
+            values = np.full(len(merged), np.nan)  # (never read: every waiter raises)
         self.rounds += 1
         self.points += len(merged)
         at = 0

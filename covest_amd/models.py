@@ -262,6 +262,24 @@ class BasicModel:
                         "covest_eval_points")
         return out
 
+    def loglikelihood_gradient_points(self, points):
+        """LL and its analytic gradient for an (n, param_count) array of points -> (ll[n], grad[n, param_count]).
+        The gradient of what the kernels evaluate, at the point after fit_to_bounds, threshold_o held fixed
+        (covest_eval_points_grad): a component whose parameter the clamp moved is 0, every component is NaN where
+        the value is not finite."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, self.param_count)
+        ll = np.empty(len(pts), dtype=np.float64)
+        grad = np.empty((len(pts), self.param_count), dtype=np.float64)
+        if len(pts):
+            _capi.check(_capi.lib().covest_eval_points_grad(self.handle, len(pts), _as_dp(pts), _as_dp(ll), _as_dp(grad)),
+                        "covest_eval_points_grad")
+        return ll, grad
+
+    def compute_loglikelihood_gradient(self, *args):
+        """(LL, [dLL/dparam ...]) at one point: compute_loglikelihood with the analytic gradient beside it."""
+        ll, grad = self.loglikelihood_gradient_points(self._points_array([args]))
+        return float(ll[0]), [float(g) for g in grad[0]]
+
     def launch_record(self):
         """What the last loglikelihood_points() launched: {"launches": {instantiation: launches}, "plans": [K-factored
         plans]} (covest_model_launch_record; host bookkeeping, nothing waits for the device)."""

@@ -114,6 +114,14 @@ int covest_threshold_o(int64_t n, const double *q123, double threshold, int32_t 
 int covest_eval_points(covest_model *m, int64_t n, const double *params, double *out_ll,
                        int32_t kernel);
 
+/* The same values and, beside them, the ANALYTIC gradient of the log-likelihood in the model's parameters: the
+ * gradient of what the kernels evaluate, at the point after fit_to_bounds, with threshold_o held fixed (DESIGN.md
+ * section 6e).  HOST arrays: params [n][param_count], out_ll[n], out_grad[n][param_count].  A component whose
+ * parameter fit_to_bounds moved is 0 (the function is constant there); where the value is not finite every component
+ * is NaN.  One kernel for both models (ll_grad.hip) and a small finishing launch; a point's numbers do not depend on
+ * what else is in the call. */
+int covest_eval_points_grad(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad);
+
 /* Documented divergence made visible: the reference forms its pmf product in x87 long double BEFORE
  * scaling it (c_src/covest_poissonmodule.c:19-24), so for large rates against large keys
  * (ln(l^i / i!) > 11356.5 at i = min(j, floor(l))) truncated_poisson returns +inf, the likelihood
