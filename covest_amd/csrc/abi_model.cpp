@@ -640,6 +640,65 @@ int covest_eval_points_grad(covest_model *m, int64_t n, const double *params, do
     return COVEST_OK;
 }
 
+int covest_eval_points_hess(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad,
+                            double *out_hess)
+{
+    if (!m || n < 0 || (n > 0 && (!params || !out_ll || !out_grad || !out_hess)))
+        return fail(COVEST_E_INVALID, "covest_eval_points_hess: bad argument");
+    if (n == 0)
+        return COVEST_OK;
+    std::lock_guard<std::mutex> guard(m->lock);
+    DeviceGuard dev_guard(m->device);
+    int rc = dev_guard.status();
+    if (rc != COVEST_OK)
+        return rc;
+    const int P = m->n_par;
+    std::vector<int32_t> t;
+    if (P == 5) {
+        t.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i)
+            t[(size_t)i] = threshold_for_point(m, params + i * P);
+    }
+    const size_t par_bytes = (size_t)n * P * sizeof(double), t_bytes = ((size_t)n * sizeof(int32_t) + 7) / 8 * 8;
+    const size_t out_bytes = (size_t)n * (1 + P + P * P) * sizeof(double); // values, gradients, Hessians
+    HIP_TRY(m->ws_hess_partial.reserve(ll_hess_partial_bytes(m->dm, n)));
+    HIP_TRY(m->ws_hess_stage.reserve(par_bytes + t_bytes));
+    char *st = m->ws_hess_stage.as<char>();
+    std::memcpy(st, params, par_bytes);
+    if (P == 5)
+        std::memcpy(st + par_bytes, t.data(), (size_t)n * sizeof(int32_t));
+    // a short list (the point of a fit) moves nothing through the copy engine, as in covest_eval_points
+    const bool in_place = n <= kInPlaceMaxPoints;
+    PointSource src{};
+    src.is_grid = 0;
+    double *out_dev;
+    if (in_place) {
+        HIP_TRY(m->ws_hess_result.reserve(out_bytes));
+        src.params = reinterpret_cast<const double *>(st);
+        src.t_list = P == 5 ? reinterpret_cast<const int32_t *>(st + par_bytes) : nullptr;
+        out_dev = m->ws_hess_result.as<double>();
+    } else {
+        HIP_TRY(m->ws_params.reserve(par_bytes + t_bytes));
+        HIP_TRY(m->ws_hess_out.reserve(out_bytes));
+        HIP_TRY(hipMemcpy(m->ws_params.ptr, st, par_bytes + t_bytes, hipMemcpyHostToDevice));
+        src.params = m->ws_params.as<double>();
+        src.t_list = P == 5 ? reinterpret_cast<const int32_t *>(m->ws_params.as<char>() + par_bytes) : nullptr;
+        out_dev = m->ws_hess_out.as<double>();
+    }
+    HIP_TRY(launch_ll_hess(m->dm, src, n, m->ws_hess_partial.as<double>(), out_dev, out_dev + n, out_dev + n * (1 + P), nullptr));
+    if (in_place) {
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        std::memcpy(out_ll, out_dev, (size_t)n * sizeof(double));
+        std::memcpy(out_grad, out_dev + n, (size_t)n * P * sizeof(double));
+        std::memcpy(out_hess, out_dev + n * (1 + P), (size_t)n * P * P * sizeof(double));
+    } else {
+        HIP_TRY(hipMemcpy(out_ll, out_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_grad, out_dev + n, (size_t)n * P * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_hess, out_dev + n * (1 + P), (size_t)n * P * P * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return COVEST_OK;
+}
+
 int64_t covest_model_launch_record(covest_model *m, char *buf, int64_t cap)
 {
     if (!m || cap < 0 || (cap > 0 && !buf))

@@ -1,0 +1,76 @@
+// grad_common.h -- what the derivative kernels share (K-grad, ll_grad.hip; K-hess, ll_hess.hip): the derivatives of the
+// log of the truncated Poisson's normaliser inside each of its pieces, and the compensated (hi, lo) sums a segment leaves.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "point_fetch.h"
+#include "wave.h"
+
+namespace covest {
+
+// d/dx of log_trunc_norm (point_fetch.h), inside each of its pieces: 1 / x on the two branches that divide by x itself,
+// 1 / (1 - exp(-xr)) of the residual otherwise.  The rint onto the 2^-63 grid is rounding noise and has no derivative.
+__device__ __forceinline__ double trunc_norm_dlog(double x)
+{
+    if (x <= 1e-8)
+        return 1.0 / x;
+    double xr = x;
+    if (x > 200.0) {
+        const double n = ceil(x / 200.0) - 1.0;
+        xr = fma(-200.0, n, x);
+        if (xr > 200.0)
+            xr -= 200.0;
+        else if (xr <= 0.0)
+            xr += 200.0;
+        if (xr <= 1e-8)
+            return 1.0 / x;
+    }
+    return -1.0 / expm1(-xr);
+}
+
+// The first AND the second derivative, piece by piece as above: L' = 1 / x, L'' = -1 / x^2 on the two branches that
+// divide by x itself; L' = 1 / (1 - exp(-xr)), L'' = -exp(-xr) / (1 - exp(-xr))^2 of the residual otherwise.  d1 is
+// trunc_norm_dlog(x), the same expressions.
+__device__ __forceinline__ void trunc_norm_dlog2(double x, double &d1, double &d2)
+{
+    double xr = x;
+    bool by_x = x <= 1e-8;
+    if (!by_x && x > 200.0) {
+        const double n = ceil(x / 200.0) - 1.0;
+        xr = fma(-200.0, n, x);
+        if (xr > 200.0)
+            xr -= 200.0;
+        else if (xr <= 0.0)
+            xr += 200.0;
+        by_x = xr <= 1e-8;
+    }
+    if (by_x) {
+        d1 = 1.0 / x;
+        d2 = -d1 * d1;
+    } else {
+        const double em = expm1(-xr); // -(1 - exp(-xr))
+        d1 = -1.0 / em;
+        d2 = -(em + 1.0) * d1 * d1;
+    }
+}
+
+// (hi, lo) += (ohi, olo), as wave_comp_sum's step
+__device__ __forceinline__ void comp_merge(CompSum &v, double ohi, double olo)
+{
+    double e;
+    two_sum(v.hi, ohi, v.hi, e);
+    v.lo += olo + e;
+}
+
+__device__ __forceinline__ CompSum wave_comp_reduce(CompSum v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ohi = __shfl_xor(v.hi, off, kWave);
+        const double olo = __shfl_xor(v.lo, off, kWave);
+        comp_merge(v, ohi, olo);
+    }
+    return v;
+}
+
+} // namespace covest

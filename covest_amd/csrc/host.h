@@ -242,6 +242,9 @@ struct covest_model {
     // device-mapped blocks a short list's parameters are read from and its results written to in place
     DevBuf ws_grad_partial, ws_grad_out;
     HostBuf ws_grad_stage, ws_grad_result;
+    // covest_eval_points_hess: the same four, of its own sizes (values, gradients, Hessians)
+    DevBuf ws_hess_partial, ws_hess_out;
+    HostBuf ws_hess_stage, ws_hess_result;
     LaunchRecord record; // what the last covest_eval_points launched (covest_model_launch_record)
     std::mutex lock;
 };

@@ -146,6 +146,15 @@ size_t ll_grad_partial_bytes(const DevModel &m, int64_t n);
 hipError_t launch_ll_grad(const DevModel &m, const PointSource &src, int64_t n, double *partial, double *out_ll,
                           double *out_grad, hipStream_t stream);
 
+// ---- K-hess (ll_hess.hip): value, analytic gradient and closed-form Hessian of a point list ----
+// K-grad's scheme with more sums a segment (`partial`: ll_hess_partial_bytes(m, n) bytes).  out_ll[n], out_grad[n][P],
+// out_hess[n][P][P] (symmetric: the upper triangle computed, mirrored); src is a point list.  Two launches (per 16384
+// points); not entered in the launch record.
+int ll_hess_segments(const DevModel &m);
+size_t ll_hess_partial_bytes(const DevModel &m, int64_t n);
+hipError_t launch_ll_hess(const DevModel &m, const PointSource &src, int64_t n, double *partial, double *out_ll,
+                          double *out_grad, double *out_hess, hipStream_t stream);
+
 // ---- K-kmer: k-mer abundance histogram (kmer_count.hip), SURVEY 8(f) row F1 ----
 // Open-addressing table in HBM, slots = 2^log2_slots, one 16-byte entry per slot: {key, count}
 // (key all-ones = empty).  Key and count share a cache line on purpose: a k-mer costs ONE scattered

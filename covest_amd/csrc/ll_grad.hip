@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "direct_point.h"
+#include "grad_common.h"
 #include "kernels.h"
 
 namespace covest {
@@ -27,45 +28,6 @@ namespace {
 constexpr int kGradWaves = 4;
 constexpr int kGradSegKeys = kGradWaves * kWave; // one key a lane
 constexpr int64_t kGradPointsPerLaunch = 16384;  // (gridDim.y)
-
-// d/dx of log_trunc_norm (point_fetch.h), inside each of its pieces: 1 / x on the two branches that divide by x itself,
-// 1 / (1 - exp(-xr)) of the residual otherwise.  The rint onto the 2^-63 grid is rounding noise and has no derivative.
-__device__ __forceinline__ double trunc_norm_dlog(double x)
-{
-    if (x <= 1e-8)
-        return 1.0 / x;
-    double xr = x;
-    if (x > 200.0) {
-        const double n = ceil(x / 200.0) - 1.0;
-        xr = fma(-200.0, n, x);
-        if (xr > 200.0)
-            xr -= 200.0;
-        else if (xr <= 0.0)
-            xr += 200.0;
-        if (xr <= 1e-8)
-            return 1.0 / x;
-    }
-    return -1.0 / expm1(-xr);
-}
-
-// (hi, lo) += (ohi, olo), as wave_comp_sum's step
-__device__ __forceinline__ void comp_merge(CompSum &v, double ohi, double olo)
-{
-    double e;
-    two_sum(v.hi, ohi, v.hi, e);
-    v.lo += olo + e;
-}
-
-__device__ __forceinline__ CompSum wave_comp_reduce(CompSum v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double ohi = __shfl_xor(v.hi, off, kWave);
-        const double olo = __shfl_xor(v.lo, off, kWave);
-        comp_merge(v, ohi, olo);
-    }
-    return v;
-}
 
 // The sums a segment leaves, each as a (hi, lo) pair: 0 sum h log p (finite terms), 1 sum p, 2 .. 2 + P - 1
 // sum h dp/p per parameter, 2 + P .. 2 + 2P - 1 sum dp per parameter; behind them ONE double: the sum of the terms

@@ -280,6 +280,26 @@ class BasicModel:
         ll, grad = self.loglikelihood_gradient_points(self._points_array([args]))
         return float(ll[0]), [float(g) for g in grad[0]]
 
+    def loglikelihood_hessian_points(self, points):
+        """LL, its analytic gradient and its Hessian in closed form for an (n, param_count) array of points ->
+        (ll[n], grad[n, param_count], hess[n, param_count, param_count]).  Second derivatives of the function
+        loglikelihood_gradient_points differentiates (covest_eval_points_hess): symmetric bit for bit, a row and column
+        whose parameter the clamp moved are 0, every entry is NaN where the value is not finite."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, self.param_count)
+        P = self.param_count
+        ll = np.empty(len(pts), dtype=np.float64)
+        grad = np.empty((len(pts), P), dtype=np.float64)
+        hess = np.empty((len(pts), P, P), dtype=np.float64)
+        if len(pts):
+            _capi.check(_capi.lib().covest_eval_points_hess(self.handle, len(pts), _as_dp(pts), _as_dp(ll), _as_dp(grad),
+                                                            _as_dp(hess)), "covest_eval_points_hess")
+        return ll, grad, hess
+
+    def compute_loglikelihood_hessian(self, *args):
+        """(LL, [dLL/dparam ...], [[d2LL/dparam dparam' ...] ...]) at one point."""
+        ll, grad, hess = self.loglikelihood_hessian_points(self._points_array([args]))
+        return float(ll[0]), [float(g) for g in grad[0]], [[float(v) for v in row] for row in hess[0]]
+
     def launch_record(self):
         """What the last loglikelihood_points() launched: {"launches": {instantiation: launches}, "plans": [K-factored
         plans]} (covest_model_launch_record; host bookkeeping, nothing waits for the device)."""

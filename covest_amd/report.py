@@ -26,9 +26,14 @@ def _finite_int(x):
 
 def print_output(hist_orig, model, success, sample_factor, estimated=None, guess=None, orig=None,
                  reads_size=None, silent=False, orig_sample_factor=1, starting_points=1,
-                 use_grid_search=False, intervals=None):
+                 use_grid_search=False, intervals=None, information=None):
     """`intervals`: the dict covest_amd.profile.coverage_interval returns; the record then carries the likelihood-ratio
-    interval of the coverage, of the genome size and its level.  Without it the record is the reference's, key for key."""
+    interval of the coverage, of the genome size and its level.  Without it the record is the reference's, key for key.
+    `information`: the dict covest_amd.information.observed_information returns (a key 'level' in it chooses the Wald
+    level, 0.95 otherwise); the record then carries standard_errors, wald_intervals, genome_size_se,
+    genome_size_wald_interval and wald_level, the coverage's in the units of the record's `coverage` (times
+    sample_factor).  They are the MODEL's standard errors: it treats the k-mer counts as independent and |LL| is
+    1e7..1e8, so they are very small.  Without it the record is unchanged."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -72,6 +77,22 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
         record['genome_size_interval'] = (None if intervals.get('genome_size_interval') is None
                                           else list(intervals['genome_size_interval']))
         record['interval_level'] = float(intervals['level'])
+    if information is not None:
+        from .information import genome_size_se, wald_intervals
+        level = float(information.get('level', 0.95))
+        scale = 1 if sample_factor is None else sample_factor
+        first = model.params[0]
+        errors = {name: (None if se is None else float(se * scale if name == first else se))
+                  for name, se in information['standard_errors'].items()}
+        walds = {name: (None if iv is None else [float(v * scale if name == first else v) for v in iv])
+                 for name, iv in wald_intervals(information, level).items()}
+        size = genome_size_se(model, hist_orig, information, sample_factor=scale, level=level)
+        record['standard_errors'] = errors
+        record['wald_intervals'] = walds
+        record['genome_size_se'] = None if size['genome_size_se'] is None else float(size['genome_size_se'])
+        record['genome_size_wald_interval'] = (None if size['genome_size_wald_interval'] is None
+                                               else [float(v) for v in size['genome_size_wald_interval']])
+        record['wald_level'] = level
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

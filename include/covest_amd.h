@@ -122,6 +122,17 @@ int covest_eval_points(covest_model *m, int64_t n, const double *params, double 
  * what else is in the call. */
 int covest_eval_points_grad(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad);
 
+/* Values, the analytic gradient and, beside them, the HESSIAN of the log-likelihood in closed form: second derivatives
+ * of the same function (what the kernels evaluate, at the point after fit_to_bounds, threshold_o held fixed; DESIGN.md
+ * section 6f).  HOST arrays: params [n][param_count], out_ll[n], out_grad[n][param_count],
+ * out_hess[n][param_count][param_count].  The matrix is symmetric bit for bit (the upper triangle is computed and
+ * mirrored).  A row and column whose parameter fit_to_bounds moved are 0, and so is that gradient component; where the
+ * value is not finite every entry of gradient and Hessian is NaN.  One kernel for both models (ll_hess.hip) and a small
+ * finishing launch, neither entered in the launch record; a point's numbers do not depend on what else is in the
+ * call.  Meant to be asked once per fit (the observed information at the optimum), not inside a search. */
+int covest_eval_points_hess(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad,
+                            double *out_hess);
+
 /* Documented divergence made visible: the reference forms its pmf product in x87 long double BEFORE
  * scaling it (c_src/covest_poissonmodule.c:19-24), so for large rates against large keys
  * (ln(l^i / i!) > 11356.5 at i = min(j, floor(l))) truncated_poisson returns +inf, the likelihood
