@@ -584,10 +584,13 @@ int covest_eval_points(covest_model *m, int64_t n, const double *params, double 
     return COVEST_OK;
 }
 
-int covest_eval_points_grad(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad)
+// covest_eval_points_grad (order 1) and covest_eval_points_hess (order 2): the device leaves values | gradients |
+// Hessians (the last block only for order 2) in one buffer; `who` names the entry point in the messages.
+static int eval_points_deriv(covest_model *m, int order, int64_t n, const double *params, double *out_ll, double *out_grad,
+                             double *out_hess, const char *who)
 {
-    if (!m || n < 0 || (n > 0 && (!params || !out_ll || !out_grad)))
-        return fail(COVEST_E_INVALID, "covest_eval_points_grad: bad argument");
+    if (!m || n < 0 || (n > 0 && (!params || !out_ll || !out_grad || (order == 2 && !out_hess))))
+        return fail(COVEST_E_INVALID, std::string(who) + ": bad argument");
     if (n == 0)
         return COVEST_OK;
     std::lock_guard<std::mutex> guard(m->lock);
@@ -603,100 +606,57 @@ int covest_eval_points_grad(covest_model *m, int64_t n, const double *params, do
             t[(size_t)i] = threshold_for_point(m, params + i * P);
     }
     const size_t par_bytes = (size_t)n * P * sizeof(double), t_bytes = ((size_t)n * sizeof(int32_t) + 7) / 8 * 8;
-    const size_t out_bytes = (size_t)n * (1 + P) * sizeof(double); // values, then gradients
-    HIP_TRY(m->ws_grad_partial.reserve(ll_grad_partial_bytes(m->dm, n)));
-    HIP_TRY(m->ws_grad_stage.reserve(par_bytes + t_bytes));
-    char *st = m->ws_grad_stage.as<char>();
+    const size_t out_bytes = (size_t)n * (1 + P + (order == 2 ? P * P : 0)) * sizeof(double);
+    HIP_TRY(m->ws_deriv_partial.reserve(ll_deriv_partial_bytes(m->dm, order, n)));
+    HIP_TRY(m->ws_deriv_stage.reserve(par_bytes + t_bytes));
+    char *st = m->ws_deriv_stage.as<char>();
     std::memcpy(st, params, par_bytes);
     if (P == 5)
         std::memcpy(st + par_bytes, t.data(), (size_t)n * sizeof(int32_t));
-    // a short list (a refinement's requests) moves nothing through the copy engine, as in covest_eval_points
+    // a short list (a refinement's requests, the point of a fit) moves nothing through the copy engine, as in
+    // covest_eval_points
     const bool in_place = n <= kInPlaceMaxPoints;
     PointSource src{};
     src.is_grid = 0;
     double *out_dev;
     if (in_place) {
-        HIP_TRY(m->ws_grad_result.reserve(out_bytes));
+        HIP_TRY(m->ws_deriv_result.reserve(out_bytes));
         src.params = reinterpret_cast<const double *>(st);
         src.t_list = P == 5 ? reinterpret_cast<const int32_t *>(st + par_bytes) : nullptr;
-        out_dev = m->ws_grad_result.as<double>();
+        out_dev = m->ws_deriv_result.as<double>();
     } else {
         HIP_TRY(m->ws_params.reserve(par_bytes + t_bytes));
-        HIP_TRY(m->ws_grad_out.reserve(out_bytes));
+        HIP_TRY(m->ws_deriv_out.reserve(out_bytes));
         HIP_TRY(hipMemcpy(m->ws_params.ptr, st, par_bytes + t_bytes, hipMemcpyHostToDevice));
         src.params = m->ws_params.as<double>();
         src.t_list = P == 5 ? reinterpret_cast<const int32_t *>(m->ws_params.as<char>() + par_bytes) : nullptr;
-        out_dev = m->ws_grad_out.as<double>();
+        out_dev = m->ws_deriv_out.as<double>();
     }
-    HIP_TRY(launch_ll_grad(m->dm, src, n, m->ws_grad_partial.as<double>(), out_dev, out_dev + n, nullptr));
-    if (in_place) {
+    HIP_TRY(launch_ll_deriv(m->dm, order, src, n, m->ws_deriv_partial.as<double>(), out_dev, out_dev + n, out_dev + n * (1 + P),
+                            nullptr));
+    // the blocks of the device's buffer and where each goes
+    const struct { double *dst; size_t first, count; } blocks[3] = {
+        {out_ll, 0, (size_t)n}, {out_grad, (size_t)n, (size_t)n * P}, {out_hess, (size_t)n * (1 + P), (size_t)n * P * P}};
+    if (in_place)
         HIP_TRY(hipStreamSynchronize(nullptr));
-        std::memcpy(out_ll, out_dev, (size_t)n * sizeof(double));
-        std::memcpy(out_grad, out_dev + n, (size_t)n * P * sizeof(double));
-    } else {
-        HIP_TRY(hipMemcpy(out_ll, out_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_grad, out_dev + n, (size_t)n * P * sizeof(double), hipMemcpyDeviceToHost));
+    for (int b = 0; b <= order; ++b) {
+        if (in_place)
+            std::memcpy(blocks[b].dst, out_dev + blocks[b].first, blocks[b].count * sizeof(double));
+        else
+            HIP_TRY(hipMemcpy(blocks[b].dst, out_dev + blocks[b].first, blocks[b].count * sizeof(double), hipMemcpyDeviceToHost));
     }
     return COVEST_OK;
+}
+
+int covest_eval_points_grad(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad)
+{
+    return eval_points_deriv(m, 1, n, params, out_ll, out_grad, nullptr, "covest_eval_points_grad");
 }
 
 int covest_eval_points_hess(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad,
                             double *out_hess)
 {
-    if (!m || n < 0 || (n > 0 && (!params || !out_ll || !out_grad || !out_hess)))
-        return fail(COVEST_E_INVALID, "covest_eval_points_hess: bad argument");
-    if (n == 0)
-        return COVEST_OK;
-    std::lock_guard<std::mutex> guard(m->lock);
-    DeviceGuard dev_guard(m->device);
-    int rc = dev_guard.status();
-    if (rc != COVEST_OK)
-        return rc;
-    const int P = m->n_par;
-    std::vector<int32_t> t;
-    if (P == 5) {
-        t.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i)
-            t[(size_t)i] = threshold_for_point(m, params + i * P);
-    }
-    const size_t par_bytes = (size_t)n * P * sizeof(double), t_bytes = ((size_t)n * sizeof(int32_t) + 7) / 8 * 8;
-    const size_t out_bytes = (size_t)n * (1 + P + P * P) * sizeof(double); // values, gradients, Hessians
-    HIP_TRY(m->ws_hess_partial.reserve(ll_hess_partial_bytes(m->dm, n)));
-    HIP_TRY(m->ws_hess_stage.reserve(par_bytes + t_bytes));
-    char *st = m->ws_hess_stage.as<char>();
-    std::memcpy(st, params, par_bytes);
-    if (P == 5)
-        std::memcpy(st + par_bytes, t.data(), (size_t)n * sizeof(int32_t));
-    // a short list (the point of a fit) moves nothing through the copy engine, as in covest_eval_points
-    const bool in_place = n <= kInPlaceMaxPoints;
-    PointSource src{};
-    src.is_grid = 0;
-    double *out_dev;
-    if (in_place) {
-        HIP_TRY(m->ws_hess_result.reserve(out_bytes));
-        src.params = reinterpret_cast<const double *>(st);
-        src.t_list = P == 5 ? reinterpret_cast<const int32_t *>(st + par_bytes) : nullptr;
-        out_dev = m->ws_hess_result.as<double>();
-    } else {
-        HIP_TRY(m->ws_params.reserve(par_bytes + t_bytes));
-        HIP_TRY(m->ws_hess_out.reserve(out_bytes));
-        HIP_TRY(hipMemcpy(m->ws_params.ptr, st, par_bytes + t_bytes, hipMemcpyHostToDevice));
-        src.params = m->ws_params.as<double>();
-        src.t_list = P == 5 ? reinterpret_cast<const int32_t *>(m->ws_params.as<char>() + par_bytes) : nullptr;
-        out_dev = m->ws_hess_out.as<double>();
-    }
-    HIP_TRY(launch_ll_hess(m->dm, src, n, m->ws_hess_partial.as<double>(), out_dev, out_dev + n, out_dev + n * (1 + P), nullptr));
-    if (in_place) {
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        std::memcpy(out_ll, out_dev, (size_t)n * sizeof(double));
-        std::memcpy(out_grad, out_dev + n, (size_t)n * P * sizeof(double));
-        std::memcpy(out_hess, out_dev + n * (1 + P), (size_t)n * P * P * sizeof(double));
-    } else {
-        HIP_TRY(hipMemcpy(out_ll, out_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_grad, out_dev + n, (size_t)n * P * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_hess, out_dev + n * (1 + P), (size_t)n * P * P * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return COVEST_OK;
+    return eval_points_deriv(m, 2, n, params, out_ll, out_grad, out_hess, "covest_eval_points_hess");
 }
 
 int64_t covest_model_launch_record(covest_model *m, char *buf, int64_t cap)

@@ -1,4 +1,4 @@
-// grad_common.h -- what the derivative kernels share (K-grad, ll_grad.hip; K-hess, ll_hess.hip): the derivatives of the
+// grad_common.h -- what the derivative kernels (K-grad and K-hess, ll_deriv.hip) need beside the walk: the derivatives of the
 // log of the truncated Poisson's normaliser inside each of its pieces, and the compensated (hi, lo) sums a segment leaves.
 #pragma once
 #include <hip/hip_runtime.h>

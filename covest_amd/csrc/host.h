@@ -238,13 +238,11 @@ struct covest_model {
     HostBuf ws_stage; // staging of a point list's tables (build_list_plan)
     HostBuf ws_result; // page-locked, device-mapped: what a point-list launch leaves for the host (list mode 1's parts)
     DevBuf ws_sub_index, ws_sub_word, ws_sub_ctl; // the queue of handed-back points of a point-list launch (direct_point.h)
-    // covest_eval_points_grad: the segments' partial sums, a long list's values and gradients, and the page-locked,
-    // device-mapped blocks a short list's parameters are read from and its results written to in place
-    DevBuf ws_grad_partial, ws_grad_out;
-    HostBuf ws_grad_stage, ws_grad_result;
-    // covest_eval_points_hess: the same four, of its own sizes (values, gradients, Hessians)
-    DevBuf ws_hess_partial, ws_hess_out;
-    HostBuf ws_hess_stage, ws_hess_result;
+    // covest_eval_points_grad / _hess (every use under `lock`, so the two share them): the segments' partial sums, a long
+    // list's values, gradients and Hessians, and the page-locked, device-mapped blocks a short list's parameters are read
+    // from and its results written to in place
+    DevBuf ws_deriv_partial, ws_deriv_out;
+    HostBuf ws_deriv_stage, ws_deriv_result;
     LaunchRecord record; // what the last covest_eval_points launched (covest_model_launch_record)
     std::mutex lock;
 };

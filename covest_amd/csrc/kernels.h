@@ -137,23 +137,17 @@ bool axis_min_plan(const int64_t *len, int n_axes, uint32_t keep_mask, int64_t f
 hipError_t launch_axis_min(const AxisMinPlan &p, const double *ll, double *partial_val, int64_t *partial_idx, double *out_val,
                            int64_t *out_idx, hipStream_t stream);
 
-// ---- K-grad (ll_grad.hip): value and analytic gradient of a point list ----
-// One workgroup per (point, segment of ll_grad_segments(m) key segments) leaves compensated partial sums in `partial`
-// (ll_grad_partial_bytes(m, n) bytes); a second launch adds a point's segments in ascending order and applies the tail
-// term.  out_ll[n], out_grad[n][P]; src is a point list.  Two launches (per 16384 points); not entered in the launch record.
-int ll_grad_segments(const DevModel &m);
-size_t ll_grad_partial_bytes(const DevModel &m, int64_t n);
-hipError_t launch_ll_grad(const DevModel &m, const PointSource &src, int64_t n, double *partial, double *out_ll,
-                          double *out_grad, hipStream_t stream);
-
-// ---- K-hess (ll_hess.hip): value, analytic gradient and closed-form Hessian of a point list ----
-// K-grad's scheme with more sums a segment (`partial`: ll_hess_partial_bytes(m, n) bytes).  out_ll[n], out_grad[n][P],
-// out_hess[n][P][P] (symmetric: the upper triangle computed, mirrored); src is a point list.  Two launches (per 16384
-// points); not entered in the launch record.
-int ll_hess_segments(const DevModel &m);
-size_t ll_hess_partial_bytes(const DevModel &m, int64_t n);
-hipError_t launch_ll_hess(const DevModel &m, const PointSource &src, int64_t n, double *partial, double *out_ll,
-                          double *out_grad, double *out_hess, hipStream_t stream);
+// ---- K-grad and K-hess (ll_deriv.hip): value, analytic gradient (order 1) and closed-form Hessian (order 2) ----
+// One workgroup per (point, segment of ll_deriv_segments(m) key segments) leaves compensated partial sums in `partial`
+// (ll_deriv_partial_bytes(m, order, n) bytes): per segment 2 + 2P sums for order 1 (h log p, p, h d_k p / p, d_k p),
+// P (P + 1) more for order 2 (the two second-order sums of each pair k <= l), each a (hi, lo) pair, and one double behind
+// them.  A second launch adds a point's segments in ascending order and applies the tail terms.  out_ll[n],
+// out_grad[n][P], and for order 2 out_hess[n][P][P] (symmetric: the upper triangle computed, mirrored; not read for
+// order 1); src is a point list.  Two launches (per 16384 points); not entered in the launch record.
+int ll_deriv_segments(const DevModel &m);
+size_t ll_deriv_partial_bytes(const DevModel &m, int order, int64_t n);
+hipError_t launch_ll_deriv(const DevModel &m, int order, const PointSource &src, int64_t n, double *partial, double *out_ll,
+                           double *out_grad, double *out_hess, hipStream_t stream);
 
 // ---- K-kmer: k-mer abundance histogram (kmer_count.hip), SURVEY 8(f) row F1 ----
 // Open-addressing table in HBM, slots = 2^log2_slots, one 16-byte entry per slot: {key, count}

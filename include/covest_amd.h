@@ -118,7 +118,7 @@ int covest_eval_points(covest_model *m, int64_t n, const double *params, double 
  * gradient of what the kernels evaluate, at the point after fit_to_bounds, with threshold_o held fixed (DESIGN.md
  * section 6e).  HOST arrays: params [n][param_count], out_ll[n], out_grad[n][param_count].  A component whose
  * parameter fit_to_bounds moved is 0 (the function is constant there); where the value is not finite every component
- * is NaN.  One kernel for both models (ll_grad.hip) and a small finishing launch; a point's numbers do not depend on
+ * is NaN.  One kernel for both models (ll_deriv.hip, order 1) and a small finishing launch; a point's numbers do not depend on
  * what else is in the call. */
 int covest_eval_points_grad(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad);
 
@@ -127,7 +127,7 @@ int covest_eval_points_grad(covest_model *m, int64_t n, const double *params, do
  * section 6f).  HOST arrays: params [n][param_count], out_ll[n], out_grad[n][param_count],
  * out_hess[n][param_count][param_count].  The matrix is symmetric bit for bit (the upper triangle is computed and
  * mirrored).  A row and column whose parameter fit_to_bounds moved are 0, and so is that gradient component; where the
- * value is not finite every entry of gradient and Hessian is NaN.  One kernel for both models (ll_hess.hip) and a small
+ * value is not finite every entry of gradient and Hessian is NaN.  One kernel for both models (ll_deriv.hip, order 2) and a small
  * finishing launch, neither entered in the launch record; a point's numbers do not depend on what else is in the
  * call.  Meant to be asked once per fit (the observed information at the optimum), not inside a search. */
 int covest_eval_points_hess(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad,

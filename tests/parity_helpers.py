@@ -5,7 +5,7 @@ import json
 import math
 import os
 
-from conftest import rel_err
+from conftest import load_hist, rel_err
 
 TOL = 1e-9
 
@@ -37,6 +37,17 @@ def _check(got, want, what, tol=TOL, slack=None):
         print("%s: %d of %d points beyond 1e-9 but inside the tail slack (largest share of it used: %.2g)" % (
             what, used, len(want), worst_use))
     return worst
+
+
+def _model(case, hist=None):
+    """The model of a fixture's case (tests/test_gpu_gradient.py, tests/test_gpu_hessian.py)."""
+    from covest_amd import BasicModel, RepeatsModel
+    hist = load_hist(case["hist"]) if hist is None else hist
+    if case["model"] == "repeats":
+        return RepeatsModel(case["k"], case["r"], hist, case["tail"], max_error=case["max_error"],
+                            threshold=case.get("threshold", 1e-8),
+                            min_single_copy_ratio=case.get("min_single_copy_ratio", 0.3))
+    return BasicModel(case["k"], case["r"], hist, case["tail"], max_error=case["max_error"], max_cov=case.get("max_cov"))
 
 
 K_TAIL = 8.0  # rounding errors of K eps per key are granted to the GPU's sp_j (first-order propagation)

@@ -1,4 +1,4 @@
-"""The analytic gradient on the GPU (covest_eval_points_grad, ll_grad.hip) against the 50-digit restatement of
+"""The analytic gradient on the GPU (covest_eval_points_grad, ll_deriv.hip) against the 50-digit restatement of
 tests/golden/gradient.json, against K-direct's value, for independence of what else is in the call, for the clamp and
 NaN conventions -- and the refinement driven by it, end to end."""
 import math
@@ -8,21 +8,9 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, load_hist, rel_err
+from parity_helpers import K_TAIL, TOL, _model
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-9
-K_TAIL = 8.0  # tests/parity_helpers.py: rounding errors of K eps per key granted to the GPU's sp_j
-
-
-def _model(case, hist=None):
-    from covest_amd import BasicModel, RepeatsModel
-    hist = load_hist(case["hist"]) if hist is None else hist
-    if case["model"] == "repeats":
-        return RepeatsModel(case["k"], case["r"], hist, case["tail"], max_error=case["max_error"],
-                            threshold=case.get("threshold", 1e-8),
-                            min_single_copy_ratio=case.get("min_single_copy_ratio", 0.3))
-    return BasicModel(case["k"], case["r"], hist, case["tail"], max_error=case["max_error"], max_cov=case.get("max_cov"))
 
 
 def test_every_fixture_point(hip_lib):

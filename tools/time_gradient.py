@@ -1,4 +1,4 @@
-"""Latency of one value+gradient call (covest_eval_points_grad, ll_grad.hip) against the P + 1-point value call the
+"""Latency of one value+gradient call (covest_eval_points_grad, ll_deriv.hip) against the P + 1-point value call the
 finite-difference route of CoverageEstimator makes (covest_eval_points, the route there was before), and a 20-start
 multi-start (bench.py --workload f2's set-up) with gradient="fd" and gradient="analytic".  One process, one device,
 after the spin-up bench.py uses; per case the median and the fastest of N calls, each call ending in a synchronise

@@ -1,4 +1,4 @@
-"""Latency of one value+gradient+Hessian call (covest_eval_points_hess, ll_hess.hip) on one point, beside the route it
+"""Latency of one value+gradient+Hessian call (covest_eval_points_hess, ll_deriv.hip) on one point, beside the route it
 replaces measured in the same process: one covest_eval_points_grad call of the 2P points a central difference of the
 analytic gradient needs.  One process, one device, after the spin-up bench.py uses; per case the median and the fastest
 of N calls, each call ending in a synchronise (both entry points wait for their stream), every route in a run of calls
