@@ -45,6 +45,8 @@ int grid_stage_commit(covest_grid *g, StageSlot &slot, void *dst, size_t bytes)
 
 } // namespace covest
 
+// Everything a grid handle holds besides its identity: called by covest_grid_create and covest_grid_reset.  Device
+// memory is only ever grown, and the small inputs (axes, threshold table, the queue's counter) go up in ONE copy:
 // optimize_grid re-configures a handle every iteration (21 times 0.2 ms of allocations and copies otherwise).
 static int grid_configure(covest_grid *g, int32_t n_axes, const double *const *axes, const int64_t *axis_len,
                           int64_t flat_begin, int64_t flat_end, const char *who)

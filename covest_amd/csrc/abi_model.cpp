@@ -4,13 +4,8 @@
 
 using namespace covest;
 
-extern "C" {
-
-int covest_model_create(const covest_model_desc *d, covest_model **out)
+static int check_model_desc(const covest_model_desc *d)
 {
-    if (!d || !out)
-        return fail(COVEST_E_INVALID, "covest_model_create: null argument");
-    *out = nullptr;
     if (d->kind != COVEST_MODEL_BASIC && d->kind != COVEST_MODEL_REPEATS)
         return fail(COVEST_E_INVALID, "covest_model_create: unknown model kind");
     if (d->n_err < 1 || d->n_err > COVEST_MAX_ERROR_CLASSES || d->n_err > d->k + 1)
@@ -23,23 +18,12 @@ int covest_model_create(const covest_model_desc *d, covest_model **out)
         return fail(COVEST_E_INVALID,
                     "covest_model_create: repeats model needs a non-empty histogram "
                     "(max() of an empty dict raises in covest/models.py:186)");
+    return COVEST_OK;
+}
 
-    int device = 0;
-    {
-        const int drc = resolve_device(d->device, "covest_model_create", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-
-    covest_model *m = new (std::nothrow) covest_model();
-    if (!m)
-        return fail(COVEST_E_NOMEM, "covest_model_create: out of host memory");
-    m->device = device;
-    m->n_par = d->kind == COVEST_MODEL_BASIC ? 2 : 5;
-    m->n_keys = d->n_keys;
-    m->threshold = d->threshold;
-    m->has_threshold = d->has_threshold != 0;
-    DevModel &dm = m->dm;
+// what the kernels read of a model description (device_model.h), except its bins
+static void fill_dev_model(DevModel &dm, const covest_model_desc *d, int n_par)
+{
     dm.kind = d->kind;
     dm.k = d->k;
     dm.r = d->r;
@@ -50,10 +34,38 @@ int covest_model_create(const covest_model_desc *d, covest_model **out)
         dm.ln_comb[s] = dm.comb[s] > 0.0 ? std::log(dm.comb[s]) : -INFINITY;
     }
     for (int i = 0; i < kMaxParams; ++i) {
-        dm.lo[i] = i < m->n_par ? d->lo[i] : std::numeric_limits<double>::quiet_NaN();
-        dm.hi[i] = i < m->n_par ? d->hi[i] : std::numeric_limits<double>::quiet_NaN();
+        dm.lo[i] = i < n_par ? d->lo[i] : std::numeric_limits<double>::quiet_NaN();
+        dm.hi[i] = i < n_par ? d->hi[i] : std::numeric_limits<double>::quiet_NaN();
     }
     dm.tail = d->tail;
+}
+
+extern "C" {
+
+int covest_model_create(const covest_model_desc *d, covest_model **out)
+{
+    if (!d || !out)
+        return fail(COVEST_E_INVALID, "covest_model_create: null argument");
+    *out = nullptr;
+    const int ok = check_model_desc(d);
+    if (ok != COVEST_OK)
+        return ok;
+
+    int device = 0;
+    const int drc = resolve_device(d->device, "covest_model_create", &device);
+    if (drc != COVEST_OK)
+        return drc;
+
+    covest_model *m = new (std::nothrow) covest_model();
+    if (!m)
+        return fail(COVEST_E_NOMEM, "covest_model_create: out of host memory");
+    m->device = device;
+    m->n_par = d->kind == COVEST_MODEL_BASIC ? 2 : 5;
+    m->n_keys = d->n_keys;
+    m->threshold = d->threshold;
+    m->has_threshold = d->has_threshold != 0;
+    DevModel &dm = m->dm;
+    fill_dev_model(dm, d, m->n_par);
 
     // Bin views.  When tail == 0 the tail term of covest/models.py:104 is exactly
     // 0 whatever sp_j is (0 * log of a positive number, or the else-branch), so
@@ -94,13 +106,9 @@ int covest_model_create(const covest_model_desc *d, covest_model **out)
 
     DeviceGuard dev_guard(m->device);
     int rc = dev_guard.status();
-    if (d->tail != 0.0) { // the evaluated view IS the full view
-        m->host_all_key.clear();
-    } else {
-        m->host_all_key = std::move(key_a);
-        m->host_all_lgam = std::move(lg_a);
-        m->host_all_cnt = std::move(cnt_a);
-    }
+    m->host_all_key = std::move(key_a); // (empty with a tail: the evaluated view IS the full view)
+    m->host_all_lgam = std::move(lg_a);
+    m->host_all_cnt = std::move(cnt_a);
     if (rc == COVEST_OK)
         rc = upload_bins(m->bins_eval, dm.bins, key_e, lg_e, cnt_e);
     if (rc == COVEST_OK && d->tail != 0.0) {
@@ -131,9 +139,10 @@ int covest_model_param_count(const covest_model *m) { return m ? m->n_par : COVE
 
 int64_t covest_model_bins_evaluated(const covest_model *m) { return m ? m->dm.bins.n : COVEST_E_INVALID; }
 
-
 } // extern "C"
 
+// Where the REFERENCE overflows (documented divergence).
+// c_src/covest_poissonmodule.c:19-24 forms the whole product prod_{i<=j} (l / i) in x87 long double BEFORE any
 // scaling, so truncated_poisson(l, j) is +inf as soon as the running product passes LDBL_MAX -- its largest
 // value is reached at i = min(j, floor(l)): l^i / i!.  A likelihood evaluation calls it for every key j of the
 // histogram and every l = o * l_s, o < threshold_o (covest/models.py:92-97, :235-241); the largest l against the
@@ -168,7 +177,6 @@ static bool reference_overflows_at(const DevModel &dm, int n_par, const double *
     const int o_max = n_par == 5 ? T - 1 : 1;
     return o_max >= 1 && reference_product_overflows((long double)((double)o_max * l_max), key_max);
 }
-
 
 namespace covest {
 
@@ -272,12 +280,10 @@ SubList sub_list_of(const covest_model *m, int t_max, void *index, void *word, v
     return l;
 }
 
-
 // `sub`: the queue the recurrence kernels append the points they hand back to (direct_point.h) -- drained right
 // behind them by the fix pass; K-direct has nothing to hand back.  The queue must be empty (counter 0) on entry.
-hipError_t launch_ll(const covest_model *m, int kernel, const PointSource &src, int64_t n,
-                            double *out, const SubList &sub, hipStream_t st, const char **name,
-                            const covest_grid *g)
+hipError_t launch_ll(const covest_model *m, int kernel, const PointSource &src, int64_t n, double *out, const SubList &sub,
+                     hipStream_t st, const char **name, const covest_grid *g)
 {
     if (kernel == COVEST_KERNEL_FACTORED) {
         if (name)
@@ -295,25 +301,242 @@ hipError_t launch_ll(const covest_model *m, int kernel, const PointSource &src, 
     return launch_ll_direct(m->dm, src, n, out, nullptr, st, kernel == COVEST_KERNEL_DIRECT_REF);
 }
 
-// Workspace of a point-list launch's queue (direct_point.h): room for n entries, counters zeroed on first use.
-
 } // namespace covest
 
 constexpr int64_t kInPlaceMaxPoints = 256;   // point lists up to this size: parameters and values in mapped host memory
 constexpr int64_t kInPlaceMaxListPoints = 4; // repeats model, list mode: tables read in place (13 KB a point, 8 workgroups each)
 
+// The queue a point-list launch hands points back through (direct_point.h): room for n entries, empty.  The counter is
+// zeroed without waiting for it: whatever touches it afterwards -- the kernels, the blocking copies of fix_points_host
+// -- is work of the same null stream and comes behind the fill, and the host never reads it.
 static int reserve_point_queue(covest_model *m, int64_t n)
 {
     HIP_TRY(m->ws_sub_index.reserve((size_t)n * sizeof(int64_t)));
     HIP_TRY(m->ws_sub_word.reserve((size_t)n * sizeof(unsigned long long)));
     HIP_TRY(m->ws_sub_ctl.reserve(sizeof(unsigned)));
-    HIP_TRY(hipMemset(m->ws_sub_ctl.ptr, 0, sizeof(unsigned))); // the queue starts empty (every point-list call)
+    HIP_TRY(hipMemsetAsync(m->ws_sub_ctl.ptr, 0, sizeof(unsigned), nullptr));
     return COVEST_OK;
 }
 
-// Point lists through K-factored's list mode: add the strict evaluation of the rows the kernel handed back
-// (words[i] != 0, direct_point.h) to out_ll[i].  Called with the model locked.
-static int fix_points_host(covest_model *m, int64_t n, const double *params, double *out_ll,
+// threshold_o of every point of a list (repeats model; the basic model has none: empty)
+static std::vector<int32_t> point_thresholds(const covest_model *m, int64_t n, const double *params)
+{
+    std::vector<int32_t> t;
+    if (m->n_par == 5) {
+        t.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i)
+            t[(size_t)i] = threshold_for_point(m, params + i * 5);
+    }
+    return t;
+}
+
+// A point list where the kernels read it and where they leave its result: stage_points.
+struct StagedPoints {
+    PointSource src{};
+    double *out = nullptr;
+    bool in_place = false; // both are the model's page-locked blocks, mapped into the device's address space
+};
+
+// Stage a whole list -- parameters, behind them the thresholds -- in the model's page-locked block, with room for
+// out_bytes of results.  A SHORT list (what scipy's refinement issues: a point and its finite-difference neighbours)
+// moves nothing through the copy engine: it is read, and its results written, IN PLACE in mapped host memory -- one wait
+// for the stream per call; a blocking copy either side of the launch was two thirds of a basic-model evaluation's 48 us.
+// A longer list goes up in ONE copy, from the page-locked block and not the caller's pageable array (HostBuf, host.h).
+static int stage_points(covest_model *m, int64_t n, const double *params, size_t out_bytes, StagedPoints &sp)
+{
+    const int P = m->n_par;
+    const std::vector<int32_t> t = point_thresholds(m, n, params);
+    const size_t par_bytes = (size_t)n * P * sizeof(double), t_bytes = (t.size() * sizeof(int32_t) + 7) / 8 * 8;
+    HIP_TRY(m->ws_stage.reserve(par_bytes + t_bytes));
+    char *base = m->ws_stage.as<char>();
+    std::memcpy(base, params, par_bytes);
+    if (!t.empty())
+        std::memcpy(base + par_bytes, t.data(), t.size() * sizeof(int32_t));
+    sp.in_place = n <= kInPlaceMaxPoints;
+    if (sp.in_place) {
+        HIP_TRY(m->ws_result.reserve(out_bytes));
+        sp.out = m->ws_result.as<double>();
+    } else {
+        HIP_TRY(m->ws_params.reserve(par_bytes + t_bytes));
+        HIP_TRY(m->ws_out.reserve(out_bytes));
+        HIP_TRY(hipMemcpy(m->ws_params.ptr, base, par_bytes + t_bytes, hipMemcpyHostToDevice));
+        base = m->ws_params.as<char>();
+        sp.out = m->ws_out.as<double>();
+    }
+    sp.src.is_grid = 0;
+    sp.src.params = reinterpret_cast<const double *>(base);
+    sp.src.t_list = P == 5 ? reinterpret_cast<const int32_t *>(base + par_bytes) : nullptr;
+    return COVEST_OK;
+}
+
+// (in place: once the caller has waited for the stream)
+static int read_result(const StagedPoints &sp, double *dst, size_t first, size_t count)
+{
+    if (sp.in_place)
+        std::memcpy(dst, sp.out + first, count * sizeof(double));
+    else
+        HIP_TRY(hipMemcpy(dst, sp.out + first, count * sizeof(double), hipMemcpyDeviceToHost));
+    return COVEST_OK;
+}
+
+// (parameters, threshold_o) of the points of a repeats-model list that idx names, in idx's order
+static void gather_points(const double *params, const std::vector<int32_t> &t, const std::vector<int64_t> &idx,
+                          std::vector<double> &sub_par, std::vector<int32_t> &sub_t)
+{
+    sub_par.resize(idx.size() * 5);
+    sub_t.resize(idx.size());
+    for (size_t k = 0; k < idx.size(); ++k) {
+        std::memcpy(&sub_par[k * 5], params + idx[k] * 5, 5 * sizeof(double));
+        sub_t[k] = t[(size_t)idx[k]];
+    }
+}
+
+// ... and up to ws_params and ws_t, for the routes that read a plain list; their values come back from ws_out, to where
+// idx says.  (eval_points_list has reserved all three for the whole call.)
+static int upload_points(covest_model *m, const double *params, const std::vector<int32_t> &t, const std::vector<int64_t> &idx,
+                         PointSource &src)
+{
+    std::vector<double> sub_par;
+    std::vector<int32_t> sub_t;
+    gather_points(params, t, idx, sub_par, sub_t);
+    HIP_TRY(hipMemcpy(m->ws_params.ptr, sub_par.data(), sub_par.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->ws_t.ptr, sub_t.data(), sub_t.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    src = PointSource{};
+    src.is_grid = 0;
+    src.params = m->ws_params.as<double>();
+    src.t_list = m->ws_t.as<int32_t>();
+    return COVEST_OK;
+}
+
+static int download_values(covest_model *m, const std::vector<int64_t> &idx, double *out_ll)
+{
+    std::vector<double> got(idx.size());
+    HIP_TRY(hipMemcpy(got.data(), m->ws_out.ptr, got.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < idx.size(); ++k)
+        out_ll[idx[k]] = got[k];
+    return COVEST_OK;
+}
+
+// One point of list mode 1 from its n_seg parts {LL part, sp_j part (hi, lo), side word}: the value, the segments added
+// in order and the tail term behind them, and in *word the segments' handed-back units, merged (0: none).
+static double combine_segments(const double *parts, int n_seg, double tail, unsigned long long *word)
+{
+    double ll = 0.0, hi = 0.0, lo = 0.0;
+    unsigned u_first = 0xFFFFFFFFu, u_last = 0;
+    bool any_unit = false;
+    for (int sg = 0; sg < n_seg; ++sg) {
+        const double *o = &parts[(size_t)sg * 4];
+        ll += o[0];
+        unsigned long long w;
+        std::memcpy(&w, &o[3], sizeof w);
+        if (w != 0) {
+            any_unit = true;
+            u_first = std::min(u_first, sub_first(w));
+            u_last = std::max(u_last, sub_last(w));
+        }
+        const double sum = hi + o[1], bb = sum - hi; // two-sum, as the kernels' CompSum
+        lo += ((hi - (sum - bb)) + (o[1] - bb)) + o[2];
+        hi = sum;
+    }
+    double tail_term = 0.0;
+    if (tail != 0.0) { // tail * log(1 - min(1, sp)), covest/models.py:103-105
+        double sp = hi + lo;
+        if (!(sp < 1.0))
+            sp = 1.0;
+        if (sp < 1.0)
+            tail_term = tail * std::log(1.0 - sp);
+    }
+    *word = any_unit ? sub_word(u_first, u_last, true) : 0ull;
+    return ll + tail_term;
+}
+
+// threshold_o - 1 within a workgroup's lanes: one workgroup per (point, key segment), list mode 1.  The kernel stores the
+// segments' parts straight into mapped host memory, 256 bytes a point, and the list's tables go up asynchronously: ONE
+// wait for the stream instead of a blocking copy either side of the launch, a third of a single evaluation's 75 us.
+static int list_points_fitting(covest_model *m, const double *params, const std::vector<int32_t> &t,
+                               const std::vector<int64_t> &idx, const SubList &none, double *out_ll,
+                               std::vector<unsigned long long> &words)
+{
+    std::vector<double> sub_par;
+    std::vector<int32_t> sub_t;
+    gather_points(params, t, idx, sub_par, sub_t);
+    FactoredPlan pl;
+    const int rc = build_list_plan(m, (int64_t)idx.size(), sub_par.data(), sub_t, nullptr, m->ws_plan, pl,
+                                   (int64_t)idx.size() <= kInPlaceMaxListPoints);
+    if (rc != COVEST_OK)
+        return rc;
+    HIP_TRY(m->ws_result.reserve(idx.size() * (size_t)pl.n_seg * 4 * sizeof(double)));
+    pl.partial = m->ws_result.as<double>();
+    record_factored_plan(pl, 0, false);
+    HIP_TRY(launch_ll_factored(m->dm, m->tv, pl, m->ws_out.as<double>(), none, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    for (size_t k = 0; k < idx.size(); ++k)
+        out_ll[idx[k]] = combine_segments(pl.partial + k * (size_t)pl.n_seg * 4, pl.n_seg, m->dm.tail, &words[(size_t)idx[k]]);
+    return COVEST_OK;
+}
+
+// threshold_o beyond that: the point is cut into chunks of kListLanes copy numbers, one workgroup each (list mode 2),
+// and ll_finish_partials adds the chunks' p_j and takes the logs.
+static int list_points_chunked(covest_model *m, const double *params, const std::vector<int32_t> &t,
+                               const std::vector<int64_t> &idx, const SubList &none, double *out_ll)
+{
+    std::vector<double> item_par, point_par;
+    std::vector<int32_t> item_t, item_ob, first_item(idx.size() + 1, 0), point_t;
+    gather_points(params, t, idx, point_par, point_t);
+    for (size_t k = 0; k < idx.size(); ++k) {
+        for (int ob = 0; ob < point_t[k] - 1; ob += kListLanes) {
+            item_par.insert(item_par.end(), &point_par[5 * k], &point_par[5 * k] + 5);
+            item_t.push_back(point_t[k]);
+            item_ob.push_back(ob);
+        }
+        first_item[k + 1] = (int32_t)item_t.size();
+    }
+    const int64_t n_items = (int64_t)item_t.size();
+    const size_t n_keys = (size_t)m->tv.n_items * kTileBins; // rows of the items (tiles.h)
+    FactoredPlan pl;
+    const int rc = build_list_plan(m, n_items, item_par.data(), item_t, &item_ob, m->ws_plan2, pl);
+    if (rc != COVEST_OK)
+        return rc;
+    HIP_TRY(m->ws_partial.reserve((size_t)n_items * n_keys * sizeof(double)));
+    // what the two kernels read besides the plan, in one copy: the items' first copy numbers | each point's first item |
+    // the points' thresholds | (8-byte aligned) the points' parameters
+    const size_t items_bytes = (size_t)n_items * sizeof(int32_t), first_bytes = first_item.size() * sizeof(int32_t);
+    const size_t pt_bytes = point_t.size() * sizeof(int32_t);
+    const size_t int_bytes = ((items_bytes + first_bytes + pt_bytes + 7) / 8) * 8;
+    std::vector<char> stage(int_bytes + point_par.size() * sizeof(double));
+    std::memcpy(stage.data(), item_ob.data(), items_bytes);
+    std::memcpy(stage.data() + items_bytes, first_item.data(), first_bytes);
+    std::memcpy(stage.data() + items_bytes + first_bytes, point_t.data(), pt_bytes);
+    std::memcpy(stage.data() + int_bytes, point_par.data(), point_par.size() * sizeof(double));
+    HIP_TRY(m->ws_items.reserve(stage.size()));
+    const char *ib = m->ws_items.as<char>();
+    HIP_TRY(hipMemcpy(m->ws_items.ptr, stage.data(), stage.size(), hipMemcpyHostToDevice));
+    pl.list_mode = 2;
+    pl.item_obase = reinterpret_cast<const int32_t *>(ib);
+    pl.partial = m->ws_partial.as<double>();
+    record_factored_plan(pl, 0, false);
+    HIP_TRY(launch_ll_factored(m->dm, m->tv, pl, m->ws_out.as<double>(), none, nullptr));
+    HIP_TRY(launch_ll_finish_partials(m->dm, m->tv, pl.partial, reinterpret_cast<const int32_t *>(ib + items_bytes),
+                                      reinterpret_cast<const double *>(ib + int_bytes),
+                                      reinterpret_cast<const int32_t *>(ib + items_bytes + first_bytes), (int64_t)idx.size(),
+                                      m->ws_out.as<double>(), nullptr));
+    return download_values(m, idx, out_ll);
+}
+
+// threshold_o == 1, nothing to sum over: K-direct
+static int list_points_direct(covest_model *m, const double *params, const std::vector<int32_t> &t,
+                              const std::vector<int64_t> &idx, const SubList &none, double *out_ll)
+{
+    PointSource src;
+    const int rc = upload_points(m, params, t, idx, src);
+    if (rc != COVEST_OK)
+        return rc;
+    HIP_TRY(launch_ll(m, COVEST_KERNEL_DIRECT, src, (int64_t)idx.size(), m->ws_out.as<double>(), none, nullptr, nullptr));
+    return download_values(m, idx, out_ll);
+}
+
+// Add the strict evaluation of the keys list mode 1 handed back (words[i] != 0, direct_point.h) to out_ll[i].
+static int fix_points_host(covest_model *m, int64_t n, const double *params, const std::vector<int32_t> &t, double *out_ll,
                            const std::vector<unsigned long long> &words)
 {
     std::vector<int64_t> again;
@@ -322,16 +545,11 @@ static int fix_points_host(covest_model *m, int64_t n, const double *params, dou
             again.push_back(i);
     if (again.empty())
         return COVEST_OK;
-    const int P = m->n_par;
     const size_t na = again.size();
-    std::vector<double> sub_par(na * (size_t)P), sub_ll(na);
-    std::vector<int32_t> sub_t(na, 2);
+    std::vector<double> sub_ll(na);
     std::vector<unsigned long long> sub_w(na);
     std::vector<int64_t> sub_i(na);
     for (size_t k = 0; k < na; ++k) {
-        std::memcpy(&sub_par[k * (size_t)P], params + again[k] * P, (size_t)P * sizeof(double));
-        if (P == 5)
-            sub_t[k] = threshold_for_point(m, params + again[k] * P);
         sub_ll[k] = out_ll[again[k]];
         sub_w[k] = words[(size_t)again[k]];
         sub_i[k] = (int64_t)k;
@@ -339,29 +557,76 @@ static int fix_points_host(covest_model *m, int64_t n, const double *params, dou
     int rc = reserve_point_queue(m, (int64_t)na);
     if (rc != COVEST_OK)
         return rc;
-    HIP_TRY(m->ws_params.reserve(sub_par.size() * sizeof(double)));
-    HIP_TRY(m->ws_t.reserve(na * sizeof(int32_t)));
-    HIP_TRY(m->ws_out.reserve(na * sizeof(double)));
-    HIP_TRY(hipMemcpy(m->ws_params.ptr, sub_par.data(), sub_par.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->ws_t.ptr, sub_t.data(), na * sizeof(int32_t), hipMemcpyHostToDevice));
+    PointSource src;
+    rc = upload_points(m, params, t, again, src);
+    if (rc != COVEST_OK)
+        return rc;
     HIP_TRY(hipMemcpy(m->ws_out.ptr, sub_ll.data(), na * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m->ws_sub_index.ptr, sub_i.data(), na * sizeof(int64_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m->ws_sub_word.ptr, sub_w.data(), na * sizeof(unsigned long long), hipMemcpyHostToDevice));
-    const unsigned count = (unsigned)na;
+    const unsigned count = (unsigned)na; // the queue arrives full
     HIP_TRY(hipMemcpy(m->ws_sub_ctl.ptr, &count, sizeof count, hipMemcpyHostToDevice));
-    PointSource src{};
-    src.is_grid = 0;
-    src.params = m->ws_params.as<double>();
-    src.t_list = P == 5 ? m->ws_t.as<int32_t>() : nullptr;
     HIP_TRY(launch_ll_fix_list(m->dm, m->tv, src, m->ws_out.as<double>(),
-                               sub_list_of(m, m->n_par == 5 ? 513 : 2, m->ws_sub_index.ptr, m->ws_sub_word.ptr, m->ws_sub_ctl.ptr), nullptr,
-                               (int64_t)na));
-    HIP_TRY(hipMemcpy(sub_ll.data(), m->ws_out.ptr, na * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < na; ++k)
-        out_ll[again[k]] = sub_ll[k];
-    return COVEST_OK;
+                               sub_list_of(m, kListLanes + 1, m->ws_sub_index.ptr, m->ws_sub_word.ptr, m->ws_sub_ctl.ptr),
+                               nullptr, (int64_t)na));
+    return download_values(m, again, out_ll);
 }
 
+// A repeats-model point list through K-factored's list mode.  A point's route depends on its own threshold_o only --
+// never on what else is in the call (refinements compare values across calls).  Called with the model locked.
+static int eval_points_list(covest_model *m, int64_t n, const double *params, double *out_ll)
+{
+    const std::vector<int32_t> t = point_thresholds(m, n, params);
+    std::vector<int64_t> fits, big, rest;
+    for (int64_t i = 0; i < n; ++i) {
+        const int o_max = t[(size_t)i] - 1;
+        (o_max < 1 ? rest : o_max <= kListLanes ? fits : big).push_back(i);
+    }
+    // (what upload_points and download_values use: any subset of the call fits)
+    HIP_TRY(m->ws_out.reserve((size_t)n * sizeof(double)));
+    HIP_TRY(m->ws_params.reserve((size_t)n * 5 * sizeof(double)));
+    HIP_TRY(m->ws_t.reserve((size_t)n * sizeof(int32_t)));
+    const SubList none = sub_list_of(m, kListLanes + 1, nullptr, nullptr, nullptr); // (list mode and K-direct hand nothing back)
+    std::vector<unsigned long long> words((size_t)n, 0ull); // keys handed back per point (direct_point.h)
+    int rc = fits.empty() ? COVEST_OK : list_points_fitting(m, params, t, fits, none, out_ll, words);
+    if (rc == COVEST_OK && !big.empty())
+        rc = list_points_chunked(m, params, t, big, none, out_ll);
+    if (rc == COVEST_OK && !rest.empty())
+        rc = list_points_direct(m, params, t, rest, none, out_ll);
+    return rc != COVEST_OK ? rc : fix_points_host(m, n, params, t, out_ll, words);
+}
+
+// covest_eval_points_grad (order 1) and covest_eval_points_hess (order 2): the device leaves values | gradients |
+// Hessians (the last block only for order 2) in one buffer; `who` names the entry point in the messages.
+static int eval_points_deriv(covest_model *m, int order, int64_t n, const double *params, double *out_ll, double *out_grad,
+                             double *out_hess, const char *who)
+{
+    if (!m || n < 0 || (n > 0 && (!params || !out_ll || !out_grad || (order == 2 && !out_hess))))
+        return fail(COVEST_E_INVALID, std::string(who) + ": bad argument");
+    if (n == 0)
+        return COVEST_OK;
+    std::lock_guard<std::mutex> guard(m->lock);
+    DeviceGuard dev_guard(m->device);
+    int rc = dev_guard.status();
+    if (rc != COVEST_OK)
+        return rc;
+    const int P = m->n_par;
+    StagedPoints sp;
+    rc = stage_points(m, n, params, (size_t)n * (1 + P + (order == 2 ? P * P : 0)) * sizeof(double), sp);
+    if (rc != COVEST_OK)
+        return rc;
+    HIP_TRY(m->ws_partial.reserve(ll_deriv_partial_bytes(m->dm, order, n)));
+    HIP_TRY(launch_ll_deriv(m->dm, order, sp.src, n, m->ws_partial.as<double>(), sp.out, sp.out + n, sp.out + n * (1 + P),
+                            nullptr));
+    if (sp.in_place)
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    rc = read_result(sp, out_ll, 0, (size_t)n);
+    if (rc == COVEST_OK)
+        rc = read_result(sp, out_grad, (size_t)n, (size_t)n * P);
+    if (rc == COVEST_OK && order == 2)
+        rc = read_result(sp, out_hess, (size_t)n * (1 + P), (size_t)n * P * P);
+    return rc;
+}
 
 extern "C" {
 
@@ -386,266 +651,23 @@ int covest_eval_points(covest_model *m, int64_t n, const double *params, double 
     if (rc != COVEST_OK)
         return rc;
     LaunchRecordScope record(m->record);
-    const int P = m->n_par;
-    // A SMALL list (what scipy's refinement issues: a point and its P finite-difference neighbours) moves nothing through
-    // the copy engine (round 5): its parameters are read, and its values written, IN PLACE in page-locked host memory
-    // mapped into the device's address space -- one launch (two with the strict pass) and one wait for the stream; a
-    // blocking copy either side of the launch was two thirds of a basic-model evaluation's 48 us.
-    const bool in_place = n <= kInPlaceMaxPoints;
-    PointSource src{};
-    src.is_grid = 0;
-    double *out_dev = nullptr; // where the kernels leave the values: HBM, or (in_place) the mapped host block
-    SubList queue = sub_list_of(m, m->n_par == 5 ? 513 : 2, nullptr, nullptr, nullptr); // (list mode and K-direct hand nothing back)
-    if (kern != COVEST_KERNEL_FACTORED) {
-        std::vector<int32_t> t;
-        if (P == 5) {
-            t.resize((size_t)n);
-            for (int64_t i = 0; i < n; ++i)
-                t[(size_t)i] = threshold_for_point(m, params + i * P);
-        }
-        const size_t par_bytes = (size_t)n * P * sizeof(double), t_bytes = ((size_t)n * sizeof(int32_t) + 7) / 8 * 8;
-        if (in_place) {
-            HIP_TRY(m->ws_stage.reserve(par_bytes + t_bytes));
-            HIP_TRY(m->ws_result.reserve((size_t)n * sizeof(double)));
-            char *st = m->ws_stage.as<char>();
-            std::memcpy(st, params, par_bytes);
-            if (P == 5)
-                std::memcpy(st + par_bytes, t.data(), (size_t)n * sizeof(int32_t));
-            src.params = reinterpret_cast<const double *>(st);
-            src.t_list = P == 5 ? reinterpret_cast<const int32_t *>(st + par_bytes) : nullptr;
-            out_dev = m->ws_result.as<double>();
-        } else {
-            HIP_TRY(m->ws_params.reserve(par_bytes));
-            HIP_TRY(m->ws_out.reserve((size_t)n * sizeof(double)));
-            HIP_TRY(hipMemcpy(m->ws_params.ptr, params, par_bytes, hipMemcpyHostToDevice));
-            src.params = m->ws_params.as<double>();
-            if (P == 5) {
-                HIP_TRY(m->ws_t.reserve((size_t)n * sizeof(int32_t)));
-                HIP_TRY(hipMemcpy(m->ws_t.ptr, t.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-                src.t_list = m->ws_t.as<int32_t>();
-            }
-            out_dev = m->ws_out.as<double>();
-        }
-        if (kern == COVEST_KERNEL_RECUR) { // K-basic hands points back through the queue (direct_point.h): empty on entry
-            HIP_TRY(m->ws_sub_index.reserve((size_t)n * sizeof(int64_t)));
-            HIP_TRY(m->ws_sub_word.reserve((size_t)n * sizeof(unsigned long long)));
-            HIP_TRY(m->ws_sub_ctl.reserve(sizeof(unsigned)));
-            HIP_TRY(hipMemsetAsync(m->ws_sub_ctl.ptr, 0, sizeof(unsigned), nullptr));
-            queue = sub_list_of(m, 2, m->ws_sub_index.ptr, m->ws_sub_word.ptr, m->ws_sub_ctl.ptr);
-        }
-    } else {
-        HIP_TRY(m->ws_out.reserve((size_t)n * sizeof(double)));
-        HIP_TRY(m->ws_params.reserve((size_t)n * P * sizeof(double)));
-        HIP_TRY(m->ws_t.reserve((size_t)n * sizeof(int32_t)));
-        src.params = m->ws_params.as<double>();
-        src.t_list = m->ws_t.as<int32_t>();
-    }
-    if (kern == COVEST_KERNEL_FACTORED) {
-        // repeats model point list: one workgroup per point (build_list_plan); a point whose threshold_o
-        // exceeds a workgroup's 512 lanes is cut into chunks of 512 copy numbers, one workgroup each, and
-        // finished by ll_finish_partials.  A point's route depends on its own threshold_o only -- never on
-        // what else is in the call (refinements compare values across calls).  threshold_o == 1 (nothing to
-        // sum) goes to K-direct.
-        std::vector<int32_t> t((size_t)n);
-        std::vector<int64_t> fits, big, rest;
-        std::vector<unsigned long long> words((size_t)n, 0ull); // keys handed back per point (direct_point.h)
-        for (int64_t i = 0; i < n; ++i) {
-            t[(size_t)i] = threshold_for_point(m, params + i * P);
-            const int o_max = t[(size_t)i] - 1;
-            (o_max < 1 ? rest : o_max <= 512 ? fits : big).push_back(i);
-        }
-        if (!fits.empty()) {
-            std::vector<double> sub_par(fits.size() * 5);
-            std::vector<int32_t> sub_t(fits.size());
-            for (size_t k = 0; k < fits.size(); ++k) {
-                std::memcpy(&sub_par[k * 5], params + fits[k] * 5, 5 * sizeof(double));
-                sub_t[k] = t[(size_t)fits[k]];
-            }
-            FactoredPlan pl;
-            rc = build_list_plan(m, (int64_t)fits.size(), sub_par.data(), sub_t, nullptr, m->ws_plan, pl,
-                                 (int64_t)fits.size() <= kInPlaceMaxListPoints);
-            if (rc != COVEST_OK)
-                return rc;
-            // {LL part, sp_j part (hi, lo), side word} per (point, key segment); the segments are added here, in order
-            // (round 5: the kernel stores them straight into page-locked, device-mapped host memory -- 256 bytes a point --
-            // and the list's tables go up asynchronously: ONE wait for the stream per call instead of a blocking copy
-            // either side of the launch, a third of a single evaluation's 75 us)
-            const size_t n_parts = fits.size() * (size_t)pl.n_seg;
-            m->ws_result.flags = hipHostMallocPortable | hipHostMallocMapped;
-            HIP_TRY(m->ws_result.reserve(n_parts * 4 * sizeof(double)));
-            pl.partial = m->ws_result.as<double>();
-            record_factored_plan(pl, 0, false);
-            HIP_TRY(launch_ll_factored(m->dm, m->tv, pl, m->ws_out.as<double>(), queue, nullptr));
-            HIP_TRY(hipStreamSynchronize(nullptr));
-            const double *got = m->ws_result.as<double>();
-            for (size_t k = 0; k < fits.size(); ++k) {
-                double ll = 0.0, hi = 0.0, lo = 0.0;
-                unsigned u_first = 0xFFFFFFFFu, u_last = 0; // the segments' handed-back units, merged
-                bool any_unit = false;
-                for (int sg = 0; sg < pl.n_seg; ++sg) {
-                    const double *o = &got[(k * (size_t)pl.n_seg + (size_t)sg) * 4];
-                    ll += o[0];
-                    unsigned long long w;
-                    std::memcpy(&w, &o[3], sizeof w);
-                    if (w != 0) {
-                        any_unit = true;
-                        u_first = std::min(u_first, sub_first(w));
-                        u_last = std::max(u_last, sub_last(w));
-                    }
-                    const double sum = hi + o[1], bb = sum - hi; // two-sum, as the kernels' CompSum
-                    lo += ((hi - (sum - bb)) + (o[1] - bb)) + o[2];
-                    hi = sum;
-                }
-                double tail_term = 0.0;
-                if (m->dm.tail != 0.0) { // tail * log(1 - min(1, sp)), covest/models.py:103-105
-                    double sp = hi + lo;
-                    if (!(sp < 1.0))
-                        sp = 1.0;
-                    if (sp < 1.0)
-                        tail_term = m->dm.tail * std::log(1.0 - sp);
-                }
-                out_ll[fits[k]] = ll + tail_term;
-                words[(size_t)fits[k]] = any_unit ? sub_word(u_first, u_last, true) : 0ull;
-            }
-        }
-        if (!big.empty()) {
-            std::vector<double> item_par, point_par(5 * big.size());
-            std::vector<int32_t> item_t, item_ob, first_item(big.size() + 1, 0), point_t(big.size());
-            for (size_t k = 0; k < big.size(); ++k) {
-                const double *par = params + big[k] * 5;
-                std::memcpy(&point_par[5 * k], par, 5 * sizeof(double));
-                point_t[k] = t[(size_t)big[k]];
-                for (int ob = 0; ob < t[(size_t)big[k]] - 1; ob += 512) {
-                    item_par.insert(item_par.end(), par, par + 5);
-                    item_t.push_back(t[(size_t)big[k]]);
-                    item_ob.push_back(ob);
-                }
-                first_item[k + 1] = (int32_t)item_t.size();
-            }
-            const int64_t n_items = (int64_t)item_t.size();
-            const size_t n_keys = (size_t)m->tv.n_items * kTileBins; // rows of the items (tiles.h)
-            FactoredPlan pl;
-            rc = build_list_plan(m, n_items, item_par.data(), item_t, &item_ob, m->ws_plan2, pl);
-            if (rc != COVEST_OK)
-                return rc;
-            HIP_TRY(m->ws_partial.reserve((size_t)n_items * n_keys * sizeof(double)));
-            const size_t items_bytes = (size_t)n_items * sizeof(int32_t), first_bytes = first_item.size() * sizeof(int32_t);
-            const size_t pt_bytes = point_t.size() * sizeof(int32_t);
-            const size_t int_bytes = ((items_bytes + first_bytes + pt_bytes + 7) / 8) * 8;
-            HIP_TRY(m->ws_items.reserve(int_bytes + point_par.size() * sizeof(double)));
-            char *ib = m->ws_items.as<char>();
-            {
-                std::vector<char> stage(int_bytes + point_par.size() * sizeof(double)); // one copy
-                std::memcpy(stage.data(), item_ob.data(), items_bytes);
-                std::memcpy(stage.data() + items_bytes, first_item.data(), first_bytes);
-                std::memcpy(stage.data() + items_bytes + first_bytes, point_t.data(), pt_bytes);
-                std::memcpy(stage.data() + int_bytes, point_par.data(), point_par.size() * sizeof(double));
-                HIP_TRY(hipMemcpy(ib, stage.data(), stage.size(), hipMemcpyHostToDevice));
-            }
-            pl.list_mode = 2;
-            pl.item_obase = reinterpret_cast<const int32_t *>(ib);
-            pl.partial = m->ws_partial.as<double>();
-            record_factored_plan(pl, 0, false);
-            HIP_TRY(launch_ll_factored(m->dm, m->tv, pl, m->ws_out.as<double>(), queue, nullptr));
-            HIP_TRY(launch_ll_finish_partials(m->dm, m->tv, pl.partial, reinterpret_cast<const int32_t *>(ib + items_bytes),
-                                              reinterpret_cast<const double *>(ib + int_bytes),
-                                              reinterpret_cast<const int32_t *>(ib + items_bytes + first_bytes),
-                                              (int64_t)big.size(), m->ws_out.as<double>(), nullptr));
-            std::vector<double> got(big.size());
-            HIP_TRY(hipMemcpy(got.data(), m->ws_out.ptr, big.size() * sizeof(double), hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < big.size(); ++k)
-                out_ll[big[k]] = got[k];
-        }
-        if (!rest.empty()) {
-            std::vector<double> sub_par(rest.size() * 5);
-            std::vector<int32_t> sub_t(rest.size());
-            for (size_t k = 0; k < rest.size(); ++k) {
-                std::memcpy(&sub_par[k * 5], params + rest[k] * 5, 5 * sizeof(double));
-                sub_t[k] = t[(size_t)rest[k]];
-            }
-            HIP_TRY(hipMemcpy(m->ws_params.ptr, sub_par.data(), sub_par.size() * sizeof(double), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(m->ws_t.ptr, sub_t.data(), sub_t.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            HIP_TRY(launch_ll(m, COVEST_KERNEL_DIRECT, src, (int64_t)rest.size(), m->ws_out.as<double>(), queue, nullptr, nullptr));
-            std::vector<double> got(rest.size());
-            HIP_TRY(hipMemcpy(got.data(), m->ws_out.ptr, rest.size() * sizeof(double), hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < rest.size(); ++k)
-                out_ll[rest[k]] = got[k];
-        }
-        return fix_points_host(m, n, params, out_ll, words);
-    }
-    // (K-basic is followed by the pass that patches the points it handed back: launch_ll)
-    HIP_TRY(launch_ll(m, kern, src, n, out_dev, queue, nullptr, nullptr));
-    if (in_place) {
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        std::memcpy(out_ll, out_dev, (size_t)n * sizeof(double));
-    } else {
-        HIP_TRY(hipMemcpy(out_ll, out_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return COVEST_OK;
-}
-
-// covest_eval_points_grad (order 1) and covest_eval_points_hess (order 2): the device leaves values | gradients |
-// Hessians (the last block only for order 2) in one buffer; `who` names the entry point in the messages.
-static int eval_points_deriv(covest_model *m, int order, int64_t n, const double *params, double *out_ll, double *out_grad,
-                             double *out_hess, const char *who)
-{
-    if (!m || n < 0 || (n > 0 && (!params || !out_ll || !out_grad || (order == 2 && !out_hess))))
-        return fail(COVEST_E_INVALID, std::string(who) + ": bad argument");
-    if (n == 0)
-        return COVEST_OK;
-    std::lock_guard<std::mutex> guard(m->lock);
-    DeviceGuard dev_guard(m->device);
-    int rc = dev_guard.status();
+    if (kern == COVEST_KERNEL_FACTORED)
+        return eval_points_list(m, n, params, out_ll);
+    StagedPoints sp;
+    rc = stage_points(m, n, params, (size_t)n * sizeof(double), sp);
     if (rc != COVEST_OK)
         return rc;
-    const int P = m->n_par;
-    std::vector<int32_t> t;
-    if (P == 5) {
-        t.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i)
-            t[(size_t)i] = threshold_for_point(m, params + i * P);
+    SubList queue = sub_list_of(m, m->n_par == 5 ? kListLanes + 1 : 2, nullptr, nullptr, nullptr); // (K-direct hands nothing back)
+    if (kern == COVEST_KERNEL_RECUR) { // K-basic hands points back through the queue, and launch_ll's fix pass drains it
+        rc = reserve_point_queue(m, n);
+        if (rc != COVEST_OK)
+            return rc;
+        queue = sub_list_of(m, 2, m->ws_sub_index.ptr, m->ws_sub_word.ptr, m->ws_sub_ctl.ptr);
     }
-    const size_t par_bytes = (size_t)n * P * sizeof(double), t_bytes = ((size_t)n * sizeof(int32_t) + 7) / 8 * 8;
-    const size_t out_bytes = (size_t)n * (1 + P + (order == 2 ? P * P : 0)) * sizeof(double);
-    HIP_TRY(m->ws_deriv_partial.reserve(ll_deriv_partial_bytes(m->dm, order, n)));
-    HIP_TRY(m->ws_deriv_stage.reserve(par_bytes + t_bytes));
-    char *st = m->ws_deriv_stage.as<char>();
-    std::memcpy(st, params, par_bytes);
-    if (P == 5)
-        std::memcpy(st + par_bytes, t.data(), (size_t)n * sizeof(int32_t));
-    // a short list (a refinement's requests, the point of a fit) moves nothing through the copy engine, as in
-    // covest_eval_points
-    const bool in_place = n <= kInPlaceMaxPoints;
-    PointSource src{};
-    src.is_grid = 0;
-    double *out_dev;
-    if (in_place) {
-        HIP_TRY(m->ws_deriv_result.reserve(out_bytes));
-        src.params = reinterpret_cast<const double *>(st);
-        src.t_list = P == 5 ? reinterpret_cast<const int32_t *>(st + par_bytes) : nullptr;
-        out_dev = m->ws_deriv_result.as<double>();
-    } else {
-        HIP_TRY(m->ws_params.reserve(par_bytes + t_bytes));
-        HIP_TRY(m->ws_deriv_out.reserve(out_bytes));
-        HIP_TRY(hipMemcpy(m->ws_params.ptr, st, par_bytes + t_bytes, hipMemcpyHostToDevice));
-        src.params = m->ws_params.as<double>();
-        src.t_list = P == 5 ? reinterpret_cast<const int32_t *>(m->ws_params.as<char>() + par_bytes) : nullptr;
-        out_dev = m->ws_deriv_out.as<double>();
-    }
-    HIP_TRY(launch_ll_deriv(m->dm, order, src, n, m->ws_deriv_partial.as<double>(), out_dev, out_dev + n, out_dev + n * (1 + P),
-                            nullptr));
-    // the blocks of the device's buffer and where each goes
-    const struct { double *dst; size_t first, count; } blocks[3] = {
-        {out_ll, 0, (size_t)n}, {out_grad, (size_t)n, (size_t)n * P}, {out_hess, (size_t)n * (1 + P), (size_t)n * P * P}};
-    if (in_place)
+    HIP_TRY(launch_ll(m, kern, sp.src, n, sp.out, queue, nullptr, nullptr));
+    if (sp.in_place)
         HIP_TRY(hipStreamSynchronize(nullptr));
-    for (int b = 0; b <= order; ++b) {
-        if (in_place)
-            std::memcpy(blocks[b].dst, out_dev + blocks[b].first, blocks[b].count * sizeof(double));
-        else
-            HIP_TRY(hipMemcpy(blocks[b].dst, out_dev + blocks[b].first, blocks[b].count * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return COVEST_OK;
+    return read_result(sp, out_ll, 0, (size_t)n);
 }
 
 int covest_eval_points_grad(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad)
@@ -672,10 +694,9 @@ int covest_reference_overflow(const covest_model *m, int64_t n, const double *pa
     if (!m || n < 0 || (n > 0 && (!params || !flags)))
         return fail(COVEST_E_INVALID, "covest_reference_overflow: bad argument");
     const int P = m->n_par;
-    for (int64_t i = 0; i < n; ++i) {
-        const int T = P == 5 ? threshold_for_point(m, params + i * P) : 2;
-        flags[i] = reference_overflows_at(m->dm, P, params + i * P, T, m->key_max) ? 1 : 0;
-    }
+    const std::vector<int32_t> t = point_thresholds(m, n, params);
+    for (int64_t i = 0; i < n; ++i)
+        flags[i] = reference_overflows_at(m->dm, P, params + i * P, t.empty() ? 2 : t[(size_t)i], m->key_max) ? 1 : 0;
     return COVEST_OK;
 }
 
@@ -720,8 +741,5 @@ int covest_probabilities(covest_model *m, const double *params, int32_t clamp, d
     HIP_TRY(hipMemcpy(out_p, m->ws_p.ptr, (size_t)m->n_keys * sizeof(double), hipMemcpyDeviceToHost));
     return COVEST_OK;
 }
-
-// Everything a grid handle holds besides its identity: called by covest_grid_create and covest_grid_reset.  Device
-// memory is only ever grown, and the small inputs (axes, threshold table, the queue's counter) go up in ONE copy:
 
 } // extern "C"

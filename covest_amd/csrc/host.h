@@ -2,7 +2,8 @@
 //   host_common.cpp   error state, device selection, ln j! table, threshold_o (host, libm)
 //   tiles_host.cpp    bins and the tile table of the recurrence kernels (tiles.h)
 //   plan_factored.cpp K-factored's work descriptions: dense-grid parts, point lists (tiles.h FactoredPlan)
-//   abi_model.cpp     covest_model_*, covest_eval_points, covest_probabilities, kernel dispatch
+//   abi_model.cpp     covest_model_*, covest_eval_points (and _grad, _hess), covest_probabilities,
+//                     covest_reference_overflow, kernel dispatch
 //   abi_grid.cpp      covest_grid_*
 //   kmer_host.cpp     covest_kmer_*
 //   thin_host.cpp     covest_thin_histogram*
@@ -233,16 +234,17 @@ struct covest_model {
     DevBuf tiles_buf;
     TileView tv{};
     bool has_tiles = false;
-    // scratch for covest_eval_points / covest_probabilities
-    DevBuf ws_params, ws_t, ws_out, ws_p, ws_plan, ws_plan2, ws_partial, ws_items;
-    HostBuf ws_stage; // staging of a point list's tables (build_list_plan)
-    HostBuf ws_result; // page-locked, device-mapped: what a point-list launch leaves for the host (list mode 1's parts)
+    // Scratch of the point-list entry points (covest_eval_points, _grad, _hess) and covest_probabilities.  Every use is
+    // under `lock`, so the entry points share them; they only grow.
+    DevBuf ws_params, ws_t, ws_out, ws_p; // a list's parameters and thresholds, and its results, in HBM; p_j
+    DevBuf ws_plan, ws_plan2, ws_partial, ws_items; // list mode 1's plan; list mode 2's plan, partial sums (p_j per chunk;
+                                                    // ll_deriv's per segment), list mode 2's item tables
+    // Page-locked, device-mapped.  ws_stage: where a call stages what goes up, and where a short list is read in place --
+    // the whole list (stage_points, abi_model.cpp) or a K-factored list's tables (build_list_plan), never both in one call:
+    // list mode keeps its parameters out of it.  ws_result: what a short list's kernels write for the host in place --
+    // values (and gradients, Hessians), or list mode 1's parts.
+    HostBuf ws_stage, ws_result;
     DevBuf ws_sub_index, ws_sub_word, ws_sub_ctl; // the queue of handed-back points of a point-list launch (direct_point.h)
-    // covest_eval_points_grad / _hess (every use under `lock`, so the two share them): the segments' partial sums, a long
-    // list's values, gradients and Hessians, and the page-locked, device-mapped blocks a short list's parameters are read
-    // from and its results written to in place
-    DevBuf ws_deriv_partial, ws_deriv_out;
-    HostBuf ws_deriv_stage, ws_deriv_result;
     LaunchRecord record; // what the last covest_eval_points launched (covest_model_launch_record)
     std::mutex lock;
 };
@@ -371,6 +373,9 @@ int grid_stage_begin(covest_grid *g, size_t bytes, StageSlot &slot);
 int grid_stage_commit(covest_grid *g, StageSlot &slot, void *dst, size_t bytes);
 
 // ---- plan_factored.cpp
+constexpr int kListLanes = 512; // copy numbers a list-mode workgroup holds, one a lane: a point with threshold_o - 1
+                                // beyond them is cut into chunks of this many (covest_eval_points)
+static_assert(kListLanes + 1 == 513, "include/covest_amd.h documents the largest threshold_o of an uncut point");
 double copy_number_weight_host(double q1, double q2, double q, int o);
 int build_factored_plan(covest_grid *g, const double *const *axes, const int64_t *axis_len,
                         const std::vector<int32_t> &t_table);

@@ -404,6 +404,4 @@ int covest_threshold_o(int64_t n, const double *q123, double threshold, int32_t 
     return COVEST_OK;
 }
 
-// ---- where the REFERENCE overflows (documented divergence) ----
-
 } // extern "C"

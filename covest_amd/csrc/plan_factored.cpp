@@ -574,7 +574,7 @@ int build_list_plan(covest_model *m, int64_t n, const double *params, const std:
     auto o_base_of = [&](int64_t i) { return o_base_list ? (*o_base_list)[(size_t)i] : 0; };
     int t_max = 1; // largest LOCAL threshold: copy numbers of an item are o_base + 1 .. o_base + t_local - 1
     for (int64_t i = 0; i < n; ++i)
-        t_max = std::max(t_max, std::min(513, (int)t_list[(size_t)i] - o_base_of(i)));
+        t_max = std::max(t_max, std::min(kListLanes + 1, (int)t_list[(size_t)i] - o_base_of(i)));
     const int ld = factored_ld(t_max - 1);
     const int n_buf = factored_n_buf(ld);
     const size_t n_slots = (size_t)n * 16, n_blocks = 1 + 2 * (size_t)n, n_unit = n_blocks * MU;
@@ -587,8 +587,8 @@ int build_list_plan(covest_model *m, int64_t n, const double *params, const std:
         axes[(size_t)n + (size_t)p] = par[1];
         const double q1 = clamp_one(m->dm, 2, par[2]), q2 = clamp_one(m->dm, 3, par[3]), q = clamp_one(m->dm, 4, par[4]);
         const int ob = o_base_of(p);
-        // local threshold: the kernel's lanes count from the chunk's start, and a chunk ends after 512 copy numbers
-        const int t = std::min(513, std::max(0, (int)t_list[(size_t)p] - ob));
+        // local threshold: the kernel's lanes count from the chunk's start, and a chunk ends after kListLanes copy numbers
+        const int t = std::min(kListLanes + 1, std::max(0, (int)t_list[(size_t)p] - ob));
         const size_t slot = (size_t)p * 16;
         q_t[slot] = t;
         q_orig[slot] = 0;
@@ -692,7 +692,7 @@ int build_list_plan(covest_model *m, int64_t n, const double *params, const std:
     pl.flat_end = n;
     pl.list_mode = 1;
     // (one value for every point list, whatever it holds: a point's value must not depend on its company)
-    pl.p_clamp = clamp_for(m, 513);
+    pl.p_clamp = clamp_for(m, kListLanes + 1);
     pl.n_seg = std::max(1, std::min(kListSegments, (int)m->tv.n_items)); // a function of the histogram alone
     pl.item_obase = nullptr;
     pl.partial = nullptr;
