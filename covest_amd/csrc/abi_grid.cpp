@@ -45,13 +45,13 @@ int grid_stage_commit(covest_grid *g, StageSlot &slot, void *dst, size_t bytes)
 
 } // namespace covest
 
-// Everything a grid handle holds besides its identity: called by covest_grid_create and covest_grid_reset.  Device
-// memory is only ever grown, and the small inputs (axes, threshold table, the queue's counter) go up in ONE copy:
-// optimize_grid re-configures a handle every iteration (21 times 0.2 ms of allocations and copies otherwise).
-static int grid_configure(covest_grid *g, int32_t n_axes, const double *const *axes, const int64_t *axis_len,
-                          int64_t flat_begin, int64_t flat_end, const char *who)
+namespace {
+
+// The arguments of covest_grid_create / covest_grid_reset: the grid's size, the axes' values together, and the block's
+// end (a negative flat_end means the whole grid).
+int check_grid_args(const covest_model *m, int32_t n_axes, const double *const *axes, const int64_t *axis_len, int64_t flat_begin,
+                    int64_t *flat_end, const char *who, int64_t *total_out, int64_t *n_values_out)
 {
-    covest_model *m = g->model;
     if (!axes || !axis_len)
         return fail(COVEST_E_INVALID, std::string(who) + ": null argument");
     if (n_axes != m->n_par)
@@ -65,10 +65,138 @@ static int grid_configure(covest_grid *g, int32_t n_axes, const double *const *a
         total *= axis_len[d];
         n_values += axis_len[d];
     }
-    if (flat_end < 0)
-        flat_end = total;
-    if (flat_begin < 0 || flat_begin > flat_end || flat_end > total)
+    if (*flat_end < 0)
+        *flat_end = total;
+    if (flat_begin < 0 || flat_begin > *flat_end || *flat_end > total)
         return fail(COVEST_E_INVALID, std::string(who) + ": bad flat index range");
+    *total_out = total;
+    *n_values_out = n_values;
+    return COVEST_OK;
+}
+
+// The arena of a grid of n points whose axes hold n_values doubles and whose threshold table holds nq entries, as byte
+// offsets: [queue counter (8 B, always at the start: its place does not move from grid to grid) | axes | t_table],
+// staged and uploaded together, then the outputs.
+struct GridArena {
+    size_t ctl, axes, table;
+    size_t staged_bytes; // the three above
+    size_t ll, idx, word, partial_val, partial_idx, result, bytes;
+    GridArena(int64_t n_values, int64_t nq, int64_t n)
+    {
+        const size_t n_pts = (size_t)(n > 0 ? n : 1);
+        ctl = 0;
+        axes = 8;
+        table = axes + (size_t)n_values * sizeof(double);
+        staged_bytes = (table + (size_t)nq * sizeof(int32_t) + 7) / 8 * 8;
+        ll = staged_bytes;
+        idx = ll + n_pts * sizeof(double);
+        word = idx + n_pts * sizeof(int64_t);
+        partial_val = word + n_pts * sizeof(unsigned long long);
+        partial_idx = partial_val + kArgminBlocks * sizeof(double);
+        result = partial_idx + kArgminBlocks * sizeof(int64_t);
+        bytes = result + sizeof(ArgminResult);
+    }
+};
+
+// Grows the arena, stages [counter | axes | table] and sends them on their way.  *inputs: where the kernels read the
+// axes and the table -- the arena, or the staging memory itself:
+// A SMALL grid of a handle that is re-configured (optimize_grid's: a few thousand points, a kilobyte of axes and
+// threshold_o) reads its axes and the table WHERE THEY ARE STAGED -- page-locked host memory mapped into the
+// device's address space: every workgroup reads a handful of values, and the copy engine's start-up (11 us by
+// the trace of a search, a sixth of an iteration) is not paid.  The queue counter behind the axes is device
+// memory all the same (atomics): cleared by a memset on the stream.  Large grids -- every point of 10^6 reads
+// its axes -- keep the copy.
+int stage_inputs(covest_grid *g, const GridArena &a, int32_t n_axes, const double *const *axes, const int64_t *axis_len,
+                 const std::vector<int32_t> &table, int64_t n, char **inputs)
+{
+    const void *arena_before = g->arena.ptr;
+    const bool counter_clean = g->counter_clean; // (the queue counter is 0: set by grid_configure, kept by every arg-min launch)
+    HIP_TRY(g->arena.reserve(a.bytes));
+    char *base = g->arena.as<char>();
+    StageSlot slot;
+    const int src = grid_stage_begin(g, a.staged_bytes, slot);
+    if (src != COVEST_OK)
+        return src;
+    char *stage = slot.ptr;
+    std::memset(stage, 0, a.staged_bytes);
+    double *sa = reinterpret_cast<double *>(stage + a.axes);
+    for (int d = 0; d < n_axes; ++d) {
+        std::copy(axes[d], axes[d] + axis_len[d], sa);
+        sa += axis_len[d];
+    }
+    if (!table.empty())
+        std::memcpy(stage + a.table, table.data(), table.size() * sizeof(int32_t));
+    if (g->async_uploads && n <= kArgminSmall) { // in place
+        *inputs = stage;
+        // (the counter's place depends on the axes' lengths: cleared unless it is where a clean one was left)
+        if (!(counter_clean && g->arena.ptr == arena_before && g->sub_ctl.ptr == base + a.ctl)) {
+            HIP_TRY(hipMemsetAsync(base + a.ctl, 0, 8, nullptr));
+            g->upload_pending = true;
+        }
+        return COVEST_OK;
+    }
+    *inputs = base;
+    return grid_stage_commit(g, slot, base, a.staged_bytes);
+}
+
+// The handle's views into the arena (axes and table: into `inputs`, see stage_inputs) and its PointSource.
+void bind_views(covest_grid *g, const GridArena &a, char *inputs, int32_t n_axes, const int64_t *axis_len, int64_t flat_begin)
+{
+    char *base = g->arena.as<char>();
+    g->axes.ptr = inputs + a.axes;
+    g->sub_ctl.ptr = base + a.ctl;
+    g->t_table.ptr = inputs + a.table;
+    g->ll.ptr = base + a.ll;
+    g->sub_index.ptr = base + a.idx;
+    g->sub_word.ptr = base + a.word;
+    g->partial_val.ptr = base + a.partial_val;
+    g->partial_idx.ptr = base + a.partial_idx;
+    g->result.ptr = base + a.result;
+    PointSource &src = g->src;
+    src = PointSource{};
+    src.is_grid = 1;
+    src.flat_begin = flat_begin;
+    int64_t off = 0;
+    for (int d = 0; d < kMaxParams; ++d) {
+        g->len[d] = src.len[d] = d < n_axes ? axis_len[d] : 1;
+        src.axis[d] = d < n_axes ? g->axes.as<double>() + off : nullptr;
+        if (d < n_axes)
+            off += axis_len[d];
+    }
+    if (g->model->n_par == 5)
+        src.t_table = g->t_table.as<int32_t>();
+}
+
+// Sums of (T - 1) of a repeats grid: over the flat indices [flat_begin, flat_end) -- whole (c, e) rows plus two ragged
+// ends -- and over the nq weight vectors.
+struct TMinus1Sums {
+    double block, q;
+};
+
+TMinus1Sums sum_t_minus_1(const std::vector<int32_t> &table, int64_t nq, int64_t flat_begin, int64_t flat_end)
+{
+    std::vector<double> prefix((size_t)nq + 1, 0.0);
+    for (int64_t i = 0; i < nq; ++i)
+        prefix[(size_t)i + 1] = prefix[(size_t)i] + (double)(table[(size_t)i] > 1 ? table[(size_t)i] - 1 : 0);
+    auto upto = [&](int64_t flat) { // sum over flat indices [0, flat)
+        return (double)(flat / nq) * prefix[(size_t)nq] + prefix[(size_t)(flat % nq)];
+    };
+    return {upto(flat_end) - upto(flat_begin), prefix[(size_t)nq]};
+}
+
+} // namespace
+
+// Everything a grid handle holds besides its identity: called by covest_grid_create and covest_grid_reset.  Device
+// memory is only ever grown, and the small inputs (axes, threshold table, the queue's counter) go up in ONE copy:
+// optimize_grid re-configures a handle every iteration (21 times 0.2 ms of allocations and copies otherwise).
+static int grid_configure(covest_grid *g, int32_t n_axes, const double *const *axes, const int64_t *axis_len,
+                          int64_t flat_begin, int64_t flat_end, const char *who)
+{
+    covest_model *m = g->model;
+    int64_t total = 0, n_values = 0;
+    const int arc = check_grid_args(m, n_axes, axes, axis_len, flat_begin, &flat_end, who, &total, &n_values);
+    if (arc != COVEST_OK)
+        return arc;
     g->configured = false; // (set again at the very end: a failure below leaves views into a freed arena behind)
     g->flat_begin = flat_begin;
     g->flat_end = flat_end;
@@ -85,95 +213,21 @@ static int grid_configure(covest_grid *g, int32_t n_axes, const double *const *a
     if (nq)
         threshold_table(m, axes[2], n1, axes[3], n2, axes[4], n3, table.data());
 
-    // arena layout: [queue counter (8 B, always at the start: its place does not move from grid to grid) | axes | t_table]
-    // uploaded together, then the outputs
-    auto up8 = [](size_t v) { return (v + 7) / 8 * 8; };
-    const size_t o_ctl = 0, o_axes = 8, o_table = o_axes + (size_t)n_values * sizeof(double);
-    const size_t o_ll = up8(o_table + (size_t)nq * sizeof(int32_t)), n_pts = (size_t)(n > 0 ? n : 1);
-    const size_t o_idx = o_ll + n_pts * sizeof(double), o_word = o_idx + n_pts * sizeof(int64_t);
-    const size_t o_pv = o_word + n_pts * sizeof(unsigned long long), o_pi = o_pv + kArgminBlocks * sizeof(double);
-    const size_t o_res = o_pi + kArgminBlocks * sizeof(int64_t), bytes = o_res + sizeof(ArgminResult);
-    const void *arena_before = g->arena.ptr;
-    const bool counter_clean = g->counter_clean; // (the queue counter is 0: set below, kept by every arg-min launch)
-    HIP_TRY(g->arena.reserve(bytes));
-    char *base = g->arena.as<char>();
-    char *host_base = nullptr;
-    bool in_place = false;
-    {
-        StageSlot slot;
-        const int src = grid_stage_begin(g, o_ll, slot);
-        if (src != COVEST_OK)
-            return src;
-        char *stage = slot.ptr;
-        std::memset(stage, 0, o_ll);
-        double *sa = reinterpret_cast<double *>(stage + o_axes);
-        for (int d = 0; d < n_axes; ++d) {
-            g->len[d] = axis_len[d];
-            std::copy(axes[d], axes[d] + axis_len[d], sa);
-            sa += axis_len[d];
-        }
-        for (int d = n_axes; d < kMaxParams; ++d)
-            g->len[d] = 1;
-        if (nq)
-            std::memcpy(stage + o_table, table.data(), (size_t)nq * sizeof(int32_t));
-        // A SMALL grid of a handle that is re-configured (optimize_grid's: a few thousand points, a kilobyte of axes and
-        // threshold_o) reads its axes and the table WHERE THEY ARE STAGED -- page-locked host memory mapped into the
-        // device's address space: every workgroup reads a handful of values, and the copy engine's start-up (11 us by
-        // the trace of a search, a sixth of an iteration) is not paid.  The queue counter behind the axes is device
-        // memory all the same (atomics): cleared by a memset on the stream.  Large grids -- every point of 10^6 reads
-        // its axes -- keep the copy.
-        in_place = g->async_uploads && n <= kArgminSmall;
-        if (in_place) {
-            host_base = stage;
-            // (the counter's place depends on the axes' lengths: cleared unless it is where a clean one was left)
-            if (!(counter_clean && g->arena.ptr == arena_before && g->sub_ctl.ptr == base + o_ctl)) {
-                HIP_TRY(hipMemsetAsync(base + o_ctl, 0, 8, nullptr));
-                g->upload_pending = true;
-            }
-        } else {
-            const int crc = grid_stage_commit(g, slot, base, o_ll);
-            if (crc != COVEST_OK)
-                return crc;
-        }
-    }
-    g->axes.ptr = (in_place ? host_base : base) + o_axes;
-    g->sub_ctl.ptr = base + o_ctl;
-    g->t_table.ptr = (in_place ? host_base : base) + o_table;
-    g->ll.ptr = base + o_ll;
-    g->sub_index.ptr = base + o_idx;
-    g->sub_word.ptr = base + o_word;
-    g->partial_val.ptr = base + o_pv;
-    g->partial_idx.ptr = base + o_pi;
-    g->result.ptr = base + o_res;
-    PointSource &src = g->src;
-    src = PointSource{};
-    src.is_grid = 1;
-    src.flat_begin = flat_begin;
-    {
-        int64_t off = 0;
-        for (int d = 0; d < kMaxParams; ++d) {
-            src.len[d] = d < n_axes ? axis_len[d] : 1;
-            src.axis[d] = d < n_axes ? g->axes.as<double>() + off : nullptr;
-            if (d < n_axes)
-                off += axis_len[d];
-        }
-    }
+    const GridArena arena(n_values, nq, n);
+    char *inputs = nullptr;
+    const int src = stage_inputs(g, arena, n_axes, axes, axis_len, table, n, &inputs);
+    if (src != COVEST_OK)
+        return src;
+    bind_views(g, arena, inputs, n_axes, axis_len, flat_begin);
 
     // the block's sum of (T - 1), and the K-factored plan
     g->sum_t_minus_1 = (double)n; // basic: T = 2 everywhere
     g->q_sum_t_minus_1 = 0.0;
     g->has_plan = false;
     if (m->n_par == 5) {
-        src.t_table = g->t_table.as<int32_t>();
-        // sum of (T-1) over flat indices [begin, end): whole (c,e) rows plus two ragged ends
-        std::vector<double> prefix((size_t)nq + 1, 0.0);
-        for (int64_t i = 0; i < nq; ++i)
-            prefix[(size_t)i + 1] = prefix[(size_t)i] + (double)(table[(size_t)i] > 1 ? table[(size_t)i] - 1 : 0);
-        auto upto = [&](int64_t flat) { // sum over flat indices [0, flat)
-            return (double)(flat / nq) * prefix[(size_t)nq] + prefix[(size_t)(flat % nq)];
-        };
-        g->sum_t_minus_1 = upto(flat_end) - upto(flat_begin);
-        g->q_sum_t_minus_1 = prefix[(size_t)nq];
+        const TMinus1Sums sums = sum_t_minus_1(table, nq, flat_begin, flat_end);
+        g->sum_t_minus_1 = sums.block;
+        g->q_sum_t_minus_1 = sums.q;
         const int prc = build_factored_plan(g, axes, axis_len, table);
         if (prc != COVEST_OK)
             return prc;
@@ -306,6 +360,78 @@ int covest_grid_kernel_ms(covest_grid *g, double *total_ms, int64_t *launches)
 
 int64_t covest_grid_size(const covest_grid *g) { return g ? g->flat_end - g->flat_begin : COVEST_E_INVALID; }
 
+// The optional hipEvent bracket around the likelihood kernel (covest_grid_profile): takes the handle's next pair of
+// events, records the first on the stream and hands back the second for the caller to record behind the launch
+// (nullptr: not profiling).
+static int bracket_begin(covest_grid *g, hipStream_t st, hipEvent_t *end)
+{
+    *end = nullptr;
+    if (!g->profiling)
+        return COVEST_OK;
+    if (g->ev_used == g->ev_begin.size()) {
+        hipEvent_t a, b;
+        HIP_TRY(hipEventCreate(&a));
+        HIP_TRY(hipEventCreate(&b));
+        g->ev_begin.push_back(a);
+        g->ev_end.push_back(b);
+    }
+    hipEvent_t begin = g->ev_begin[g->ev_used];
+    *end = g->ev_end[g->ev_used];
+    g->ev_used++;
+    HIP_TRY(hipEventRecord(begin, st));
+    return COVEST_OK;
+}
+
+#ifdef COVEST_DIAG
+// Diagnostic builds only (env COVEST_DIAG_QUEUE): how many points the recurrence kernel handed back for the strict
+// evaluation, how long the row ranges they name are, and their threshold_o.
+static int report_queue(covest_grid *g, hipStream_t st, int64_t n)
+{
+    if (!std::getenv("COVEST_DIAG_QUEUE"))
+        return COVEST_OK;
+    unsigned queued = 0;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(&queued, g->sub_ctl.ptr, sizeof queued, hipMemcpyDeviceToHost));
+    std::fprintf(stderr, "covest_grid_eval: %u of %lld points handed back\n", queued, (long long)n);
+    if (queued == 0)
+        return COVEST_OK;
+    std::vector<unsigned long long> words(queued); // the row ranges named: how long they are
+    HIP_TRY(hipMemcpy(words.data(), g->sub_word.ptr, (size_t)queued * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    double sum = 0;
+    long long mx = 0, mn = 1 << 30, first_sum = 0;
+    for (unsigned long long w : words) {
+        const long long unit = sub_units16(w) ? 16 : 1;
+        const long long len = ((long long)sub_last(w) - (long long)sub_first(w) + 1) * unit;
+        sum += (double)len;
+        mx = std::max(mx, len);
+        mn = std::min(mn, len);
+        first_sum += (long long)sub_first(w) * unit;
+    }
+    std::fprintf(stderr, "covest_grid_eval: rows named per point: min %lld mean %.1f max %lld; mean first row %.1f\n", mn,
+                 sum / queued, mx, (double)first_sum / queued);
+    if (!g->src.t_table)
+        return COVEST_OK;
+    const int64_t n_q = g->src.len[2] * g->src.len[3] * g->src.len[4]; // the queued points' threshold_o
+    std::vector<int32_t> tt((size_t)n_q);
+    std::vector<int64_t> idx(queued);
+    HIP_TRY(hipMemcpy(tt.data(), g->src.t_table, (size_t)n_q * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(idx.data(), g->sub_index.ptr, (size_t)queued * sizeof(int64_t), hipMemcpyDeviceToHost));
+    long long tmin = 1 << 30, tmax = 0;
+    double tsum = 0;
+    long long hist[6] = {0, 0, 0, 0, 0, 0}; // T <= 16, 32, 64, 128, 256, more
+    for (int64_t i : idx) {
+        const long long T = tt[(size_t)((g->src.flat_begin + i) % n_q)];
+        tmin = std::min(tmin, T);
+        tmax = std::max(tmax, T);
+        tsum += (double)T;
+        hist[T <= 16 ? 0 : T <= 32 ? 1 : T <= 64 ? 2 : T <= 128 ? 3 : T <= 256 ? 4 : 5]++;
+    }
+    std::fprintf(stderr, "covest_grid_eval: threshold_o of the queued points: min %lld mean %.1f max %lld; <=16 %lld <=32 %lld <=64 %lld <=128 %lld <=256 %lld more %lld\n",
+                 tmin, tsum / queued, tmax, hist[0], hist[1], hist[2], hist[3], hist[4], hist[5]);
+    return COVEST_OK;
+}
+#endif
+
 static int grid_eval(covest_grid *g, int32_t kernel, void *stream, bool scan, double scan_start)
 {
     if (!g)
@@ -326,67 +452,19 @@ static int grid_eval(covest_grid *g, int32_t kernel, void *stream, bool scan, do
     const int64_t n = g->flat_end - g->flat_begin;
     if (g->upload_pending && st != nullptr && g->upload_ev)
         HIP_TRY(hipStreamWaitEvent(st, g->upload_ev, 0)); // (covest_grid_reset's copies run on the null stream)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (g->profiling) {
-        if (g->ev_used == g->ev_begin.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
-            g->ev_begin.push_back(a);
-            g->ev_end.push_back(b);
-        }
-        e0 = g->ev_begin[g->ev_used];
-        e1 = g->ev_end[g->ev_used];
-        g->ev_used++;
-        HIP_TRY(hipEventRecord(e0, st));
-    }
+    hipEvent_t bracket_end = nullptr;
+    rc = bracket_begin(g, st, &bracket_end);
+    if (rc != COVEST_OK)
+        return rc;
     HIP_TRY(launch_ll(m, kern, g->src, n, g->ll.as<double>(), sub_list_of(m, g->has_plan ? g->t_max : 2, g->sub_index.ptr, g->sub_word.ptr, g->sub_ctl.ptr), st,
                       &g->last_kernel, g));
     g->last_kernel_id = kern;
-    if (e1)
-        HIP_TRY(hipEventRecord(e1, st));
-#ifdef COVEST_DIAG // diagnostic builds only: how many points the recurrence kernel handed back for the strict evaluation
-    if (std::getenv("COVEST_DIAG_QUEUE")) {
-        unsigned queued = 0;
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(&queued, g->sub_ctl.ptr, sizeof queued, hipMemcpyDeviceToHost));
-        std::fprintf(stderr, "covest_grid_eval: %u of %lld points handed back\n", queued, (long long)n);
-        if (queued > 0) { // the row ranges named: how long they are
-            std::vector<unsigned long long> words(queued);
-            HIP_TRY(hipMemcpy(words.data(), g->sub_word.ptr, (size_t)queued * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            double sum = 0;
-            long long mx = 0, mn = 1 << 30, first_sum = 0;
-            for (unsigned long long w : words) {
-                const long long unit = sub_units16(w) ? 16 : 1;
-                const long long len = ((long long)sub_last(w) - (long long)sub_first(w) + 1) * unit;
-                sum += (double)len;
-                mx = std::max(mx, len);
-                mn = std::min(mn, len);
-                first_sum += (long long)sub_first(w) * unit;
-            }
-            std::fprintf(stderr, "covest_grid_eval: rows named per point: min %lld mean %.1f max %lld; mean first row %.1f\n", mn,
-                         sum / queued, mx, (double)first_sum / queued);
-            if (g->src.t_table) { // the queued points' threshold_o
-                const int64_t n_q = g->src.len[2] * g->src.len[3] * g->src.len[4];
-                std::vector<int32_t> tt((size_t)n_q);
-                std::vector<int64_t> idx(queued);
-                HIP_TRY(hipMemcpy(tt.data(), g->src.t_table, (size_t)n_q * sizeof(int32_t), hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(idx.data(), g->sub_index.ptr, (size_t)queued * sizeof(int64_t), hipMemcpyDeviceToHost));
-                long long tmin = 1 << 30, tmax = 0;
-                double tsum = 0;
-                long long hist[6] = {0, 0, 0, 0, 0, 0}; // T <= 16, 32, 64, 128, 256, more
-                for (int64_t i : idx) {
-                    const long long T = tt[(size_t)((g->src.flat_begin + i) % n_q)];
-                    tmin = std::min(tmin, T);
-                    tmax = std::max(tmax, T);
-                    tsum += (double)T;
-                    hist[T <= 16 ? 0 : T <= 32 ? 1 : T <= 64 ? 2 : T <= 128 ? 3 : T <= 256 ? 4 : 5]++;
-                }
-                std::fprintf(stderr, "covest_grid_eval: threshold_o of the queued points: min %lld mean %.1f max %lld; <=16 %lld <=32 %lld <=64 %lld <=128 %lld <=256 %lld more %lld\n",
-                             tmin, tsum / queued, tmax, hist[0], hist[1], hist[2], hist[3], hist[4], hist[5]);
-            }
-        }
-    }
+    if (bracket_end)
+        HIP_TRY(hipEventRecord(bracket_end, st));
+#ifdef COVEST_DIAG
+    rc = report_queue(g, st, n);
+    if (rc != COVEST_OK)
+        return rc;
 #endif
     if (!g->result_host) { // (page-locked, mapped: argmin_stage2 stores the winner there itself)
         static_assert(sizeof(ArgminResult) <= 64 && 64 + sizeof(ScanRecords) <= kPinnedBlockBytes, "pinned block");
@@ -534,7 +612,6 @@ int covest_grid_ll_host(covest_grid *g, double *out_ll)
     return COVEST_OK;
 }
 
-
 int64_t covest_grid_diag(covest_grid *g, int64_t *out, int64_t n)
 {
     if (!g || !g->has_plan || !g->plan.diag)
@@ -582,6 +659,5 @@ int covest_grid_work(const covest_grid *g, double *pmf_terms, double *flops, con
         *kernel = g->last_kernel;
     return COVEST_OK;
 }
-
 
 } // extern "C"

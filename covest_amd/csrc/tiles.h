@@ -1,5 +1,6 @@
 // tiles.h -- the tile table of the pmf recurrence (see streams.h), shared by the
-// host builder (tiles_host.cpp: build_tiles) and the fast kernels.
+// host builder (tiles_host.cpp: build_tiles) and the fast kernels.  The table's layout is defined HERE, once:
+// tile_view_from, tile_arrays_dbl, tile_dbl_count, tile_int_count.  The host builder fills its staging block through them.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -85,8 +86,11 @@ inline __host__ __device__ int64_t tile_arrays_dbl(int32_t nt, int32_t ni)
     return (n + 7) / 8 * 8;
 }
 inline __host__ __device__ int64_t tile_dbl_count(int32_t nt, int32_t ni) { return tile_arrays_dbl(nt, ni) + 8 * (int64_t)nt; }
+// int32s of the raw int32 buffer, which follows the doubles in the one block the host uploads
+inline __host__ __device__ int64_t tile_int_count(int32_t nt, int32_t ni) { return 4 * (int64_t)nt + 3 * (int64_t)ni + (int64_t)nt * kTileBins; }
 
-// The layout of tiles_host.cpp: build_tiles.
+// The layout, defined here and nowhere else: tiles_host.cpp builds this view over its staging block and fills the
+// arrays by name.
 inline __host__ __device__ TileView tile_view_from(int32_t nt, int32_t ni, const double *dbl, const int32_t *ints)
 {
     TileView tv;

@@ -1,37 +1,16 @@
 // plan_bytes.cpp -- K-factored's planner (plan_factored.cpp) without a GPU: every byte it uploads and every field of every
 // FactoredPlan it fills, over dense grids (shared and plain order, 1 to 4 passes, q-blocks, long parts, tails; each built
 // twice on one handle) and point lists (list modes 1 and 2, in place and copied), written to a file that two builds of the
-// planner must produce identically.  HIP and the staging of host.h are replaced by malloc and memcpy below; clamp_one
-// and clamp_for by look-alikes (pure functions of the same arguments).  tools/plan_bytes.sh builds it against a
-// revision's planner and the tree's and compares.  A third argument N times the plan of dense case N instead.
-#include "host.h"
+// planner must produce identically.  HIP and the staging of host.h are replaced by malloc and memcpy, clamp_one and clamp_for
+// by look-alikes (pure functions of the same arguments): tools/host_standins.h, shared with tools/tiles_bytes.cpp.
+// tools/plan_bytes.sh builds it against a revision's planner and the tree's and compares.  A third argument N times the plan
+// of dense case N instead.
+#define STANDIN_GRID_STAGE
+#include "host_standins.h"
 #include <random>
 #include <chrono>
-static std::vector<std::pair<char*, size_t>> g_allocs;
-extern "C" {
-hipError_t hipDeviceSynchronize() { return hipSuccess; }
-hipError_t hipFree(void *p) { return hipSuccess; }
-hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
-hipError_t hipSetDevice(int) { return hipSuccess; }
-hipError_t hipHostFree(void *p) { return hipSuccess; }
-hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = calloc(1, n); return hipSuccess; }
-static bool g_timing; hipError_t hipMalloc(void **p, size_t n) { *p = calloc(1, n); if (!g_timing) g_allocs.push_back({(char*)*p, n}); return hipSuccess; }
-hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
-hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
-}
 namespace covest {
-int set_error(int code, const std::string &msg) { fprintf(stderr, "error %d %s\n", code, msg.c_str()); return code; }
-int fail_hip(hipError_t e, const char *w) { fprintf(stderr, "hip error %s\n", w); return -1; }
-bool dev_cache_take(size_t, void **, size_t *, int *) { return false; }
-bool dev_cache_give(void *, size_t, int) { return true; }
-DeviceIdleScope::DeviceIdleScope() {}
-DeviceIdleScope::~DeviceIdleScope() {}
-bool DeviceIdleScope::active() { return true; }
-double clamp_one(const DevModel &dm, int d, double v) { return std::min(std::max(v, dm.lo[d]), dm.hi[d]); }
 double clamp_for(const covest_model *m, int t_max) { return (m->dm.n_err + t_max) * 7e-317; }
-static std::vector<char> g_stage;
-int grid_stage_begin(covest_grid *, size_t bytes, StageSlot &slot) { if (g_stage.size() < bytes || !g_timing) g_stage.assign(bytes, 0x5a); slot.ptr = g_stage.data(); return 0; }
-int grid_stage_commit(covest_grid *, StageSlot &slot, void *dst, size_t bytes) { memcpy(dst, slot.ptr, bytes); return 0; }
 }
 static FILE *out;
 static const char *g_base; static size_t g_cap;
@@ -54,7 +33,6 @@ static void dump_bytes(const char *tag, const void *p, size_t n)
     fprintf(out, "%s %zu bytes fnv %016llx\n", tag, n, h);
     fwrite(p, 1, n, out); fputc('\n', out);
 }
-static size_t alloc_size(const void *p) { for (auto &a : g_allocs) if (a.first == p) return a.second; return 0; }
 int main(int argc, char **argv)
 {
     out = fopen(argv[1], "wb");
