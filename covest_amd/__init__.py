@@ -10,4 +10,4 @@ from .hist_steps import (load_histogram, save_histogram, process_histogram, samp
                          compute_coverage_apx)
 from .report import print_output  # noqa: F401,E402
 from .profile import profile_negll, likelihood_interval, coverage_interval  # noqa: F401,E402
-from .information import observed_information, wald_intervals, genome_size_se  # noqa: F401,E402
+from .information import observed_information, sandwich_covariance, wald_intervals, genome_size_se  # noqa: F401,E402

@@ -23,6 +23,7 @@ EXPORTS = (
     "covest_abi_version", "covest_device_count", "covest_last_error",
     "covest_model_create", "covest_model_destroy", "covest_model_param_count",
     "covest_model_bins_evaluated", "covest_threshold_o", "covest_eval_points", "covest_eval_points_grad", "covest_eval_points_hess",
+    "covest_eval_points_opg",
     "covest_probabilities", "covest_reference_overflow", "covest_grid_create", "covest_grid_reset", "covest_grid_destroy", "covest_grid_size",
     "covest_grid_eval", "covest_grid_eval_scan", "covest_grid_scan", "covest_grid_argmin", "covest_grid_axis_min", "covest_grid_argmin_pair_device",
     "covest_grid_ll_device",
@@ -125,6 +126,8 @@ def lib():
     L.covest_eval_points_grad.argtypes = [vp, i64, dp, dp, dp]
     L.covest_eval_points_hess.restype = ctypes.c_int
     L.covest_eval_points_hess.argtypes = [vp, i64, dp, dp, dp, dp]
+    L.covest_eval_points_opg.restype = ctypes.c_int
+    L.covest_eval_points_opg.argtypes = [vp, i64, dp, dp, dp, dp]
     L.covest_reference_overflow.restype = ctypes.c_int
     L.covest_reference_overflow.argtypes = [vp, i64, dp, ctypes.POINTER(ctypes.c_uint8)]
     L.covest_probabilities.restype = ctypes.c_int

@@ -596,12 +596,13 @@ static int eval_points_list(covest_model *m, int64_t n, const double *params, do
     return rc != COVEST_OK ? rc : fix_points_host(m, n, params, t, out_ll, words);
 }
 
-// covest_eval_points_grad (order 1) and covest_eval_points_hess (order 2): the device leaves values | gradients |
-// Hessians (the last block only for order 2) in one buffer; `who` names the entry point in the messages.
+// covest_eval_points_grad (order 1), covest_eval_points_hess (order 2) and covest_eval_points_opg (order kDerivOpg): the
+// device leaves values | gradients | matrices (Hessians or score outer products; no last block for order 1) in one
+// buffer; `who` names the entry point in the messages.
 static int eval_points_deriv(covest_model *m, int order, int64_t n, const double *params, double *out_ll, double *out_grad,
                              double *out_hess, const char *who)
 {
-    if (!m || n < 0 || (n > 0 && (!params || !out_ll || !out_grad || (order == 2 && !out_hess))))
+    if (!m || n < 0 || (n > 0 && (!params || !out_ll || !out_grad || (order != 1 && !out_hess))))
         return fail(COVEST_E_INVALID, std::string(who) + ": bad argument");
     if (n == 0)
         return COVEST_OK;
@@ -612,7 +613,7 @@ static int eval_points_deriv(covest_model *m, int order, int64_t n, const double
         return rc;
     const int P = m->n_par;
     StagedPoints sp;
-    rc = stage_points(m, n, params, (size_t)n * (1 + P + (order == 2 ? P * P : 0)) * sizeof(double), sp);
+    rc = stage_points(m, n, params, (size_t)n * (1 + P + (order != 1 ? P * P : 0)) * sizeof(double), sp);
     if (rc != COVEST_OK)
         return rc;
     HIP_TRY(m->ws_partial.reserve(ll_deriv_partial_bytes(m->dm, order, n)));
@@ -623,7 +624,7 @@ static int eval_points_deriv(covest_model *m, int order, int64_t n, const double
     rc = read_result(sp, out_ll, 0, (size_t)n);
     if (rc == COVEST_OK)
         rc = read_result(sp, out_grad, (size_t)n, (size_t)n * P);
-    if (rc == COVEST_OK && order == 2)
+    if (rc == COVEST_OK && order != 1)
         rc = read_result(sp, out_hess, (size_t)n * (1 + P), (size_t)n * P * P);
     return rc;
 }
@@ -679,6 +680,12 @@ int covest_eval_points_hess(covest_model *m, int64_t n, const double *params, do
                             double *out_hess)
 {
     return eval_points_deriv(m, 2, n, params, out_ll, out_grad, out_hess, "covest_eval_points_hess");
+}
+
+int covest_eval_points_opg(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad,
+                           double *out_opg)
+{
+    return eval_points_deriv(m, kDerivOpg, n, params, out_ll, out_grad, out_opg, "covest_eval_points_opg");
 }
 
 int64_t covest_model_launch_record(covest_model *m, char *buf, int64_t cap)

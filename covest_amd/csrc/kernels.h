@@ -137,13 +137,16 @@ bool axis_min_plan(const int64_t *len, int n_axes, uint32_t keep_mask, int64_t f
 hipError_t launch_axis_min(const AxisMinPlan &p, const double *ll, double *partial_val, int64_t *partial_idx, double *out_val,
                            int64_t *out_idx, hipStream_t stream);
 
-// ---- K-grad and K-hess (ll_deriv.hip): value, analytic gradient (order 1) and closed-form Hessian (order 2) ----
+// ---- K-grad, K-hess and K-opg (ll_deriv.hip): value, analytic gradient (order 1), closed-form Hessian (order 2), or the
+// outer product of the per-k-mer scores beside order 1's value and gradient (order kDerivOpg: a mode, not a derivative) ----
 // One workgroup per (point, segment of ll_deriv_segments(m) key segments) leaves compensated partial sums in `partial`
 // (ll_deriv_partial_bytes(m, order, n) bytes): per segment 2 + 2P sums for order 1 (h log p, p, h d_k p / p, d_k p),
 // P (P + 1) more for order 2 (the two second-order sums of each pair k <= l), each a (hi, lo) pair, and one double behind
-// them.  A second launch adds a point's segments in ascending order and applies the tail terms.  out_ll[n],
-// out_grad[n][P], and for order 2 out_hess[n][P][P] (symmetric: the upper triangle computed, mirrored; not read for
-// order 1); src is a point list.  Two launches (per 16384 points); not entered in the launch record.
+// them; P (P + 1) / 2 more than order 1 for kDerivOpg (sum h (d_k p / p)(d_l p / p) of each pair).  A second launch adds
+// a point's segments in ascending order and applies the tail terms.  out_ll[n], out_grad[n][P], and for order 2 or
+// kDerivOpg out_hess[n][P][P], the Hessian or the outer product (symmetric: the upper triangle computed, mirrored; not
+// read for order 1); src is a point list.  Two launches (per 16384 points); not entered in the launch record.
+constexpr int kDerivOpg = 3;
 int ll_deriv_segments(const DevModel &m);
 size_t ll_deriv_partial_bytes(const DevModel &m, int order, int64_t n);
 hipError_t launch_ll_deriv(const DevModel &m, int order, const PointSource &src, int64_t n, double *partial, double *out_ll,

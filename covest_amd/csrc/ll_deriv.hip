@@ -1,6 +1,10 @@
 // ll_deriv.hip -- the derivative kernels, for gfx950.  ORDER 1 is K-grad: the log-likelihood of a point list AND its
-// analytic gradient.  ORDER 2 is K-hess: those two AND the Hessian in closed form.  One source, templated on the model
-// (P parameters) and on the order; everything second-order sits behind `if constexpr (ORDER == 2)`.
+// analytic gradient.  ORDER 2 is K-hess: those two AND the Hessian in closed form.  ORDER kDerivOpg (3; a mode, not a
+// third derivative) is K-opg: K-grad's walk, unchanged, AND the outer product of the per-k-mer scores,
+//     B_kl = sum_{h_j != 0} h_j r_k(j) r_l(j) + [tail != 0, sp < 1] tail S_k S_l / (1 - sp)^2,   r_k = d_k p_j / p_j,
+// S_k = sum_j d_k p_j: the meat of the sandwich covariance.  One source, templated on the model
+// (P parameters) and on the order; everything second-order sits behind `if constexpr (ORDER == 2)`, everything of the
+// outer product behind `if constexpr (ORDER == kDerivOpg)`.
 //
 // The function differentiated is what the kernels evaluate, piece by piece, at the point after fit_to_bounds
 // (clamp_point), with threshold_o held fixed, the reference's two roundings kept in the weights and given no derivative
@@ -18,7 +22,7 @@
 // one exp per (component, key), every lane owning keys; the value uses the same expressions.  But ONE WORKGROUP PER
 // (point, key segment) instead of one wave per point: keys are independent up to the final sums, so a segment of
 // kDerivSegKeys keys -- one key a lane, four waves -- leaves compensated partial sums, and ll_deriv_finish_kernel adds a
-// point's segments in ascending order, applies the tail terms and (ORDER 2) mirrors the upper triangle.  The segment
+// point's segments in ascending order, applies the tail terms and (ORDER 2, K-opg) mirrors the upper triangle.  The segment
 // size and every order of summation are a function of the model alone: a point's numbers do not depend on what else is
 // in the call.  The first-order arithmetic is the same expressions in both orders, so the two return the same value and
 // the same gradient.
@@ -39,17 +43,19 @@ constexpr int kDerivSegKeys = kDerivWaves * kWave; // one key a lane
 constexpr int64_t kDerivPointsPerLaunch = 16384;   // (gridDim.y)
 
 // The sums a segment leaves, each as a (hi, lo) pair, NP the parameter pairs (k <= l, row by row) of ORDER 2, none of
-// ORDER 1:
+// the others; NB the same pairs of K-opg, none of the others:
 //   0 sum h log p (finite terms), 1 sum p,
 //   kG + k   sum h d_k p / p,            kD + k   sum d_k p,
-//   kH + kl  sum h (d_k d_l p / p - d_k p d_l p / p^2),      kDD + kl  sum d_k d_l p;
+//   kH + kl  sum h (d_k d_l p / p - d_k p d_l p / p^2),      kDD + kl  sum d_k d_l p,
+//   kB + kl  sum h (d_k p / p)(d_l p / p);
 // behind them ONE double: the sum of the terms h log p that are not finite (-inf where p_j = 0, NaN), kept out of the
 // compensated sums they would poison.
 template <int P, int ORDER> struct DerivLayout {
-    static_assert(ORDER == 1 || ORDER == 2, "K-grad or K-hess");
+    static_assert(ORDER == 1 || ORDER == 2 || ORDER == kDerivOpg, "K-grad, K-hess or K-opg");
     static constexpr int kPairs = ORDER == 2 ? P * (P + 1) / 2 : 0;
-    static constexpr int kG = 2, kD = 2 + P, kH = 2 + 2 * P, kDD = 2 + 2 * P + kPairs;
-    static constexpr int kSums = 2 + 2 * P + 2 * kPairs;
+    static constexpr int kOuter = ORDER == kDerivOpg ? P * (P + 1) / 2 : 0;
+    static constexpr int kG = 2, kD = 2 + P, kH = 2 + 2 * P, kDD = 2 + 2 * P + kPairs, kB = 2 + 2 * P + 2 * kPairs;
+    static constexpr int kSums = 2 + 2 * P + 2 * kPairs + kOuter;
     static constexpr int kStride = 2 * kSums + 1;
     static_assert(kSums + 1 <= kWave, "the finishing kernel adds one quantity a thread");
 };
@@ -335,6 +341,17 @@ __global__ __launch_bounds__(kDerivWaves *kWave) void ll_deriv_kernel(const DevM
                         for (int l = k; l < P; ++l)
                             val[L::kH + pair_index(P, k, l)] = h * (p2[pair_index(P, k, l)] / p - r1[k] * r1[l]);
                 }
+                if constexpr (ORDER == kDerivOpg) {
+                    double r1[P]; // the score's factors d_k p / p
+#pragma unroll
+                    for (int d = 0; d < P; ++d)
+                        r1[d] = p1[d] / p;
+#pragma unroll
+                    for (int k = 0; k < P; ++k)
+#pragma unroll
+                        for (int l = k; l < P; ++l)
+                            val[L::kB + pair_index(P, k, l)] = h * r1[k] * r1[l];
+                }
             }
         }
     }
@@ -374,8 +391,9 @@ __global__ __launch_bounds__(kDerivWaves *kWave) void ll_deriv_kernel(const DevM
 // on = [tail != 0 and sp < 1]:  LL = sum h log p + on tail log(1 - sp);  threads 0 .. P - 1 form
 // d_k LL = sum h d_k p / p - on tail (sum d_k p) / (1 - sp), and (ORDER 2) threads 0 .. NP - 1 one pair (k <= l) each,
 // d_k d_l LL = sum h (d_k d_l p / p - d_k p d_l p / p^2) - on tail [sum d_k d_l p / (1 - sp) + (sum d_k p)(sum d_l p) / (1 - sp)^2],
-// written to H[k][l] and H[l][k] (out_hess is not read for ORDER 1).  A component, a row and a column whose parameter
-// the clamp moved are 0; where LL is not finite every entry is NaN.
+// written to H[k][l] and H[l][k] (out_hess is not read for ORDER 1).  K-opg has the same threads form
+// B_kl = sum h (d_k p / p)(d_l p / p) + on tail (sum d_k p)(sum d_l p) / (1 - sp)^2 and write it where ORDER 2 writes H.
+// A component, a row and a column whose parameter the clamp moved are 0; where LL is not finite every entry is NaN.
 template <int P, int ORDER>
 __global__ __launch_bounds__(kWave) void ll_deriv_finish_kernel(const DevModel m, const PointSource src, int n_seg,
                                                                 const double *__restrict__ partial, double *__restrict__ out_ll,
@@ -383,7 +401,7 @@ __global__ __launch_bounds__(kWave) void ll_deriv_finish_kernel(const DevModel m
 {
     using L = DerivLayout<P, ORDER>;
     constexpr int NQ = L::kSums, STRIDE = L::kStride;
-    constexpr int NT = ORDER == 2 ? L::kPairs : P; // threads with an entry to write
+    constexpr int NT = ORDER == 2 ? L::kPairs : ORDER == kDerivOpg ? L::kOuter : P; // threads with an entry to write
     __shared__ double tot[NQ + 1];
     const int64_t pt = blockIdx.x;
     const int q = threadIdx.x;
@@ -408,13 +426,13 @@ __global__ __launch_bounds__(kWave) void ll_deriv_finish_kernel(const DevModel m
         for (int d = 0; d < P; ++d)
             par[d] = raw[d];
         clamp_point<P>(m, par);
-        int k = 0, l = 0; // (ORDER 2) the pair this thread owns
+        int k = 0, l = 0; // (ORDER 2, K-opg) the pair this thread owns
         bool moved_k = false, moved_l = false, moved_q = false;
 #pragma unroll
         for (int a = 0; a < P; ++a) {
             if (a == q)
                 moved_q = par[a] != raw[a];
-            if constexpr (ORDER == 2) {
+            if constexpr (ORDER != 1) {
 #pragma unroll
                 for (int b = a; b < P; ++b)
                     if (pair_index(P, a, b) == q) {
@@ -429,6 +447,8 @@ __global__ __launch_bounds__(kWave) void ll_deriv_finish_kernel(const DevModel m
         double hkl = 0.0;
         if constexpr (ORDER == 2)
             hkl = tot[L::kH + q];
+        if constexpr (ORDER == kDerivOpg)
+            hkl = tot[L::kB + q];
         if (m.tail != 0.0) { // tail * log(1 - min(1, sp)), covest/models.py:103-105
             double sp = tot[1];
             if (!(sp < 1.0))
@@ -441,6 +461,10 @@ __global__ __launch_bounds__(kWave) void ll_deriv_finish_kernel(const DevModel m
                     const double inv = 1.0 / (1.0 - sp);
                     hkl -= m.tail * (tot[L::kDD + q] * inv + tot[L::kD + k] * tot[L::kD + l] * inv * inv);
                 }
+                if constexpr (ORDER == kDerivOpg) { // the tail as one more class: score -S_k / (1 - sp), tail times
+                    const double inv = 1.0 / (1.0 - sp);
+                    hkl += m.tail * (tot[L::kD + k] * tot[L::kD + l] * inv * inv);
+                }
             }
         }
         if (moved_q)
@@ -451,7 +475,7 @@ __global__ __launch_bounds__(kWave) void ll_deriv_finish_kernel(const DevModel m
             g = NAN;
             hkl = NAN;
         }
-        if constexpr (ORDER == 2) {
+        if constexpr (ORDER != 1) {
             out_hess[(pt * P + k) * P + l] = hkl;
             out_hess[(pt * P + l) * P + k] = hkl;
         }
@@ -483,8 +507,12 @@ int ll_deriv_segments(const DevModel &m)
 size_t ll_deriv_partial_bytes(const DevModel &m, int order, int64_t n)
 {
     const int64_t pts = n < kDerivPointsPerLaunch ? n : kDerivPointsPerLaunch;
-    const int stride = m.kind == 0 ? (order == 2 ? DerivLayout<2, 2>::kStride : DerivLayout<2, 1>::kStride)
-                                   : (order == 2 ? DerivLayout<5, 2>::kStride : DerivLayout<5, 1>::kStride);
+    const int stride = m.kind == 0 ? (order == 2           ? DerivLayout<2, 2>::kStride
+                                      : order == kDerivOpg ? DerivLayout<2, kDerivOpg>::kStride
+                                                           : DerivLayout<2, 1>::kStride)
+                                   : (order == 2           ? DerivLayout<5, 2>::kStride
+                                      : order == kDerivOpg ? DerivLayout<5, kDerivOpg>::kStride
+                                                           : DerivLayout<5, 1>::kStride);
     return (size_t)pts * (size_t)ll_deriv_segments(m) * (size_t)stride * sizeof(double);
 }
 
@@ -493,19 +521,19 @@ hipError_t launch_ll_deriv(const DevModel &m, int order, const PointSource &src,
 {
     if (n <= 0)
         return hipSuccess;
-    if (src.is_grid || (order != 1 && order != 2))
+    if (src.is_grid || (order != 1 && order != 2 && order != kDerivOpg))
         return hipErrorInvalidValue;
     const int n_seg = ll_deriv_segments(m);
     const int P = m.kind == 0 ? 2 : 5;
-    const auto launch = P == 2 ? (order == 1 ? launch_part<2, 1> : launch_part<2, 2>)
-                               : (order == 1 ? launch_part<5, 1> : launch_part<5, 2>);
+    const auto launch = P == 2 ? (order == 1 ? launch_part<2, 1> : order == 2 ? launch_part<2, 2> : launch_part<2, kDerivOpg>)
+                               : (order == 1 ? launch_part<5, 1> : order == 2 ? launch_part<5, 2> : launch_part<5, kDerivOpg>);
     for (int64_t first = 0; first < n; first += kDerivPointsPerLaunch) {
         const int64_t cnt = n - first < kDerivPointsPerLaunch ? n - first : kDerivPointsPerLaunch;
         PointSource part = src;
         part.params = src.params + first * P;
         part.t_list = src.t_list ? src.t_list + first : nullptr;
         launch(m, part, n_seg, cnt, partial, out_ll + first, out_grad + first * P,
-               order == 2 ? out_hess + first * P * P : nullptr, stream);
+               order != 1 ? out_hess + first * P * P : nullptr, stream);
     }
     return hipGetLastError();
 }

@@ -5,7 +5,12 @@ correlations and Wald intervals -- for every parameter and the genome size, with
 What these numbers are and are not (the caveat of DESIGN.md 6d, unchanged): the model treats the k-mer counts as
 independent and |LL| is 1e7..1e8 on real histograms, so the curvature is huge and the standard errors are very small.
 They are the MODEL's standard errors -- how sharply this likelihood singles out its optimum -- not a statement about
-how far the estimate is from the truth.  Nothing here corrects for that (no sandwich covariance).
+how far the estimate is from the truth.  sandwich_covariance corrects them for ONE way the model can be wrong: misfit
+of the mixture (the histogram does not follow the model's law), through the robust covariance A^-1 B A^-1 with B the
+centred outer product of the per-k-mer scores (covest_eval_points_opg).  It does NOT correct for the
+other: the unit is still one distinct k-mer counted as independent of the others, overlapping k-mers are not, and a
+histogram carries no information to correct that -- robust standard errors are still far too small as a statement about
+the truth.
 """
 import math
 
@@ -71,6 +76,53 @@ def observed_information(model, estimate, fix=None):
     return info
 
 
+def sandwich_covariance(model, estimate, fix=None, info=None):
+    """The robust (sandwich) covariance of `estimate`: V = A^-1 B_c A^-1 over observed_information's `free` set, with
+    A = -Hessian the observed information and B_c = B - g g^T / n the centred outer product of the per-k-mer scores,
+    B = model.loglikelihood_score_outer_points's matrix at the estimate, g the gradient that call returns and
+    n = sum h + tail the number of observations.  If the mixture is the true law of the abundances B_c ~ A and V ~ A^-1.
+    `info`: observed_information's dict for the same model, estimate and fix, computed here when None.
+
+    Returns that dict (a copy) extended with opg (B as returned, P x P, lists), robust_covariance (of the free block,
+    in the order of `free`), robust_standard_errors ({name: se or None}), se_ratio ({name: robust / model or None}) and
+    information_ratio (the eigenvalues of A^-1 B_c on the free block, ascending; all ~ 1 when the model fits).  Where
+    the sandwich cannot be formed -- no covariance to start from, or B not finite -- these are None and `reason` says
+    why; A^-1 comes from the Cholesky factor of the same block, nothing is regularised.  See the module's docstring
+    for what the sandwich does and does not correct."""
+    if info is None:
+        info = observed_information(model, estimate, fix)
+    out = dict(info)
+    names = list(out['params'])
+    P = len(names)
+    ll, grad, opg = model.loglikelihood_score_outer_points([out['estimate']])
+    B = np.asarray(opg, dtype=np.float64).reshape(P, P)
+    g = np.asarray(grad, dtype=np.float64).reshape(P)
+    out.update(opg=B.tolist(), robust_covariance=None, robust_standard_errors={n: None for n in names},
+               se_ratio={n: None for n in names}, information_ratio=None)
+    if out['covariance'] is None:
+        if out['reason'] is None:
+            out['reason'] = "no covariance of the model to build the sandwich on"
+        return out
+    free = list(out['free'])
+    if not (np.all(np.isfinite(B)) and np.all(np.isfinite(g))):
+        out['reason'] = "the outer product of the scores is not finite at this point"
+        return out
+    n_obs = float(sum(model.hist.values())) + float(model.tail)
+    A = np.asarray(out['hessian'], dtype=np.float64)[np.ix_(free, free)]
+    centred = B[np.ix_(free, free)] - np.outer(g[free], g[free]) / n_obs
+    inv_chol = np.linalg.solve(np.linalg.cholesky(A), np.eye(len(free)))
+    middle = inv_chol @ centred @ inv_chol.T  # L^-1 B_c L^-T: similar to A^-1 B_c, and symmetric
+    cov = inv_chol.T @ middle @ inv_chol
+    out['robust_covariance'] = cov.tolist()
+    out['information_ratio'] = [float(v) for v in np.linalg.eigvalsh(middle)]
+    for at, d in enumerate(free):
+        if cov[at, at] >= 0.0:
+            se = math.sqrt(cov[at, at])
+            out['robust_standard_errors'][names[d]] = se
+            out['se_ratio'][names[d]] = se / out['standard_errors'][names[d]]
+    return out
+
+
 def _z(level):
     if not (isinstance(level, (int, float)) and 0.0 < level < 1.0):
         raise ValueError("level must be inside (0, 1)")
@@ -78,13 +130,15 @@ def _z(level):
     return float(norm.ppf(0.5 + 0.5 * level))
 
 
-def wald_intervals(info, level=0.95):
+def wald_intervals(info, level=0.95, robust=False):
     """{name: (lo, hi) or None}: estimate +- z se with z the normal quantile of `level`, clipped to the model's bounds;
-    None where the parameter has no standard error.  The model's intervals (module docstring)."""
+    None where the parameter has no standard error.  The model's intervals (module docstring), or with `robust` those of
+    sandwich_covariance's robust_standard_errors (`info` is then its dict)."""
     z = _z(level)
+    errors = info['robust_standard_errors' if robust else 'standard_errors']
     out = {}
     for name, value, (lo, hi) in zip(info['params'], info['estimate'], info['bounds']):
-        se = info['standard_errors'][name]
+        se = errors[name]
         if se is None:
             out[name] = None
             continue
@@ -93,18 +147,18 @@ def wald_intervals(info, level=0.95):
     return out
 
 
-def genome_size_se(model, hist_orig, info, sample_factor=1, level=0.95):
+def genome_size_se(model, hist_orig, info, sample_factor=1, level=0.95, robust=False):
     """The delta method on G = sum_i i h_i / correct_c(c * sample_factor): G is proportional to 1 / c, so
     se_G = G se_c / c.  Returns {'genome_size': G (not rounded), 'genome_size_se', 'genome_size_wald_interval':
     (G - z se_G, G + z se_G)}; the last two None where the coverage has no standard error.  `info`:
-    observed_information's dict."""
+    observed_information's dict, or with `robust` sandwich_covariance's, whose robust standard error is then used."""
     z = _z(level)
     scale = 1 if sample_factor is None else sample_factor
     c = info['estimate'][0]
     occurrences = sum(i * n for i, n in hist_orig.items())
     corrected = model.correct_c(c * scale)
     size = occurrences / corrected if corrected != 0 else float('inf')
-    se_c = info['standard_errors'][info['params'][0]]
+    se_c = info['robust_standard_errors' if robust else 'standard_errors'][info['params'][0]]
     if se_c is None or not math.isfinite(size):
         return {'genome_size': size, 'genome_size_se': None, 'genome_size_wald_interval': None}
     se = size * se_c / abs(c)

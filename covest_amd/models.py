@@ -300,6 +300,28 @@ class BasicModel:
         ll, grad, hess = self.loglikelihood_hessian_points(self._points_array([args]))
         return float(ll[0]), [float(g) for g in grad[0]], [[float(v) for v in row] for row in hess[0]]
 
+    def loglikelihood_score_outer_points(self, points):
+        """LL, its analytic gradient and the outer product of the per-k-mer scores for an (n, param_count) array of
+        points -> (ll[n], grad[n, param_count], opg[n, param_count, param_count]):
+        B_kl = sum_{h_j != 0} h_j (d_k p_j / p_j)(d_l p_j / p_j) + [tail != 0, sp < 1] tail S_k S_l / (1 - sp)^2 with
+        S_k = sum_j d_k p_j, of the function loglikelihood_gradient_points differentiates (covest_eval_points_opg; ll
+        and grad are that call's bits).  Symmetric bit for bit, a row and column whose parameter the clamp moved are 0,
+        every entry is NaN where the value is not finite.  The meat of information.sandwich_covariance."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, self.param_count)
+        P = self.param_count
+        ll = np.empty(len(pts), dtype=np.float64)
+        grad = np.empty((len(pts), P), dtype=np.float64)
+        opg = np.empty((len(pts), P, P), dtype=np.float64)
+        if len(pts):
+            _capi.check(_capi.lib().covest_eval_points_opg(self.handle, len(pts), _as_dp(pts), _as_dp(ll), _as_dp(grad),
+                                                           _as_dp(opg)), "covest_eval_points_opg")
+        return ll, grad, opg
+
+    def compute_loglikelihood_score_outer(self, *args):
+        """(LL, [dLL/dparam ...], [[B_kl ...] ...]) at one point."""
+        ll, grad, opg = self.loglikelihood_score_outer_points(self._points_array([args]))
+        return float(ll[0]), [float(g) for g in grad[0]], [[float(v) for v in row] for row in opg[0]]
+
     def launch_record(self):
         """What the last loglikelihood_points() launched: {"launches": {instantiation: launches}, "plans": [K-factored
         plans]} (covest_model_launch_record; host bookkeeping, nothing waits for the device)."""

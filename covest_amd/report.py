@@ -33,7 +33,10 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
     level, 0.95 otherwise); the record then carries standard_errors, wald_intervals, genome_size_se,
     genome_size_wald_interval and wald_level, the coverage's in the units of the record's `coverage` (times
     sample_factor).  They are the MODEL's standard errors: it treats the k-mer counts as independent and |LL| is
-    1e7..1e8, so they are very small.  Without it the record is unchanged."""
+    1e7..1e8, so they are very small.  Without it the record is unchanged.  When the dict is
+    covest_amd.information.sandwich_covariance's (it carries 'robust_standard_errors') the record adds
+    robust_standard_errors, robust_wald_intervals and genome_size_robust_se, scaled like their neighbours: corrected
+    for misfit of the mixture, NOT for dependence between overlapping k-mers; otherwise it does not."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -93,6 +96,15 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
         record['genome_size_wald_interval'] = (None if size['genome_size_wald_interval'] is None
                                                else [float(v) for v in size['genome_size_wald_interval']])
         record['wald_level'] = level
+        if 'robust_standard_errors' in information:
+            robust = genome_size_se(model, hist_orig, information, sample_factor=scale, level=level, robust=True)
+            record['robust_standard_errors'] = {
+                name: (None if se is None else float(se * scale if name == first else se))
+                for name, se in information['robust_standard_errors'].items()}
+            record['robust_wald_intervals'] = {
+                name: (None if iv is None else [float(v * scale if name == first else v) for v in iv])
+                for name, iv in wald_intervals(information, level, robust=True).items()}
+            record['genome_size_robust_se'] = None if robust['genome_size_se'] is None else float(robust['genome_size_se'])
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

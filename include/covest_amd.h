@@ -133,6 +133,21 @@ int covest_eval_points_grad(covest_model *m, int64_t n, const double *params, do
 int covest_eval_points_hess(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad,
                             double *out_hess);
 
+/* Values, the analytic gradient (the same bits covest_eval_points_grad returns) and, beside them, the OUTER PRODUCT OF
+ * THE SCORES, the meat of the sandwich (robust) covariance A^-1 B A^-1: with
+ * r_k(j) = d_k p_j / p_j, sp = sum_j p_j, S_k = sum_j d_k p_j over the evaluated keys and on = [tail != 0 and sp < 1],
+ *     B_kl = sum_{h_j != 0} h_j r_k(j) r_l(j)  +  on tail S_k S_l / (1 - sp)^2,
+ * the uncentred sum over k-mers of the outer product of their scores, the tail as one more class; of the function
+ * covest_eval_points_grad differentiates.  HOST arrays: params [n][param_count], out_ll[n], out_grad[n][param_count],
+ * out_opg[n][param_count][param_count].  The matrix is symmetric bit for bit (the upper triangle is computed and
+ * mirrored).  A row and column whose parameter fit_to_bounds moved are 0; where the value is not finite every entry of
+ * gradient and matrix is NaN.  The order-1 walk of ll_deriv.hip with one product per parameter pair in each key's
+ * epilogue, and a small finishing launch, neither entered in the launch record; a point's numbers do not depend on
+ * what else is in the call.  The unit is one distinct k-mer counted as independent of the others: B corrects the
+ * covariance for misfit of the mixture, not for dependence between overlapping k-mers. */
+int covest_eval_points_opg(covest_model *m, int64_t n, const double *params, double *out_ll, double *out_grad,
+                           double *out_opg);
+
 /* Documented divergence made visible: the reference forms its pmf product in x87 long double BEFORE
  * scaling it (c_src/covest_poissonmodule.c:19-24), so for large rates against large keys
  * (ln(l^i / i!) > 11356.5 at i = min(j, floor(l))) truncated_poisson returns +inf, the likelihood
