@@ -611,6 +611,7 @@ static int eval_points_deriv(covest_model *m, int order, int64_t n, const double
     int rc = dev_guard.status();
     if (rc != COVEST_OK)
         return rc;
+    LaunchRecordScope record(m->record);
     const int P = m->n_par;
     StagedPoints sp;
     rc = stage_points(m, n, params, (size_t)n * (1 + P + (order != 1 ? P * P : 0)) * sizeof(double), sp);

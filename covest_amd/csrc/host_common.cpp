@@ -372,6 +372,7 @@ int64_t covest_compiled_variants(char *buf, int64_t cap)
     add(kBasicVariantNames, kBasicVariants);
     add(kFixVariantNames, kFixVariants);
     add(kArgminVariantNames, kArgminVariants);
+    add(kDerivVariantNames, kDerivVariants);
     if (buf && cap > 0) {
         const size_t n = std::min<size_t>(t.size(), (size_t)(cap - 1));
         std::memcpy(buf, t.data(), n);

@@ -13,7 +13,7 @@ namespace covest {
 // Host bookkeeping only.  A launcher notes the instantiation it picked and how many launches it took into the record
 // of the evaluation in progress on the calling thread (LaunchRecordScope; none: nothing is noted).  Nothing is read from
 // the device and nothing waits for it.  The names come from the tables beside the instantiation lists (kVariantNames of
-// ll_factored.hip, ll_basic.hip and argmin.hip); covest_compiled_variants lists those tables.
+// ll_factored.hip, ll_basic.hip, argmin.hip and ll_deriv.hip); covest_compiled_variants lists those tables.
 struct LaunchRecord {
     struct Entry {
         const char *name;
@@ -37,12 +37,13 @@ struct LaunchRecordScope { // notes go to `r` (cleared) until the scope ends
     LaunchRecord *prev;
 };
 // The instantiations linked in, by family; a launcher records kXxxVariantNames[its index].
-constexpr int kFactoredVariants = 10, kBasicVariants = 8, kFixVariants = 6, kArgminVariants = 3;
+constexpr int kFactoredVariants = 10, kBasicVariants = 8, kFixVariants = 6, kArgminVariants = 3, kDerivVariants = 7;
 extern const char *const kFactoredVariantNames[kFactoredVariants]; // ll_factored.hip
 extern const char *const kFactoredFinishNames[2];                   // ll_factored.hip: ll_finish_dense, ll_finish_partials
 extern const char *const kBasicVariantNames[kBasicVariants];       // ll_basic.hip
 extern const char *const kFixVariantNames[kFixVariants];           // argmin.hip
 extern const char *const kArgminVariantNames[kArgminVariants];     // argmin.hip
+extern const char *const kDerivVariantNames[kDerivVariants];       // ll_deriv.hip: six ll_deriv<P,mode>, then ll_deriv_finish
 
 // K-direct: one wavefront per grid point, one exp per pmf term (ll_direct.hip).
 // out_ll[n]; when out_p != nullptr (n must be 1) also writes p_j for every bin
@@ -145,7 +146,7 @@ hipError_t launch_axis_min(const AxisMinPlan &p, const double *ll, double *parti
 // them; P (P + 1) / 2 more than order 1 for kDerivOpg (sum h (d_k p / p)(d_l p / p) of each pair).  A second launch adds
 // a point's segments in ascending order and applies the tail terms.  out_ll[n], out_grad[n][P], and for order 2 or
 // kDerivOpg out_hess[n][P][P], the Hessian or the outer product (symmetric: the upper triangle computed, mirrored; not
-// read for order 1); src is a point list.  Two launches (per 16384 points); not entered in the launch record.
+// read for order 1); src is a point list.  Two launches (per 16384 points), each noted in the launch record.
 constexpr int kDerivOpg = 3;
 int ll_deriv_segments(const DevModel &m);
 size_t ll_deriv_partial_bytes(const DevModel &m, int order, int64_t n);

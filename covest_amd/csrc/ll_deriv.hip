@@ -498,6 +498,11 @@ void launch_part(const DevModel &m, const PointSource &part, int n_seg, int64_t 
 
 } // namespace
 
+// the instantiations of launch_ll_deriv's dispatch, by name (the launch record, covest_compiled_variants): 3 * (P == 5) +
+// (order 1, 2, kDerivOpg -> 0, 1, 2); the finishing kernel's six share one name
+const char *const kDerivVariantNames[kDerivVariants] = {"ll_deriv<2,grad>", "ll_deriv<2,hess>", "ll_deriv<2,opg>", "ll_deriv<5,grad>",
+                                                        "ll_deriv<5,hess>", "ll_deriv<5,opg>", "ll_deriv_finish"};
+
 int ll_deriv_segments(const DevModel &m)
 {
     const int64_t n = (m.bins.n + kDerivSegKeys - 1) / kDerivSegKeys;
@@ -534,6 +539,8 @@ hipError_t launch_ll_deriv(const DevModel &m, int order, const PointSource &src,
         part.t_list = src.t_list ? src.t_list + first : nullptr;
         launch(m, part, n_seg, cnt, partial, out_ll + first, out_grad + first * P,
                order != 1 ? out_hess + first * P * P : nullptr, stream);
+        record_launch(kDerivVariantNames[(P == 5 ? 3 : 0) + (order == 1 ? 0 : order == 2 ? 1 : 2)]);
+        record_launch(kDerivVariantNames[kDerivVariants - 1]);
     }
     return hipGetLastError();
 }

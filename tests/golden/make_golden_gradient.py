@@ -54,6 +54,10 @@ SMALL = mpf(1e-8)  # the double the extension compares with
 
 
 def load(name):
+    """The histogram `name`.hist -- or one given inline as {"keys": [...], "counts": [...]}, dictionary order as listed
+    (tests/golden/make_golden_deriv_shapes.py)."""
+    if not isinstance(name, str):
+        return {int(j): h for j, h in zip(name["keys"], name["counts"])}
     hist = {}
     with open(os.path.join(HERE, name + ".hist")) as f:
         for line in f:
@@ -98,6 +102,12 @@ def dlog_norm(x):
     return 1 / (1 - mp.exp(-xr))
 
 
+def class_rates(k, r, c, e, S):
+    """lambda_s = ck 3^-s (1 - e)^(k - s) e^s for s < S, ck = c (r - k + 1) / r."""
+    ck = c * (r - k + 1) / r
+    return [ck * mpf(3) ** -s * (1 - e) ** (k - s) * e ** s for s in range(S)]
+
+
 def weights(q1, q2, q, o):
     """b_o and its derivatives in q1, q2, q."""
     if o == 1:
@@ -122,9 +132,8 @@ def grad_partial(consts, theta, o_lo, o_hi, with_grad=True, quantize=True):
     q1, q2, q = (theta[2], theta[3], theta[4]) if repeats else (mpf(1), mpf(0), mpf(0))
     S = len(comb)
     ck = c * (r - k + 1) / r
-    lam, dlc, dle = [], [], []
+    lam, dlc, dle = class_rates(k, r, c, e, S), [], []
     for s in range(S):
-        lam.append(ck * mpf(3) ** -s * (1 - e) ** (k - s) * e ** s)
         dlc.append(lam[s] / c)
         d = mpf(0)
         if s > 0:

@@ -1,6 +1,6 @@
 """What the GPU parity tests share (tests/test_gpu_parity.py, tests/test_gpu_variants.py): the comparison at 1e-9
 relative with IEEE specials identical, and the graded slack of the tail term tail * log(1 - sp_j) with its committed
-budgets (tests/golden/tail_noise_bounds.json)."""
+budgets (tests/golden/tail_noise_bounds.json); and the bounds of the derivative tests."""
 import json
 import math
 import os
@@ -51,6 +51,36 @@ def _model(case, hist=None):
 
 
 K_TAIL = 8.0  # rounding errors of K eps per key are granted to the GPU's sp_j (first-order propagation)
+
+
+# ---- the derivative tests' bounds (tests/test_gpu_gradient.py, _hessian.py, _opg.py, _deriv_shapes.py): the plain TOL applied
+# to the quantity's own condition sum from the 50-digit fixture, plus the first-order propagation of the slack
+# delta = K_TAIL eps n_keys the parity suite grants sp (only where there is a live tail term: tail != 0 and sp < 1)
+def _tail_delta(n_keys):
+    return K_TAIL * 2.0 ** -52 * n_keys
+
+
+def _grad_bound(tail, sp, C, D, delta):
+    """|g_k - want| <= TOL C_k + |tail| D_k delta / (1 - sp)^2, D_k = |sum_j d_k p_j|."""
+    return TOL * C + (abs(tail) * D * delta / (1 - sp) ** 2 if tail and sp < 1 else 0.0)
+
+
+def _hess_bound(tail, sp, C, D2, Dk, Dl, delta):
+    """|H_kl - want| <= TOL C_kl + s_kl, s_kl = |tail| (D2_kl delta / (1 - sp)^2 + 2 D_k D_l delta / (1 - sp)^3)."""
+    s_kl = 0.0
+    if tail and sp < 1:
+        s_kl = abs(tail) * (D2 * delta / (1 - sp) ** 2 + 2 * Dk * Dl * delta / (1 - sp) ** 3)
+    return TOL * C + s_kl
+
+
+def _opg_slack(tail, sp, Dk, Dl, delta):
+    """s_kl = |tail| 2 |S_k| |S_l| delta / (1 - sp)^3 (tests/golden/opg.json stores it as `s`)."""
+    return abs(tail) * 2 * Dk * Dl * delta / (1 - sp) ** 3 if tail and sp < 1 else 0.0
+
+
+def _opg_bound(C, s_kl):
+    """|B_kl - want| <= TOL C_kl + s_kl."""
+    return TOL * C + s_kl
 
 
 def _tail_slack(tail, ll, sp, n_keys):

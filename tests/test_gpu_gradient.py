@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, load_hist, rel_err
-from parity_helpers import K_TAIL, TOL, _model
+from parity_helpers import TOL, _grad_bound, _model, _tail_delta
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +22,7 @@ def test_every_fixture_point(hip_lib):
     for case in g["cases"]:
         m = _model(case)
         ll, grad = m.loglikelihood_gradient_points(case["points"])
-        delta = K_TAIL * 2.0 ** -52 * case["n_keys"]
+        delta = _tail_delta(case["n_keys"])
         for i, point in enumerate(case["points"]):
             n += 1
             e = rel_err(float(ll[i]), case["ll"][i])
@@ -32,7 +32,7 @@ def test_every_fixture_point(hip_lib):
             sp, tail = case["sp"][i], case["tail"]
             for d, want in enumerate(case["grad"][i]):
                 C, D = case["C"][i][d], case["D"][i][d]
-                bound = TOL * C + (abs(tail) * D * delta / (1 - sp) ** 2 if tail and sp < 1 else 0.0)
+                bound = _grad_bound(tail, sp, C, D, delta)
                 diff = abs(float(grad[i, d]) - want)
                 print("    d%d: got %.17g want %.17g |diff| %.3g bound %.3g (C %.3g)" % (d, grad[i, d], want, diff, bound, C))
                 if C > 0:

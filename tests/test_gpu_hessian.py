@@ -7,14 +7,13 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, load_hist, rel_err
-from parity_helpers import K_TAIL, TOL, _model
+from parity_helpers import TOL, _grad_bound, _hess_bound, _model, _tail_delta
 
 pytestmark = pytest.mark.gpu
 
 
-def _grad_bound(case, i, d, delta):
-    sp, tail = case["sp"][i], case["tail"]
-    return TOL * case["Cg"][i][d] + (abs(tail) * case["D"][i][d] * delta / (1 - sp) ** 2 if tail and sp < 1 else 0.0)
+def _grad_bound_of(case, i, d, delta):
+    return _grad_bound(case["tail"], case["sp"][i], case["Cg"][i][d], case["D"][i][d], delta)
 
 
 def test_every_fixture_point(hip_lib):
@@ -28,7 +27,7 @@ def test_every_fixture_point(hip_lib):
         m = _model(case)
         P = m.param_count
         ll, grad, hess = m.loglikelihood_hessian_points(case["points"])
-        delta = K_TAIL * 2.0 ** -52 * case["n_keys"]
+        delta = _tail_delta(case["n_keys"])
         tail = case["tail"]
         for i, point in enumerate(case["points"]):
             n += 1
@@ -38,7 +37,7 @@ def test_every_fixture_point(hip_lib):
             assert e <= TOL, (case["source"], point, float(ll[i]), case["ll"][i])
             sp = case["sp"][i]
             for d, want in enumerate(case["grad"][i]):
-                bound = _grad_bound(case, i, d, delta)
+                bound = _grad_bound_of(case, i, d, delta)
                 diff = abs(float(grad[i, d]) - want)
                 if case["Cg"][i][d] > 0:
                     worst_g = max(worst_g, diff / case["Cg"][i][d])
@@ -46,11 +45,7 @@ def test_every_fixture_point(hip_lib):
             for k in range(P):
                 for l in range(P):
                     want, C = case["hess"][i][k][l], case["C"][i][k][l]
-                    s_kl = 0.0
-                    if tail and sp < 1:
-                        s_kl = abs(tail) * (case["D2"][i][k][l] * delta / (1 - sp) ** 2
-                                            + 2 * case["D"][i][k] * case["D"][i][l] * delta / (1 - sp) ** 3)
-                    bound = TOL * C + s_kl
+                    bound = _hess_bound(tail, sp, C, case["D2"][i][k][l], case["D"][i][k], case["D"][i][l], delta)
                     diff = abs(float(hess[i, k, l]) - want)
                     if l >= k:
                         print("    H%d%d: got %.17g want %.17g |diff| %.3g bound %.3g (C %.3g)" % (k, l, hess[i, k, l], want, diff, bound, C))
@@ -71,11 +66,11 @@ def test_value_is_k_directs_and_gradient_is_k_grads(hip_lib):
         ll, grad, _ = m.loglikelihood_hessian_points(case["points"])
         want = m.loglikelihood_points(case["points"], kernel="direct")
         _, want_g = m.loglikelihood_gradient_points(case["points"])
-        delta = K_TAIL * 2.0 ** -52 * case["n_keys"]
+        delta = _tail_delta(case["n_keys"])
         for i, p in enumerate(case["points"]):
             assert rel_err(float(ll[i]), float(want[i])) <= 1e-11, (case["source"], p, float(ll[i]), float(want[i]))
             for d in range(m.param_count):
-                assert abs(float(grad[i, d]) - float(want_g[i, d])) <= 2 * _grad_bound(case, i, d, delta), (case["source"], p, d)
+                assert abs(float(grad[i, d]) - float(want_g[i, d])) <= 2 * _grad_bound_of(case, i, d, delta), (case["source"], p, d)
         m.close()
 
 

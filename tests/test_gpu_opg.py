@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, load_hist, rel_err
-from parity_helpers import K_TAIL, TOL, _model
+from parity_helpers import K_TAIL, TOL, _grad_bound, _model, _opg_bound, _tail_delta
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +26,7 @@ def test_every_fixture_point(hip_lib):
         m = _model(case)
         P = m.param_count
         ll, grad, opg = m.loglikelihood_score_outer_points(case["points"])
-        delta = K_TAIL * 2.0 ** -52 * case["n_keys"]
+        delta = _tail_delta(case["n_keys"])
         tail = case["tail"]
         for i, point in enumerate(case["points"]):
             n += 1
@@ -36,7 +36,7 @@ def test_every_fixture_point(hip_lib):
             assert e <= TOL, (case["source"], point, float(ll[i]), case["ll"][i])
             sp = case["sp"][i]
             for d, want in enumerate(case["grad"][i]):
-                bound = TOL * case["Cg"][i][d] + (abs(tail) * case["D"][i][d] * delta / (1 - sp) ** 2 if tail and sp < 1 else 0.0)
+                bound = _grad_bound(tail, sp, case["Cg"][i][d], case["D"][i][d], delta)
                 diff = abs(float(grad[i, d]) - want)
                 if case["Cg"][i][d] > 0:
                     worst_g = max(worst_g, diff / case["Cg"][i][d])
@@ -44,7 +44,7 @@ def test_every_fixture_point(hip_lib):
             for k in range(P):
                 for l in range(P):
                     want, C, s_kl = case["opg"][i][k][l], case["C"][i][k][l], case["s"][i][k][l]
-                    bound = TOL * C + s_kl
+                    bound = _opg_bound(C, s_kl)
                     diff = abs(float(opg[i, k, l]) - want)
                     if l >= k:
                         print("    B%d%d: got %.17g want %.17g |diff| %.3g bound %.3g (C %.3g)" % (k, l, opg[i, k, l], want, diff, bound, C))

@@ -14,7 +14,7 @@ import zlib
 import numpy as np
 import pytest
 
-from conftest import rel_err
+from conftest import load_hist, rel_err
 from parity_helpers import TOL, _check, _slack_budget, _tail_noise
 
 SUBNORMAL = 2.2250738585072014e-308
@@ -26,6 +26,7 @@ FAMILIES = {
     "factored point lists": lambda n: n == "ll_finish_partials",
     "basic and hand-back": lambda n: n.startswith(("ll_basic<", "fix_")),
     "arg-min": lambda n: n.startswith("argmin_"),
+    "derivatives": lambda n: n.startswith("ll_deriv"),
 }
 
 
@@ -385,6 +386,40 @@ def test_argmin_variants(hip_lib):
             g.close()
     m.close()
     _report("arg-min", observed)
+
+
+# ---- the derivative kernel ---------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_derivative_variants(hip_lib):
+    """ll_deriv<P,mode> for both models and the three modes (value + gradient, + Hessian, + outer product of the scores)
+    on the 15-key histogram: each call's record shows its instantiation and ll_deriv_finish, once each and nothing else;
+    a call of 16384 + 16384 + 3 points shows three launches of each.  The value beside the derivatives is K-direct's at
+    1e-11 (the values themselves: tests/test_gpu_deriv_shapes.py and the three fixtures' tests)."""
+    from covest_amd import BasicModel, RepeatsModel
+    observed = {}
+    hist = load_hist("sim_c10_e0.05")
+    modes = (("grad", "loglikelihood_gradient_points"), ("hess", "loglikelihood_hessian_points"),
+             ("opg", "loglikelihood_score_outer_points"))
+    for cls, P, pts in ((BasicModel, 2, [[10.0, 0.05], [8.0, 0.02]]),
+                        (RepeatsModel, 5, [[10.0, 0.05, 0.6, 0.5, 0.3], [8.0, 0.02, 0.8, 0.3, 0.6]])):
+        m = cls(21, 100, hist, 0, max_error=8)
+        direct = m.loglikelihood_points(pts, kernel="direct")
+        for mode, fn in modes:
+            name = "ll_deriv<%d,%s>" % (P, mode)
+            out = getattr(m, fn)(pts)
+            rec = m.launch_record()
+            assert rec["launches"] == {name: 1, "ll_deriv_finish": 1} and rec["plans"] == [], (name, rec)
+            _observe(observed, "derivatives: " + name, rec)
+            _check(out[0], direct, name + " vs direct", tol=1e-11)
+            assert all(np.all(np.isfinite(a)) for a in out), name
+        big = np.tile(np.array(pts), (16386, 1))[:2 * 16384 + 3]
+        ll, _ = m.loglikelihood_gradient_points(big)
+        rec = m.launch_record()
+        assert rec["launches"] == {"ll_deriv<%d,grad>" % P: 3, "ll_deriv_finish": 3}, rec
+        _observe(observed, "derivatives: %d points, P = %d" % (len(big), P), rec)
+        assert ll.shape == (len(big),) and np.array_equal(ll[:2], ll[-3:-1]) and ll[-1] == ll[0]
+        m.close()
+    _report("derivatives", observed)
 
 
 def test_every_compiled_variant_has_a_family(hip_lib):
