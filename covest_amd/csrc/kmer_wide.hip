@@ -17,7 +17,8 @@
 // it took the lock, before any lane of the wave comes round again.  Readers load state and key past their L1
 // (agent-scope atomic loads): a line cached while the slot was still empty would otherwise hide the key.
 // Capability path: 1 + W loads and one atomic per occurrence, a CAS and W + 1 stores per new key; K-kmer's line
-// sharing and four-bases-per-load tricks are not repeated here.
+// sharing and four-bases-per-load tricks are not repeated here.  Every width and both sides of every change of width
+// are counted against a reference in tests/test_gpu_kmer_widths.py.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

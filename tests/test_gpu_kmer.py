@@ -51,8 +51,9 @@ def test_random_reads_against_oracle(hip_lib, canonical):
         assert counts.histogram() == want
         assert len(counts) == len(ko.count_kmers(reads, k, canonical=canonical)[0])
         counts.close()
-    # k > 31: keys of 2, 4 and 8 words (kmer_wide.hip) -- the reference's integers have no limit (bin/kmer_hist.py:
-    # 18-31); a small table that has to grow several times, several launches
+    # k > 31: keys of 2 and 4 words (kmer_wide.hip; every width, the 8-word keys of k = 128 .. 255 included, is in
+    # tests/test_gpu_kmer_widths.py) -- the reference's integers have no limit (bin/kmer_hist.py:18-31); a small table
+    # that has to grow several times, several launches
     few = reads[:3000]
     for k in (32, 45, 63, 64, 90, 100):
         counts = kh.KmerCounts(k, canonical=canonical, min_slots=1024)
