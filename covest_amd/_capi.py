@@ -36,6 +36,7 @@ EXPORTS = (
     "covest_kmer_scatter_rate",
     "covest_reads_open", "covest_reads_close", "covest_reads_next", "covest_reads_bytes",
     "covest_thin_histogram", "covest_thin_histogram_timed",
+    "covest_truncated_poisson", "covest_truncated_poisson_table",
 )
 
 
@@ -205,6 +206,10 @@ def lib():
     L.covest_thin_histogram_timed.restype = ctypes.c_int
     L.covest_thin_histogram_timed.argtypes = [ctypes.c_int32, i64, ctypes.POINTER(ctypes.c_int32), dp, ctypes.c_double,
                                               i64, dp, ctypes.c_int32, dp]
+    L.covest_truncated_poisson.restype = ctypes.c_int
+    L.covest_truncated_poisson.argtypes = [i32, i64, dp, i64p, i32, dp]
+    L.covest_truncated_poisson_table.restype = ctypes.c_int
+    L.covest_truncated_poisson_table.argtypes = [i32, i64, dp, i64, i64p, dp]
     L.covest_grid_diag.restype = i64
     L.covest_grid_diag.argtypes = [vp, ctypes.POINTER(i64), i64]
     L.covest_grid_launch_record.restype = i64

@@ -19,9 +19,10 @@ LIB_PATH = os.path.join(LIB_DIR, "libcovest_amd.so")
 # when one of its kernels is first launched, so a process only pays for the variants it uses.
 SOURCES = [("host_common.cpp", (), "host_common"), ("tiles_host.cpp", (), "tiles_host"), ("plan_factored.cpp", (), "plan_factored"),
            ("abi_model.cpp", (), "abi_model"), ("abi_grid.cpp", (), "abi_grid"), ("kmer_host.cpp", (), "kmer_host"),
-           ("thin_host.cpp", (), "thin_host"), ("reads_io.cpp", (), "reads_io"), ("ll_direct.hip", (), "ll_direct"),
+           ("thin_host.cpp", (), "thin_host"), ("abi_tp.cpp", (), "abi_tp"), ("reads_io.cpp", (), "reads_io"), ("ll_direct.hip", (), "ll_direct"),
            ("ll_basic.hip", (), "ll_basic"), ("ll_factored.hip", (), "ll_factored"), ("argmin.hip", (), "argmin"), ("axis_min.hip", (), "axis_min"), ("ll_deriv.hip", (), "ll_deriv"),
-           ("kmer_count.hip", (), "kmer_count"), ("kmer_wide.hip", (), "kmer_wide"), ("kmer_bulk.hip", (), "kmer_bulk"), ("thin_hist.hip", (), "thin_hist")]
+           ("kmer_count.hip", (), "kmer_count"), ("kmer_wide.hip", (), "kmer_wide"), ("kmer_bulk.hip", (), "kmer_bulk"), ("thin_hist.hip", (), "thin_hist"),
+           ("tp_eval.hip", (), "tp_eval")]
 SOURCES += [("ll_factored.hip", ("-DCOVEST_FACTORED_VARIANT=%d" % v,), "ll_factored_v%d" % v) for v in range(10)]
 SOURCES += [("ll_basic.hip", ("-DCOVEST_BASIC_VARIANT=%d" % v,), "ll_basic_v%d" % v) for v in range(8)]
 MAX_PARALLEL = 8

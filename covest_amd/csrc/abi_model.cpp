@@ -303,7 +303,6 @@ hipError_t launch_ll(const covest_model *m, int kernel, const PointSource &src, 
 
 } // namespace covest
 
-constexpr int64_t kInPlaceMaxPoints = 256;   // point lists up to this size: parameters and values in mapped host memory
 constexpr int64_t kInPlaceMaxListPoints = 4; // repeats model, list mode: tables read in place (13 KB a point, 8 workgroups each)
 
 // The queue a point-list launch hands points back through (direct_point.h): room for n entries, empty.  The counter is

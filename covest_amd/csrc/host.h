@@ -7,6 +7,7 @@
 //   abi_grid.cpp      covest_grid_*
 //   kmer_host.cpp     covest_kmer_*
 //   thin_host.cpp     covest_thin_histogram*
+//   abi_tp.cpp        covest_truncated_poisson, covest_truncated_poisson_table
 // ).  Nothing here is part of the C ABI (include/covest_amd.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -382,7 +383,8 @@ int build_factored_plan(covest_grid *g, const double *const *axes, const int64_t
 int build_list_plan(covest_model *m, int64_t n, const double *params, const std::vector<int32_t> &t_list,
                     const std::vector<int32_t> *o_base_list, DevBuf &buf, FactoredPlan &pl, bool in_place = false);
 
-// ---- abi_model.cpp: kernel dispatch shared with the grid entry points
+// ---- abi_model.cpp: kernel dispatch shared with the grid entry points; the in-place limit shared with abi_tp.cpp
+constexpr int64_t kInPlaceMaxPoints = 256; // lists (of points, of pmf pairs) up to this size: read and written in mapped host memory
 int resolve_kernel(const covest_model *m, int32_t kernel, const covest_grid *g);
 SubList sub_list_of(const covest_model *m, int t_max, void *index, void *word, void *ctl);
 hipError_t launch_ll(const covest_model *m, int kernel, const PointSource &src, int64_t n, double *out, const SubList &sub,

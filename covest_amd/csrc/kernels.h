@@ -153,6 +153,20 @@ size_t ll_deriv_partial_bytes(const DevModel &m, int order, int64_t n);
 hipError_t launch_ll_deriv(const DevModel &m, int order, const PointSource &src, int64_t n, double *partial, double *out_ll,
                            double *out_grad, double *out_hess, hipStream_t stream);
 
+// ---- K-tp (tp_eval.hip): the truncated-Poisson pmf itself, c_src/covest_poissonmodule.c:7-35 ----
+// Modes of the pairs kernel (include/covest_amd.h COVEST_TP_*): the finite value the formula defines (0 below the
+// doubles' range, 0 at a rate that is 0 or NaN); the same with +inf where the extension's running long-double product
+// overflows (direct_point.h REF_OVF's rule); the exponent itself (-inf where the value mode returns 0 for its rate).
+constexpr int kTpValue = 0, kTpReference = 1, kTpLog = 2;
+constexpr int64_t kTpMaxPairs = (int64_t)1 << 30; // pairs of one launch
+// in: [4][n] doubles = rate | key | ln key! | ln m!, m = min(key, floor(rate)) (anything where rate < 1); out[n].
+// K-direct's expressions in K-direct's order, one pair a lane.  One launch, not entered in the launch record.
+hipError_t launch_tp_pairs(int mode, int64_t n, const double *in, double *out, hipStream_t stream);
+// out[n_l][n_j] = TP(rates[i], key of bin b) in value mode BY THE RECURRENCE (streams.h), along the tiles of `tv`: a
+// table built over the key list with counts that are not 0 and bin index = position in the list (tiles_host.cpp).
+hipError_t launch_tp_table(const TileView &tv, int64_t n_l, const double *rates, int64_t n_j, double *out,
+                           hipStream_t stream);
+
 // ---- K-kmer: k-mer abundance histogram (kmer_count.hip), SURVEY 8(f) row F1 ----
 // Open-addressing table in HBM, slots = 2^log2_slots, one 16-byte entry per slot: {key, count}
 // (key all-ones = empty).  Key and count share a cache line on purpose: a k-mer costs ONE scattered

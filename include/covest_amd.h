@@ -157,6 +157,29 @@ int covest_eval_points_opg(covest_model *m, int64_t n, const double *params, dou
  * work.  No benchmark configuration contains such a point. */
 int covest_reference_overflow(const covest_model *m, int64_t n, const double *params, uint8_t *flags);
 
+/* ---- the pmf itself: covest_poisson.truncated_poisson(l, j), c_src/covest_poissonmodule.c:7-35 ----
+ * The function every likelihood value above is a mixture of, on its own.  No model handle;
+ * HOST arrays owned by the caller; device < 0 = the calling thread's current device.
+ *   COVEST_TP_VALUE      the finite value the formula defines: 0 where it lies below the doubles' range, never inf;
+ *                        0.0 where l == 0 or l is NaN (:15), and for a negative l (no rate: the kernels' `x > 0`)
+ *   COVEST_TP_REFERENCE  the same, but +inf exactly where the extension's running long-double product overflows
+ *                        (:19-24; the rule of COVEST_KERNEL_DIRECT_REF): what the extension returns
+ *   COVEST_TP_LOG        the logarithm of that value before the last exp: finite wherever l > 0 -- also where the
+ *                        value underflows and where the extension overflows --, -inf where the value modes return 0
+ *                        for the rate's sake
+ * covest_truncated_poisson: out[i] = TP(l[i], j[i]), one pair a lane, the likelihood kernels' term-by-term arithmetic
+ * (K-direct's), ln j! from the host's long-double table.  j >= 1, at most 4194304 (COVEST_E_INVALID otherwise, and
+ * for an unknown mode or more than 2^30 pairs); n == 0 returns COVEST_OK without touching the device.  A pair's bits
+ * do not depend on what else is in the call.
+ * covest_truncated_poisson_table: out[n_l][n_j] (row-major) = TP(l[i], j[b]) in COVEST_TP_VALUE mode BY THE RECURRENCE
+ * the fast likelihood kernels walk (one multiply a key along tiles of <= 32 keys, anchored by one exp where a rate's
+ * terms enter the doubles' range): j strictly ascending integers in 1..16384, COVEST_E_INVALID otherwise. */
+#define COVEST_TP_VALUE 0
+#define COVEST_TP_REFERENCE 1
+#define COVEST_TP_LOG 2
+int covest_truncated_poisson(int32_t device, int64_t n, const double *l, const int64_t *j, int32_t mode, double *out);
+int covest_truncated_poisson_table(int32_t device, int64_t n_l, const double *l, int64_t n_j, const int64_t *j, double *out);
+
 /* model.compute_probabilities(*params): models.py:81-98, :211-242.  out_p[n_keys]
  * in key order (host).  clamp != 0 applies fit_to_bounds first, which is how
  * compute_loglikelihood calls it (models.py:101-102); clamp == 0 is the raw
