@@ -13,3 +13,5 @@ from .profile import profile_negll, likelihood_interval, coverage_interval  # no
 from .information import observed_information, sandwich_covariance, wald_intervals, genome_size_se  # noqa: F401,E402
 from . import poisson  # noqa: F401,E402
 from .poisson import truncated_poisson, truncated_poisson_many, truncated_poisson_table  # noqa: F401,E402
+from . import simulate  # noqa: F401,E402
+from .simulate import random_genome, simulate_reads, SimulatedReads  # noqa: F401,E402

@@ -37,6 +37,7 @@ EXPORTS = (
     "covest_reads_open", "covest_reads_close", "covest_reads_next", "covest_reads_bytes",
     "covest_thin_histogram", "covest_thin_histogram_timed",
     "covest_truncated_poisson", "covest_truncated_poisson_table",
+    "covest_random_genome", "covest_random_genome_device", "covest_simulate_reads", "covest_simulate_reads_device",
 )
 
 
@@ -210,6 +211,15 @@ def lib():
     L.covest_truncated_poisson.argtypes = [i32, i64, dp, i64p, i32, dp]
     L.covest_truncated_poisson_table.restype = ctypes.c_int
     L.covest_truncated_poisson_table.argtypes = [i32, i64, dp, i64, i64p, dp]
+    u64 = ctypes.c_uint64
+    L.covest_random_genome.restype = ctypes.c_int
+    L.covest_random_genome.argtypes = [i32, i64, u64, vp]
+    L.covest_random_genome_device.restype = ctypes.c_int
+    L.covest_random_genome_device.argtypes = [i32, i64, u64, vp, vp]
+    L.covest_simulate_reads.restype = ctypes.c_int
+    L.covest_simulate_reads.argtypes = [i32, vp, i64, i32, i64, i64, ctypes.c_double, u64, i32, vp, vp]
+    L.covest_simulate_reads_device.restype = ctypes.c_int
+    L.covest_simulate_reads_device.argtypes = [i32, vp, i64, i32, i64, i64, ctypes.c_double, u64, i32, vp, vp, vp]
     L.covest_grid_diag.restype = i64
     L.covest_grid_diag.argtypes = [vp, ctypes.POINTER(i64), i64]
     L.covest_grid_launch_record.restype = i64

@@ -267,4 +267,14 @@ int thin_hist_chunks();
 hipError_t launch_thin_hist(const ThinSource *src, int64_t n, const double *lgam, double factor, int64_t out_len,
                             double *partial, double *out, hipStream_t stream);
 
+// ---- K-sim: the read simulator (sim_reads.hip; tools/simulator/ of the reference) ----
+// out[n]: a random genome, upper-case ASCII.  Any alignment of `out`.
+hipError_t launch_random_genome(int64_t n, uint64_t seed, unsigned char *out, hipStream_t stream);
+// out[n_reads * read_len]: reads first_read .. first_read + n_reads of the stream of `seed`, back to back; origin
+// (or nullptr)[n_reads] = pos << 1 | forward.  thr = floor(error_rate * 2^32), 2^32 included.  Any alignment of `out`;
+// nothing outside the two arrays is written.  One launch per 4 GiB of output.
+hipError_t launch_sim_reads(const unsigned char *genome, int64_t genome_len, int read_len, int64_t first_read,
+                            int64_t n_reads, uint64_t thr, uint64_t seed, int both_strands, unsigned char *out,
+                            int64_t *origin, hipStream_t stream);
+
 } // namespace covest

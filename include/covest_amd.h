@@ -370,6 +370,35 @@ int covest_reads_next(covest_reads *r, int64_t max_bases, const uint8_t **bases,
 /* file bytes consumed so far */
 int64_t covest_reads_bytes(const covest_reads *r);
 
+/* ---- read simulator: tools/simulator/generate_sequence.py, read_simulator.py:60-88 ----
+ * Reads of KNOWN coverage and error rate, written in the layout covest_kmer_add_device and
+ * covest_kmer_count_reads_device take (upper-case ASCII, read_len bases each, back to back, no offsets).  Where the
+ * reference draws from Python's unseeded `random`, every byte here is a function of (seed, read index, base index)
+ * through Philox4x32-10 (Random123; key = seed's low and high word), so reads [first_read, first_read + n_reads) of
+ * one call are the same slice of any other call with the same seed, genome and settings:
+ *   genome base i: block (lo32(i>>2), hi32(i>>2), 0, 1), word i & 3, "ACGT"[word >> 30]
+ *   read r:        header block (lo32(r), hi32(r), 0, 0) = w0..w3: pos = mulhi64(w0 | w1 << 32, genome_len - read_len)
+ *                  -- randrange(genome_size - read_length), the last start never drawn (:75) --; the forward slice if
+ *                  w2 & 1 or both_strands == 0, else its reverse complement (:77-78)
+ *   base i of it:  block (lo32(r), hi32(r), 1 + (i >> 2), 0), w = word i & 3: substituted iff w < floor(error_rate *
+ *                  2^32) by the base of code (code + 1 + w % 3) & 3, A C G T = 0 1 2 3: one of the other three (:16-20, :79)
+ * origin (may be NULL)[n_reads] = pos << 1 | forward.  The genome is a/c/g/t in either case (-s, the IUPAC
+ * substitution of :34-57, is not built): the host form answers COVEST_E_INVALID for any other byte; the device form
+ * does not look, and takes (byte >> 1) & 3 for a code, so any byte is SOME base.
+ * COVEST_E_INVALID: genome_len <= read_len, read_len < 1, n_reads < 0, first_read < 0, error_rate outside [0, 1] or
+ * NaN.  n_reads == 0 (n == 0): COVEST_OK, nothing launched.  device < 0 = the calling thread's current device.
+ * The _device forms take DEVICE buffers of any alignment and are asynchronous on `stream`; they write nothing outside
+ * d_bases[0 .. n_reads * read_len) and d_origin[0 .. n_reads).  The others take HOST buffers, copy and wait;
+ * COVEST_E_NOMEM where the device buffers of the call do not fit. */
+int covest_random_genome_device(int32_t device, int64_t n, uint64_t seed, uint8_t *d_out, void *stream);
+int covest_simulate_reads_device(int32_t device, const uint8_t *d_genome, int64_t genome_len, int32_t read_len,
+                                 int64_t first_read, int64_t n_reads, double error_rate, uint64_t seed,
+                                 int32_t both_strands, uint8_t *d_bases, int64_t *d_origin, void *stream);
+int covest_random_genome(int32_t device, int64_t n, uint64_t seed, uint8_t *out);
+int covest_simulate_reads(int32_t device, const uint8_t *genome, int64_t genome_len, int32_t read_len,
+                          int64_t first_read, int64_t n_reads, double error_rate, uint64_t seed,
+                          int32_t both_strands, uint8_t *bases, int64_t *origin);
+
 /* ---- histogram down-sampling: covest/histogram.py:47-70 sample_histogram ----
  * Expected counts of the histogram after keeping every read with probability 1/factor, BEFORE the
  * reference's randomised rounding (:71-74, host side): out[j-1] = sum_i counts_i * pmf_i(j) for
