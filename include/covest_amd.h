@@ -399,6 +399,38 @@ int covest_simulate_reads(int32_t device, const uint8_t *genome, int64_t genome_
                           int64_t first_read, int64_t n_reads, double error_rate, uint64_t seed,
                           int32_t both_strands, uint8_t *bases, int64_t *origin);
 
+/* ---- read sampler: covest/data.py:57-63 sample_reads, bin/read_sampler.py ----
+ * Keeps every read with probability 1 / factor and writes the kept reads, IN INPUT ORDER, in the layout they came in:
+ * the packed layout of covest_kmer_add_device (bases back to back at any alignment; offsets[n_reads + 1] ascending, or
+ * NULL when every read is read_len bases long).  Empty reads are reads: a kept one is an empty read of the output.
+ * Where the reference draws from Python's unseeded `random`, the selection is a function of (seed, read index):
+ *   read r = index within the call + first_read (64-bit);
+ *   w = word 0 of Philox4x32-10 (as above; key = seed's low and high word) on the counter (lo32(r), hi32(r), 0, 2);
+ *   the read is kept iff (uint64_t)w < thr, thr = floor((1.0 / factor) * 2^32) formed in double on the host
+ *   (prob = 1.0 / factor of data.py:58, quantised as the simulator quantises error_rate); factor == 1: thr = 2^32,
+ *   every read is kept.
+ * The simulator's counters end in (.., 0, 1) (genome) and (.., j, 0) (reads), so the selection of simulated reads with
+ * their own seed is independent of their content.  A chunk [a, a + m) sampled with first_read = a keeps exactly the
+ * reads the whole run keeps among those rows.
+ * Output: out_bases (any alignment), out_offsets[n_kept + 1] (may be NULL where offsets is), kept_index[n_kept] (may be
+ * NULL): the global indices r; counts[2] = (reads kept, bases kept).  The caller sizes the outputs for the input (the
+ * upper bound); nothing is written outside out_bases[0 .. bases_kept), out_offsets[0 .. n_kept], kept_index[0 .. n_kept)
+ * and counts[0 .. 2).  Scratch is the library's own (8 bytes a read of the input).
+ * COVEST_E_INVALID: factor < 1, NaN or infinite; n_reads < 0 or first_read < 0; offsets == NULL with read_len < 0;
+ * offsets without out_offsets; a NULL counts.  n_reads == 0: COVEST_OK, no kernel launched, counts (0, 0) and
+ * out_offsets[0] = 0 (the device form sets them by a memset on the stream).  COVEST_E_NOMEM where the device buffers of
+ * the call do not fit.  device < 0 = the calling thread's current device.
+ * The _device form takes DEVICE buffers, is asynchronous on `stream` and does not look at the offsets; the other takes
+ * HOST buffers, copies and waits, and answers COVEST_E_INVALID for offsets that are negative or descend. */
+int covest_sample_reads_device(int32_t device, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                               int64_t read_len, int64_t first_read, double factor, uint64_t seed,
+                               uint8_t *d_out_bases, int64_t *d_out_offsets, int64_t *d_kept_index,
+                               int64_t *d_counts, void *stream);
+int covest_sample_reads(int32_t device, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
+                        int64_t read_len, int64_t first_read, double factor, uint64_t seed,
+                        uint8_t *out_bases, int64_t *out_offsets, int64_t *kept_index,
+                        int64_t *n_kept, int64_t *bases_kept);
+
 /* ---- histogram down-sampling: covest/histogram.py:47-70 sample_histogram ----
  * Expected counts of the histogram after keeping every read with probability 1/factor, BEFORE the
  * reference's randomised rounding (:71-74, host side): out[j-1] = sum_i counts_i * pmf_i(j) for
