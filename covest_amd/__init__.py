@@ -15,3 +15,5 @@ from . import poisson  # noqa: F401,E402
 from .poisson import truncated_poisson, truncated_poisson_many, truncated_poisson_table  # noqa: F401,E402
 from . import simulate  # noqa: F401,E402
 from .simulate import random_genome, simulate_reads, SimulatedReads  # noqa: F401,E402
+from .simulate import (repeat_plan, repeat_genome, repeat_genome_device, RepeatGenome, genome_spectrum,  # noqa: F401,E402
+                       spectrum_to_q)

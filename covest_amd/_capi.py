@@ -39,6 +39,7 @@ EXPORTS = (
     "covest_truncated_poisson", "covest_truncated_poisson_table",
     "covest_random_genome", "covest_random_genome_device", "covest_simulate_reads", "covest_simulate_reads_device",
     "covest_sample_reads", "covest_sample_reads_device",
+    "covest_repeat_plan", "covest_repeat_genome", "covest_repeat_genome_device",
 )
 
 
@@ -225,6 +226,12 @@ def lib():
     L.covest_sample_reads.argtypes = [i32, vp, vp, i64, i64, i64, ctypes.c_double, u64, vp, vp, vp, i64p, i64p]
     L.covest_sample_reads_device.restype = ctypes.c_int
     L.covest_sample_reads_device.argtypes = [i32, vp, vp, i64, i64, i64, ctypes.c_double, u64, vp, vp, vp, vp, vp]
+    L.covest_repeat_plan.restype = ctypes.c_int
+    L.covest_repeat_plan.argtypes = [i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, u64, i32, vp, i64p]
+    L.covest_repeat_genome.restype = ctypes.c_int
+    L.covest_repeat_genome.argtypes = [i32, vp, i64, i32, i64, ctypes.c_double, u64, vp]
+    L.covest_repeat_genome_device.restype = ctypes.c_int
+    L.covest_repeat_genome_device.argtypes = [i32, vp, i64, i32, i64, ctypes.c_double, u64, vp, vp]
     L.covest_grid_diag.restype = i64
     L.covest_grid_diag.argtypes = [vp, ctypes.POINTER(i64), i64]
     L.covest_grid_launch_record.restype = i64

@@ -9,6 +9,7 @@
 //   thin_host.cpp     covest_thin_histogram*
 //   abi_tp.cpp        covest_truncated_poisson, covest_truncated_poisson_table
 //   abi_sim.cpp       covest_random_genome*, covest_simulate_reads*
+//   abi_repeat.cpp    covest_repeat_plan, covest_repeat_genome*
 // ).  Nothing here is part of the C ABI (include/covest_amd.h).
 #pragma once
 #include <hip/hip_runtime.h>

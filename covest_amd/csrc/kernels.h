@@ -277,4 +277,12 @@ hipError_t launch_sim_reads(const unsigned char *genome, int64_t genome_len, int
                             int64_t n_reads, uint64_t thr, uint64_t seed, int both_strands, unsigned char *out,
                             int64_t *origin, hipStream_t stream);
 
+// ---- K-repeat: a genome whose units are copies of families (sim_repeats.hip) ----
+// out[n]: unit u = i / unit_len of the genome is family plan[u] >> 1, forward iff plan[u] & 1, substituted at
+// thr = floor(divergence * 2^32) (2^32 included; 0: no divergence block is computed).  plan[ceil(n / unit_len)] on the
+// device, entries >= 0 with (f + 1) * unit_len within 63 bits.  Any alignment of `out`; nothing outside it is written.
+// One launch per 4 GiB of output.
+hipError_t launch_repeat_genome(const int64_t *plan, int unit_len, int64_t n, uint64_t thr, uint64_t seed,
+                                unsigned char *out, hipStream_t stream);
+
 } // namespace covest

@@ -10,6 +10,14 @@ base index) through Philox4x32-10 (include/covest_amd.h), so a run is reproducib
 (`first_read`, `n_reads`) equals the same rows of the whole run.  The genome is a/c/g/t in either case: -s, the IUPAC
 substitution of :34-57, is not built.  The output is the layout KmerCounts.add_device and count_reads_device take.
 There is no CPU path: without the library or a HIP device every call raises CovestHipError.
+
+A random genome has no repeats; `repeat_genome` builds one whose k-mers have a prescribed copy-number distribution
+(DESIGN.md section 6n), and `genome_spectrum` / `spectrum_to_q` measure the truth of the repeat model's (q1, q2, q)
+from the genome itself:
+
+    rg = repeat_genome(300_000, 250, q1=0.7, q2=0.5, q=0.5, seed=1)
+    reads = simulate_reads(rg.bases, 100, coverage=20, error_rate=0.01, seed=1, both_strands=False)
+    q1, q2, q = spectrum_to_q(genome_spectrum(rg, 21))
 """
 import ctypes
 import math
@@ -175,3 +183,176 @@ def simulate_reads(genome, read_length, coverage=None, error_rate=0.0, seed=0, n
         int(device), g.ctypes.data, g.size, read_length, first_read, n, error_rate, seed, 1 if both_strands else 0,
         bases.ctypes.data, origin.ctypes.data), "covest_simulate_reads")
     return SimulatedReads(bases, origin, g.size, error_rate, seed, first_read)
+
+
+# ---- repeat-bearing genomes ---------------------------------------------------------------------
+MAX_COPIES_LIMIT = 1 << 20
+
+
+def _check_seed(seed):
+    if not (0 <= seed < 1 << 64):
+        raise ValueError("seed must fit 64 bits")
+
+
+def _check_plan_args(n_units, q1, q2, q, seed, max_copies):
+    """The argument rules of covest_repeat_plan, before the library is asked."""
+    if int(n_units) != n_units or n_units < 0:
+        raise ValueError("n_units must be an integer, not negative")
+    for name, v in (("q1", q1), ("q2", q2), ("q", q)):
+        if not (0.0 <= v <= 1.0):  # (NaN fails both)
+            raise ValueError("%s must be in [0, 1]" % name)
+    if int(max_copies) != max_copies or not (1 <= max_copies <= MAX_COPIES_LIMIT):
+        raise ValueError("max_copies must be in 1 .. 2^20")
+    _check_seed(seed)
+
+
+def _check_genome_args(n, unit_len, n_units, divergence, seed):
+    """The argument rules of covest_repeat_genome, before the library is asked."""
+    if int(unit_len) != unit_len or not (1 <= unit_len < 1 << 31):
+        raise ValueError("unit_len must be a positive integer that fits 31 bits")
+    if int(n) != n or n < 0:
+        raise ValueError("n must be an integer, not negative")
+    if n_units < 0 or n > n_units * int(unit_len):
+        raise ValueError("n is more than n_units * unit_len")
+    if not (0.0 <= divergence <= 1.0):
+        raise ValueError("divergence must be in [0, 1]")
+    _check_seed(seed)
+
+
+def repeat_plan(n_units, q1, q2, q, seed, max_copies=64, both_orientations=True):
+    """(plan, n_families): which family each of `n_units` units copies and which way round, `plan[u] = family << 1 |
+    forward` (int64).  Family f has o copies with the repeat model's probability b_o(q1, q2, q) (o = max_copies takes
+    the rest); the units are shuffled, and reverse-complemented at random unless both_orientations is False.  Host
+    arithmetic of the library (covest_repeat_plan): needs no device."""
+    q1, q2, q, seed = float(q1), float(q2), float(q), int(seed)
+    _check_plan_args(n_units, q1, q2, q, seed, max_copies)
+    n_units = int(n_units)
+    plan = np.empty(n_units, dtype=np.int64)
+    n_families = ctypes.c_int64(0)
+    _capi.check(_capi.lib().covest_repeat_plan(n_units, q1, q2, q, int(max_copies), seed, 1 if both_orientations else 0,
+                                               plan.ctypes.data, ctypes.byref(n_families)), "covest_repeat_plan")
+    return plan, int(n_families.value)
+
+
+class RepeatGenome:
+    """What repeat_genome returns: `bases` (n,) uint8 upper-case ASCII (simulate_reads takes it as it is), `plan`
+    (n_units,) int64 = family << 1 | forward, `unit_len`, `family_of_unit`, `forward`, and the settings that made it."""
+
+    def __init__(self, bases, plan, unit_len, divergence, seed):
+        self.bases = bases
+        self.plan = plan
+        self.unit_len = int(unit_len)
+        self.family_of_unit = plan >> 1
+        self.forward = (plan & 1).astype(bool)
+        self.divergence = float(divergence)
+        self.seed = int(seed)
+
+    def __len__(self):
+        return self.bases.size
+
+    @property
+    def n_units(self):
+        """Units the genome holds (the last may be cut): ceil(n / unit_len)."""
+        return -(-self.bases.size // self.unit_len)
+
+    def copies(self):
+        """{family id: copies of it among the genome's units} -- the copy numbers realised in the plan."""
+        ids, counts = np.unique(self.family_of_unit[:self.n_units], return_counts=True)
+        return dict(zip(ids.tolist(), counts.tolist()))
+
+
+def repeat_genome_device(plan_ptr, n_units, unit_len, n, out_ptr, divergence=0.0, seed=0, stream=None, device=-1):
+    """`n` bases into device memory at `out_ptr` (any alignment) from a plan of `n_units` int64 entries resident at
+    `plan_ptr` (raw device pointers); asynchronous on `stream`.  The plan is not looked at here: its entries must not be
+    negative, and (family + 1) * unit_len must fit 63 bits."""
+    _check_genome_args(n, unit_len, int(n_units), float(divergence), int(seed))
+    _capi.require_shared_runtime("repeat_genome_device")
+    _capi.check(_capi.lib().covest_repeat_genome_device(
+        int(device), ctypes.c_void_p(plan_ptr), int(n_units), int(unit_len), int(n), float(divergence), int(seed),
+        ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0)), "covest_repeat_genome_device")
+
+
+def repeat_genome(n, unit_len, q1=None, q2=None, q=None, seed=0, divergence=0.0, max_copies=64, both_orientations=True,
+                  plan=None, device=-1):
+    """A genome of `n` bases made of units of `unit_len` bases, each a copy of a family (forward or
+    reverse-complemented) with every base then substituted with probability `divergence`.  The plan is
+    repeat_plan(ceil(n / unit_len), q1, q2, q, seed, max_copies, both_orientations) unless `plan` is given (an int64
+    array of family << 1 | forward, at least ceil(n / unit_len) entries: a tandem array, one family everywhere, ...);
+    then q1, q2 and q are not used."""
+    seed, divergence = int(seed), float(divergence)
+    if plan is None:
+        if int(unit_len) != unit_len or unit_len < 1 or int(n) != n or n < 0:
+            raise ValueError("n must be a non-negative and unit_len a positive integer")
+        if q1 is None or q2 is None or q is None:
+            raise ValueError("give q1, q2 and q, or a plan")
+        _check_plan_args(-(-int(n) // int(unit_len)), float(q1), float(q2), float(q), seed, max_copies)
+        _check_genome_args(n, unit_len, -(-int(n) // int(unit_len)), divergence, seed)
+        plan, _ = repeat_plan(-(-int(n) // int(unit_len)), q1, q2, q, seed, max_copies, both_orientations)
+    else:
+        plan = np.ascontiguousarray(np.asarray(plan), dtype=np.int64)
+        if plan.ndim != 1:
+            raise ValueError("plan must be one-dimensional")
+        _check_genome_args(n, unit_len, plan.size, divergence, seed)
+        if plan.size and int(plan.min()) < 0:
+            raise ValueError("negative plan entry")
+        if plan.size and (int(plan.max()) >> 1) > ((1 << 63) - 1) // int(unit_len) - 1:
+            raise ValueError("family id times unit_len leaves 63 bits")
+    n, unit_len = int(n), int(unit_len)
+    out = np.empty(n, dtype=np.uint8)
+    _capi.check(_capi.lib().covest_repeat_genome(int(device), plan.ctypes.data, plan.size, unit_len, n, divergence, seed,
+                                                 out.ctypes.data), "covest_repeat_genome")
+    return RepeatGenome(out, plan, unit_len, divergence, seed)
+
+
+_SPECTRUM_WINDOW = 1 << 16  # k-mer starts a window of genome_spectrum holds
+
+
+def genome_spectrum(genome, k, canonical=False, device=-1):
+    """The genome's own copy-number spectrum {o: distinct k-mers occurring o times} (a k-mer and its reverse complement
+    taken together if `canonical`), counted on the device with KmerCounts.  The genome (a RepeatGenome, str, bytes or
+    uint8 array of a/c/g/t) is handed over as overlapping windows of up to 65 536 + k - 1 bases, a window a read, so
+    every k-mer start falls in exactly one window."""
+    from .kmer_hist import KmerCounts
+    g = genome.bases if isinstance(genome, RepeatGenome) else _genome_bytes(genome)
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    if g.size and not _VALID[g].all():
+        raise ValueError("genome byte outside acgtACGT")
+    n_starts = g.size - k + 1
+    if n_starts <= 0:
+        return {}
+    starts = np.arange(0, n_starts, _SPECTRUM_WINDOW, dtype=np.int64)
+    lens = np.minimum(_SPECTRUM_WINDOW, n_starts - starts) + (k - 1)  # every window holds a k-mer
+    offsets = np.zeros(starts.size + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    blob = np.concatenate([g[a:a + m] for a, m in zip(starts.tolist(), lens.tolist())])
+    counts = KmerCounts(k, canonical=canonical, device=device)
+    try:
+        counts.add_packed(blob.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                          offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), starts.size, blob.size)
+        hist = counts.histogram()
+    finally:
+        counts.close()
+    return {o: int(v) for o, v in enumerate(hist) if o > 0 and v > 0}
+
+
+def spectrum_to_q(spectrum):
+    """(q1, q2, q) of the repeat model that a copy-number spectrum {o: N_o} realises: q1 = N_1 / N, q2 = N_2 /
+    (N - N_1), q = N_{>=3} / sum_{o>=3} (o - 2) N_o -- the maximum-likelihood rate of the geometric tail b_o ~
+    q (1 - q)^(o - 3).  A component whose denominator is 0 is None."""
+    total = one = two = more = weight = 0
+    for o, v in spectrum.items():
+        o, v = int(o), int(v)
+        if o < 1 or v < 0:
+            raise ValueError("a spectrum maps copy numbers >= 1 to counts >= 0")
+        total += v
+        if o == 1:
+            one += v
+        elif o == 2:
+            two += v
+        else:
+            more += v
+            weight += (o - 2) * v
+    return (one / total if total else None, two / (total - one) if total - one else None,
+            more / weight if weight else None)

@@ -399,6 +399,48 @@ int covest_simulate_reads(int32_t device, const uint8_t *genome, int64_t genome_
                           int64_t first_read, int64_t n_reads, double error_rate, uint64_t seed,
                           int32_t both_strands, uint8_t *bases, int64_t *origin);
 
+/* ---- repeat-bearing genomes: a prescribed copy-number distribution of k-mers ----
+ * covest_random_genome draws every base on its own, so every k-mer of it is single-copy and the repeat model's
+ * (q1, q2, q) have no truth to find.  A REPEAT GENOME of n bases is n_units = ceil(n / unit_len) units of unit_len
+ * bases (the last may be cut), each a copy of one FAMILY, forward or reverse-complemented, then mutated away from it
+ * at rate `divergence`.  Philox4x32-10 as above, key = seed's low and high word; the last counter words 3 to 6 are
+ * this section's (0: reads, 1: genome, 2: sampler), so everything here is independent of those under one seed.
+ *   family base g (g = f * unit_len + offset, 64-bit): block (lo32(g>>2), hi32(g>>2), 0, 3), word g & 3,
+ *                  "ACGT"[word >> 30]
+ *   copy number of family f: u = word 0 of block (lo32(f), hi32(f), 0, 4); o_f = 1 + the number of o in
+ *                  1 .. max_copies - 1 with t_o <= u, t_o = min(2^32, floor(cdf_o * 2^32)).  The cdf is formed in
+ *                  double by basic IEEE operations only, in this order (no pow): cdf_1 = q1;
+ *                  cdf_2 = cdf_1 + (1 - q1) * q2; b = ((1 - q1) * (1 - q2)) * q; cdf_3 = cdf_2 + b; from there
+ *                  b = b * (1 - q), cdf_{o+1} = cdf_o + b.  This is RepeatsModel.get_b_o (covest/models.py:193-208)
+ *                  as a distribution; the mass the thresholds leave lands on max_copies.
+ *   unit list:     families 0, 1, 2, ... each repeated o_f times until n_units entries exist (the last family is cut
+ *                  to fit; *n_families = families in the list).  Entry j gets block (lo32(j), hi32(j), 0, 5) = w0..w3;
+ *                  the list is stably sorted by the 64-bit key w0 | w1 << 32, ties by j; the entry is forward iff
+ *                  w2 & 1 or both_orientations == 0.  plan[slot] = f << 1 | forward.
+ *   genome base i: u = i / unit_len, off = i % unit_len, (f, fwd) = plan[u].  Forward: the family base at
+ *                  f * unit_len + off.  Reverse: 3 - code of the family base at f * unit_len + unit_len - 1 - off.
+ *                  Then divergence: w = word i & 3 of block (lo32(i>>2), hi32(i>>2), 0, 6); the base is substituted
+ *                  iff w < floor(divergence * 2^32), by code (code + 1 + w % 3) & 3 -- the reads' rule.  At
+ *                  divergence 0 those blocks are not computed.
+ * A plan is plain data: a caller may hand-write one (a tandem array, one family everywhere, all distinct).
+ * covest_repeat_plan is host arithmetic and needs no device.  COVEST_E_INVALID: q1, q2 or q outside [0, 1] or NaN,
+ * max_copies outside 1 .. 2^20, n_units < 0, a NULL output with n_units > 0.  n_units == 0: COVEST_OK, *n_families = 0.
+ * COVEST_E_NOMEM: n_units beyond 2^40, or a unit list (16 bytes a unit while it is sorted) the host cannot hold.
+ * covest_repeat_genome*: COVEST_E_INVALID for unit_len < 1, n < 0, n > n_units * unit_len, divergence outside [0, 1]
+ * or NaN, a NULL buffer with n > 0, and -- host form only -- a negative plan entry or a family id whose bases leave 63
+ * bits ((f + 1) * unit_len > 2^63 - 1); with the device form both are the caller's duty.  The host form looks at all
+ * n_units entries of the plan, whatever n is (n == 0 included: a bad plan is refused before anything else), and copies
+ * to the device only the ceil(n / unit_len) entries the genome uses.  n == 0 otherwise: COVEST_OK, nothing
+ * launched.  The _device form takes DEVICE buffers (d_out of any alignment), is asynchronous on `stream` and writes
+ * nothing outside d_out[0 .. n); the other takes HOST buffers, copies and waits.  device < 0 = the calling thread's
+ * current device. */
+int covest_repeat_plan(int64_t n_units, double q1, double q2, double q, int32_t max_copies, uint64_t seed,
+                       int32_t both_orientations, int64_t *plan, int64_t *n_families);
+int covest_repeat_genome_device(int32_t device, const int64_t *d_plan, int64_t n_units, int32_t unit_len, int64_t n,
+                                double divergence, uint64_t seed, uint8_t *d_out, void *stream);
+int covest_repeat_genome(int32_t device, const int64_t *plan, int64_t n_units, int32_t unit_len, int64_t n,
+                         double divergence, uint64_t seed, uint8_t *out);
+
 /* ---- read sampler: covest/data.py:57-63 sample_reads, bin/read_sampler.py ----
  * Keeps every read with probability 1 / factor and writes the kept reads, IN INPUT ORDER, in the layout they came in:
  * the packed layout of covest_kmer_add_device (bases back to back at any alignment; offsets[n_reads + 1] ascending, or
