@@ -79,7 +79,7 @@ int covest_repeat_plan(int64_t n_units, double q1, double q2, double q, int32_t 
     }
     if (n_units > kMaxPlanUnits) // (before std::vector is asked: beyond its max_size it throws length_error, not bad_alloc)
         return fail(COVEST_E_NOMEM, "covest_repeat_plan: more than 2^40 units");
-    const uint32_t key0 = (uint32_t)seed, key1 = (uint32_t)(seed >> 32);
+    const PhiloxKey key = philox_key(seed);
     struct Entry {
         uint64_t key;
         int64_t rec; // family << 1 | forward
@@ -91,12 +91,12 @@ int covest_repeat_plan(int64_t n_units, double q1, double q2, double q, int32_t 
         uint64_t f = 0;
         while ((int64_t)list.size() < n_units) {
             uint32_t w[4];
-            philox4x32_10((uint32_t)f, (uint32_t)(f >> 32), 0u, 4u, key0, key1, w);
+            philox_block(f, 0u, kStreamCopies, key, w);
             // o_f = 1 + the number of thresholds <= u (they ascend: the cdf only grows)
             const int64_t copies = 1 + (std::upper_bound(t.begin(), t.end(), (uint64_t)w[0]) - t.begin());
             for (int64_t c = 0; c < copies && (int64_t)list.size() < n_units; ++c) {
                 const uint64_t j = (uint64_t)list.size();
-                philox4x32_10((uint32_t)j, (uint32_t)(j >> 32), 0u, 5u, key0, key1, w);
+                philox_block(j, 0u, kStreamShuffle, key, w);
                 const int64_t forward = (w[2] & 1u) | (both_orientations ? 0u : 1u);
                 list.push_back({(uint64_t)w[0] | ((uint64_t)w[1] << 32), (int64_t)(f << 1) | forward});
             }
@@ -117,19 +117,11 @@ int covest_repeat_genome_device(int32_t device, const int64_t *d_plan, int64_t n
                                 double divergence, uint64_t seed, uint8_t *d_out, void *stream)
 {
     uint64_t thr = 0;
-    const int rc = check_genome_args("covest_repeat_genome_device", d_plan, n_units, unit_len, n, divergence, d_out, &thr);
-    if (rc != COVEST_OK)
-        return rc;
+    COVEST_TRY(check_genome_args("covest_repeat_genome_device", d_plan, n_units, unit_len, n, divergence, d_out, &thr));
     if (n == 0)
         return COVEST_OK;
-    {
-        const int drc = resolve_device(device, "covest_repeat_genome_device", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-    DeviceGuard dev_guard(device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    DeviceCall call(device, "covest_repeat_genome_device");
+    COVEST_TRY(call.status());
     HIP_TRY(launch_repeat_genome(d_plan, unit_len, n, thr, seed, d_out, static_cast<hipStream_t>(stream)));
     return COVEST_OK;
 }
@@ -138,9 +130,7 @@ int covest_repeat_genome(int32_t device, const int64_t *plan, int64_t n_units, i
                          double divergence, uint64_t seed, uint8_t *out)
 {
     uint64_t thr = 0;
-    const int rc = check_genome_args("covest_repeat_genome", plan, n_units, unit_len, n, divergence, out, &thr);
-    if (rc != COVEST_OK)
-        return rc;
+    COVEST_TRY(check_genome_args("covest_repeat_genome", plan, n_units, unit_len, n, divergence, out, &thr));
     if (plan) {
         // the largest family id whose last base, (f + 1) * unit_len - 1, still fits 63 bits
         const int64_t f_max = std::numeric_limits<int64_t>::max() / unit_len - 1;
@@ -153,31 +143,13 @@ int covest_repeat_genome(int32_t device, const int64_t *plan, int64_t n_units, i
     }
     if (n == 0)
         return COVEST_OK;
-    {
-        const int drc = resolve_device(device, "covest_repeat_genome", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-    DeviceGuard dev_guard(device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    DeviceCall call(device, "covest_repeat_genome");
+    COVEST_TRY(call.status());
     const size_t n_used = (size_t)((n - 1) / unit_len + 1), plan_bytes = n_used * sizeof(int64_t); // the units the kernel reads
     DevBuf d_plan, d_out; // (go with the call, on every path; the last copy has waited for the kernel)
     HIP_TRY(d_plan.reserve(plan_bytes));
     HIP_TRY(d_out.reserve((size_t)n));
-    {
-        // the plan through the process's page-locked block, a piece at a time (as covest_simulate_reads stages the genome)
-        constexpr size_t kPiece = (size_t)8 << 20;
-        SharedStage &ss = shared_stage();
-        std::lock_guard<std::mutex> hold(ss.mu);
-        HIP_TRY(ss.buf.reserve(std::min<size_t>(plan_bytes, kPiece)));
-        const char *src = reinterpret_cast<const char *>(plan);
-        for (size_t at = 0; at < plan_bytes; at += kPiece) {
-            const size_t len = std::min<size_t>(plan_bytes - at, kPiece);
-            std::memcpy(ss.buf.ptr, src + at, len);
-            HIP_TRY(hipMemcpy(d_plan.as<char>() + at, ss.buf.ptr, len, hipMemcpyHostToDevice));
-        }
-    }
+    COVEST_TRY(stage_upload(d_plan.ptr, plan, plan_bytes, "covest_repeat_genome: upload of the plan"));
     HIP_TRY(launch_repeat_genome(d_plan.as<int64_t>(), unit_len, n, thr, seed, d_out.as<uint8_t>(), nullptr));
     HIP_TRY(hipMemcpy(out, d_out.ptr, (size_t)n, hipMemcpyDeviceToHost));
     return COVEST_OK;

@@ -102,20 +102,12 @@ int covest_sample_reads_device(int32_t device, const uint8_t *d_bases, const int
                                int64_t *d_out_offsets, int64_t *d_kept_index, int64_t *d_counts, void *stream)
 {
     uint64_t thr = 0;
-    const int rc = check_sample_args("covest_sample_reads_device", d_offsets, n_reads, read_len, first_read, factor,
-                                     d_out_offsets, &thr);
-    if (rc != COVEST_OK)
-        return rc;
+    COVEST_TRY(check_sample_args("covest_sample_reads_device", d_offsets, n_reads, read_len, first_read, factor,
+                                 d_out_offsets, &thr));
     if (!d_counts)
         return fail(COVEST_E_INVALID, "covest_sample_reads_device: d_counts is null");
-    {
-        const int drc = resolve_device(device, "covest_sample_reads_device", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-    DeviceGuard dev_guard(device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    DeviceCall call(device, "covest_sample_reads_device");
+    COVEST_TRY(call.status());
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_reads == 0) { // nothing launched: the counts, and the one output offset there is, by a memset on the stream
         HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), st));
@@ -124,9 +116,7 @@ int covest_sample_reads_device(int32_t device, const uint8_t *d_bases, const int
         return COVEST_OK;
     }
     SampleScratch *scratch = nullptr;
-    const int src = scratch_take(device, sample_scratch_bytes(n_reads), &scratch);
-    if (src != COVEST_OK)
-        return src;
+    COVEST_TRY(scratch_take(call.device(), sample_scratch_bytes(n_reads), &scratch));
     const hipError_t e = launch_sample_reads(d_bases, d_offsets, n_reads, read_len, first_read, thr, seed, d_out_bases,
                                              d_out_offsets, d_kept_index, d_counts, scratch->buf.ptr, st);
     scratch_give(scratch, st); // (whatever was launched before a failure still works on the block)
@@ -139,10 +129,7 @@ int covest_sample_reads(int32_t device, const uint8_t *bases, const int64_t *off
                         int64_t *kept_index, int64_t *n_kept, int64_t *bases_kept)
 {
     uint64_t thr = 0;
-    const int rc = check_sample_args("covest_sample_reads", offsets, n_reads, read_len, first_read, factor, out_offsets,
-                                     &thr);
-    if (rc != COVEST_OK)
-        return rc;
+    COVEST_TRY(check_sample_args("covest_sample_reads", offsets, n_reads, read_len, first_read, factor, out_offsets, &thr));
     if (!n_kept || !bases_kept)
         return fail(COVEST_E_INVALID, "covest_sample_reads: n_kept and bases_kept must not be null");
     if (offsets) {
@@ -161,14 +148,8 @@ int covest_sample_reads(int32_t device, const uint8_t *bases, const int64_t *off
             out_offsets[0] = 0;
         return COVEST_OK;
     }
-    {
-        const int drc = resolve_device(device, "covest_sample_reads", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-    DeviceGuard dev_guard(device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    DeviceCall call(device, "covest_sample_reads");
+    COVEST_TRY(call.status());
     const size_t n_bytes = (size_t)end_byte, index_bytes = (size_t)n_reads * sizeof(int64_t);
     // (go with the call, on every path; the copies back have waited for the kernels)
     DevBuf d_bases, d_offsets, d_out_bases, d_out_offsets, d_kept, d_counts, d_scratch;

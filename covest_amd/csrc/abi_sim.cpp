@@ -50,14 +50,8 @@ int covest_random_genome_device(int32_t device, int64_t n, uint64_t seed, uint8_
         return fail(COVEST_E_INVALID, "covest_random_genome_device: bad argument");
     if (n == 0)
         return COVEST_OK;
-    {
-        const int drc = resolve_device(device, "covest_random_genome_device", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-    DeviceGuard dev_guard(device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    DeviceCall call(device, "covest_random_genome_device");
+    COVEST_TRY(call.status());
     HIP_TRY(launch_random_genome(n, seed, d_out, static_cast<hipStream_t>(stream)));
     return COVEST_OK;
 }
@@ -67,20 +61,12 @@ int covest_simulate_reads_device(int32_t device, const uint8_t *d_genome, int64_
                                  int32_t both_strands, uint8_t *d_bases, int64_t *d_origin, void *stream)
 {
     uint64_t thr = 0;
-    const int rc = check_reads_args("covest_simulate_reads_device", d_genome, genome_len, read_len, first_read, n_reads,
-                                    error_rate, d_bases, &thr);
-    if (rc != COVEST_OK)
-        return rc;
+    COVEST_TRY(check_reads_args("covest_simulate_reads_device", d_genome, genome_len, read_len, first_read, n_reads,
+                                error_rate, d_bases, &thr));
     if (n_reads == 0)
         return COVEST_OK;
-    {
-        const int drc = resolve_device(device, "covest_simulate_reads_device", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-    DeviceGuard dev_guard(device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    DeviceCall call(device, "covest_simulate_reads_device");
+    COVEST_TRY(call.status());
     HIP_TRY(launch_sim_reads(d_genome, genome_len, read_len, first_read, n_reads, thr, seed, both_strands != 0, d_bases,
                              d_origin, static_cast<hipStream_t>(stream)));
     return COVEST_OK;
@@ -92,14 +78,8 @@ int covest_random_genome(int32_t device, int64_t n, uint64_t seed, uint8_t *out)
         return fail(COVEST_E_INVALID, "covest_random_genome: bad argument");
     if (n == 0)
         return COVEST_OK;
-    {
-        const int drc = resolve_device(device, "covest_random_genome", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-    DeviceGuard dev_guard(device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    DeviceCall call(device, "covest_random_genome");
+    COVEST_TRY(call.status());
     DevBuf d_out; // (goes with the call; hipMemcpy below has waited for the kernel by then)
     HIP_TRY(d_out.reserve((size_t)n));
     HIP_TRY(launch_random_genome(n, seed, d_out.as<uint8_t>(), nullptr));
@@ -112,43 +92,23 @@ int covest_simulate_reads(int32_t device, const uint8_t *genome, int64_t genome_
                           int64_t *origin)
 {
     uint64_t thr = 0;
-    const int rc = check_reads_args("covest_simulate_reads", genome, genome_len, read_len, first_read, n_reads, error_rate,
-                                    bases, &thr);
-    if (rc != COVEST_OK)
-        return rc;
+    COVEST_TRY(check_reads_args("covest_simulate_reads", genome, genome_len, read_len, first_read, n_reads, error_rate,
+                                bases, &thr));
     if (genome)
         for (int64_t i = 0; i < genome_len; ++i)
             if (!is_acgt(genome[i])) // (-s, the IUPAC substitution of read_simulator.py:34-57, is not built)
                 return fail(COVEST_E_INVALID, "covest_simulate_reads: genome byte outside acgtACGT at " + std::to_string(i));
     if (n_reads == 0)
         return COVEST_OK;
-    {
-        const int drc = resolve_device(device, "covest_simulate_reads", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-    DeviceGuard dev_guard(device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    DeviceCall call(device, "covest_simulate_reads");
+    COVEST_TRY(call.status());
     const size_t n_bytes = (size_t)n_reads * (size_t)read_len, origin_bytes = (size_t)n_reads * sizeof(int64_t);
     DevBuf d_genome, d_bases, d_origin; // (go with the call, on every path; the last copy has waited for the kernel)
     HIP_TRY(d_genome.reserve((size_t)genome_len));
     HIP_TRY(d_bases.reserve(n_bytes));
     if (origin)
         HIP_TRY(d_origin.reserve(origin_bytes));
-    {
-        // the genome through the process's page-locked block, a piece at a time: a pageable source is pinned or
-        // bounced by the runtime per copy (host.h HostBuf), and a genome may be larger than that block should grow
-        constexpr size_t kPiece = (size_t)8 << 20;
-        SharedStage &ss = shared_stage();
-        std::lock_guard<std::mutex> hold(ss.mu);
-        HIP_TRY(ss.buf.reserve(std::min<size_t>((size_t)genome_len, kPiece)));
-        for (size_t at = 0; at < (size_t)genome_len; at += kPiece) {
-            const size_t len = std::min<size_t>((size_t)genome_len - at, kPiece);
-            std::memcpy(ss.buf.ptr, genome + at, len);
-            HIP_TRY(hipMemcpy(d_genome.as<uint8_t>() + at, ss.buf.ptr, len, hipMemcpyHostToDevice));
-        }
-    }
+    COVEST_TRY(stage_upload(d_genome.ptr, genome, (size_t)genome_len, "covest_simulate_reads: upload of the genome"));
     HIP_TRY(launch_sim_reads(d_genome.as<uint8_t>(), genome_len, read_len, first_read, n_reads, thr, seed, both_strands != 0,
                              d_bases.as<uint8_t>(), origin ? d_origin.as<int64_t>() : nullptr, nullptr));
     HIP_TRY(hipMemcpy(bases, d_bases.ptr, n_bytes, hipMemcpyDeviceToHost));

@@ -58,14 +58,8 @@ int covest_truncated_poisson(int32_t device, int64_t n, const double *l, const i
     }
     if (n == 0)
         return COVEST_OK;
-    {
-        const int drc = resolve_device(device, "covest_truncated_poisson", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-    DeviceGuard dev_guard(device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    DeviceCall call(device, "covest_truncated_poisson");
+    COVEST_TRY(call.status());
     lgamma_ensure(j_max); // as a model does for its keys: one lock for the whole call
 
     const size_t in_bytes = (size_t)n * 4 * sizeof(double), out_bytes = (size_t)n * sizeof(double);
@@ -106,20 +100,12 @@ int covest_truncated_poisson_table(int32_t device, int64_t n_l, const double *l,
         return fail(COVEST_E_INVALID, "covest_truncated_poisson_table: more than 2^30 rates in one call");
     if (n_l == 0 || n_j == 0)
         return COVEST_OK;
-    {
-        const int drc = resolve_device(device, "covest_truncated_poisson_table", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-    DeviceGuard dev_guard(device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    DeviceCall call(device, "covest_truncated_poisson_table");
+    COVEST_TRY(call.status());
 
     covest_model tmp; // (owns the tile table's device buffer; goes with the call)
-    tmp.device = device;
-    const int rc = tiles_over_keys(tmp, n_j, j);
-    if (rc != COVEST_OK)
-        return rc;
+    tmp.device = call.device();
+    COVEST_TRY(tiles_over_keys(tmp, n_j, j));
     const size_t l_bytes = (size_t)n_l * sizeof(double), out_bytes = (size_t)n_l * (size_t)n_j * sizeof(double);
     DevBuf d_l, d_out;
     HIP_TRY(d_l.reserve(l_bytes));

@@ -23,6 +23,7 @@
 #include <limits>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -43,6 +44,13 @@ int fail_hip(hipError_t e, const char *what);
         hipError_t e__ = (expr);                     \
         if (e__ != hipSuccess)                       \
             return fail_hip(e__, #expr);             \
+    } while (0)
+// ... and of a call of the library's own that returns a status code (and has set the message)
+#define COVEST_TRY(expr)                             \
+    do {                                             \
+        const int rc__ = (expr);                     \
+        if (rc__ != COVEST_OK)                       \
+            return rc__;                             \
     } while (0)
 
 // Small device buffers that a handle lets go are KEPT for the next handle of the process (round 4): hipMalloc costs
@@ -209,6 +217,27 @@ class DeviceGuard {
 
 
 int resolve_device(int device, const char *who, int *out);
+
+// The opening of an entry point that has no handle: `device` resolved (resolve_device) and made current for the call.
+// It goes after the argument checks and the early returns for empty work: nothing computed, no device needed.
+class DeviceCall {
+  public:
+    DeviceCall(int device, const char *who) : status_(resolve_device(device, who, &device_))
+    {
+        if (status_ == COVEST_OK)
+            status_ = guard_.emplace(device_).status();
+    }
+    int status() const { return status_; }
+    int device() const { return device_; }
+
+  private:
+    int device_ = -1, status_;
+    std::optional<DeviceGuard> guard_;
+};
+
+// `bytes` of pageable host memory to the device through shared_stage(), 8 MiB at a time under its mutex (a genome may
+// be larger than that block should grow).  `what` names the upload in the message of a failure.
+int stage_upload(void *d_dst, const void *src, size_t bytes, const char *what);
 
 } // namespace covest
 

@@ -141,6 +141,20 @@ SharedStage &shared_stage()
     return *s;
 }
 
+int stage_upload(void *d_dst, const void *src, size_t bytes, const char *what)
+{
+    constexpr size_t kPiece = (size_t)8 << 20;
+    SharedStage &ss = shared_stage();
+    std::lock_guard<std::mutex> hold(ss.mu);
+    hipError_t e = ss.buf.reserve(std::min(bytes, kPiece));
+    for (size_t at = 0; e == hipSuccess && at < bytes; at += kPiece) {
+        const size_t len = std::min(bytes - at, kPiece);
+        std::memcpy(ss.buf.ptr, static_cast<const char *>(src) + at, len);
+        e = hipMemcpy(static_cast<char *>(d_dst) + at, ss.buf.ptr, len, hipMemcpyHostToDevice);
+    }
+    return e == hipSuccess ? COVEST_OK : fail_hip(e, what);
+}
+
 
 // RepeatsModel.get_b_o / get_hist_threshold, covest/models.py:185-208, with libm
 // pow as CPython's float ** int.  b_o is non-increasing in o for o >= 3 when

@@ -543,14 +543,8 @@ int covest_kmer_scatter_rate(int32_t device, int64_t slots, int64_t ops, double 
 {
     if (slots < 1 || ops < 1 || !ops_per_s)
         return fail(COVEST_E_INVALID, "covest_kmer_scatter_rate: bad argument");
-    {
-        const int drc = resolve_device(device, "covest_kmer_scatter_rate", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-    DeviceGuard dev_guard(device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    DeviceCall call(device, "covest_kmer_scatter_rate");
+    COVEST_TRY(call.status());
     DevBuf words;
     HIP_TRY(words.reserve(((size_t)slots + 1) * sizeof(unsigned long long)));
     hipEvent_t a = nullptr, b = nullptr;

@@ -13,8 +13,8 @@
 //   3. sample_place   a lane a read again: the flag recomputed (a Philox block is cheaper than a stored flag read back),
 //                     a scan within the workgroup; a kept read writes, at its rank, its output offset, its global index
 //                     and its SOURCE offset (scratch: the gather never reads d_offsets)
-//   4. sample_gather  the hot path.  The output is cut into tiles of kTile bytes, 16-byte aligned IN MEMORY; a fixed
-//                     number of workgroups each walks a contiguous share of them (the tile count is known on the device
+//   4. sample_gather  the hot path.  The output goes through the tile image (tile_image.h); a fixed number of
+//                     workgroups each walks a contiguous share of the tiles (their count is known on the device
 //                     only).  A workgroup finds the kept read that holds its first byte by a 256-way search of the output
 //                     offsets (once: from tile to tile the place is carried), loads the offsets of the kept reads that
 //                     touch the tile into LDS, kBatch at a time (a run of empty reads is only more batches), and
@@ -22,8 +22,7 @@
 //                     search in the LDS table; a dword that lies within one read is two aligned source dwords (one
 //                     where the source is aligned too) funnel-shifted into one aligned LDS store; a dword that straddles
 //                     reads, or the ends of the output, is assembled byte by byte from aligned source dwords -- byte
-//                     stores happen in LDS.  The image goes out with one 16-byte store a lane; only a lane whose 16
-//                     bytes hang over either end of the caller's buffer stores bytes.
+//                     stores happen in LDS.
 // An aligned source dword is loaded only when it holds a byte that is wanted, so no load leaves the 4-byte granule of
 // a byte of the caller's buffer.  Nothing is written outside d_out_bases[0 .. bases_kept), d_out_offsets[0 .. n_kept],
 // d_kept_index[0 .. n_kept), d_counts[0 .. 2) and the library's scratch.
@@ -33,6 +32,7 @@
 
 #include "sample.h"
 #include "sim_philox.h"
+#include "tile_image.h"
 
 namespace covest {
 
@@ -42,14 +42,14 @@ constexpr int kThreads = kSampleShare;          // reads a workgroup of stages 1
 constexpr int kWaves = kThreads / 64;
 constexpr int kScanThreads = 1024;
 constexpr int kScanPerLane = 4;                 // pairs a lane of the scan takes per round
-constexpr int kTile = 16 * kThreads;            // bytes of output a workgroup assembles at a time
+static_assert(kThreads == kImageThreads, "the gather's workgroup is the tile image's");
 constexpr int kBatch = kThreads;                // kept reads whose offsets the workgroup holds in LDS at a time
 constexpr int64_t kBlocksPerLaunch = (int64_t)1 << 22; // 2^30 threads a launch (HIP wraps grids beyond 2^32 threads)
 
 __device__ __forceinline__ bool kept(unsigned long long r, unsigned long long thr, uint32_t key0, uint32_t key1)
 {
     uint32_t w[4];
-    philox4x32_10((uint32_t)r, (uint32_t)(r >> 32), 0u, 2u, key0, key1, w);
+    philox_block(r, 0u, kStreamKeep, PhiloxKey{key0, key1}, w);
     return (unsigned long long)w[0] < thr;
 }
 
@@ -227,15 +227,15 @@ __global__ __launch_bounds__(kThreads) void sample_gather_kernel(
     const unsigned char *__restrict__ src, const long long *__restrict__ counts, const long long *__restrict__ out_off,
     const long long read_len, const long long *__restrict__ src_off, unsigned char *__restrict__ out, const int lead)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char image[kTile];
-    __shared__ int rel[kBatch + 1];       // output offset of the batch's reads less the tile's, kept within [0, kTile + 1]
+    __shared__ __attribute__((aligned(16))) unsigned char image[kImageTile];
+    __shared__ int rel[kBatch + 1];       // output offset of the batch's reads less the tile's, kept within [0, kImageTile + 1]
     __shared__ long long delta[kBatch];   // source offset less output offset
 
     const int tid = threadIdx.x;
     const long long n_kept = counts[0], total = counts[1];
     if (total <= 0)
         return;
-    const long long n_tiles = (total + lead + kTile - 1) / kTile;
+    const long long n_tiles = image_tiles(total, lead);
     const long long share = (n_tiles + gridDim.x - 1) / gridDim.x;
     const long long tile_lo = (long long)blockIdx.x * share;
     const long long tile_hi = tile_lo + share < n_tiles ? tile_lo + share : n_tiles;
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(kThreads) void sample_gather_kernel(
     // the last rank whose output offset is not beyond the share's first byte: rank 0 has offset 0
     long long r0;
     {
-        const long long target = tile_lo * kTile - lead > 0 ? tile_lo * kTile - lead : 0;
+        const long long target = tile_span(tile_lo, lead, total).o_begin;
         if (!out_off) {
             r0 = target / read_len;
         } else {
@@ -265,10 +265,10 @@ __global__ __launch_bounds__(kThreads) void sample_gather_kernel(
     }
 
     for (long long tile = tile_lo; tile < tile_hi; ++tile) {
-        // the tile in output bytes: [t_begin, t_begin + kTile), of which [o_begin, o_end) are the caller's
-        const long long t_begin = tile * kTile - lead;
-        const int e_begin = t_begin < 0 ? (int)-t_begin : 0;
-        const int e_end = t_begin + kTile < total ? kTile : (int)(total - t_begin);
+        // the caller's part of the tile, in the image's coordinates: [e_begin, e_end)
+        const TileSpan span = tile_span(tile, lead, total);
+        const long long t_begin = span.t_begin;
+        const int e_begin = (int)(span.o_begin - t_begin), e_end = (int)(span.o_end - t_begin);
         long long rb0 = r0;
         int cnt;
         for (;;) {
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(kThreads) void sample_gather_kernel(
             for (int i = tid; i <= cnt; i += kThreads) {
                 const long long o = rb0 + i < n_kept ? off_of(out_off, read_len, rb0 + i) : total;
                 const long long d = o - t_begin;
-                rel[i] = d < 0 ? 0 : d > kTile + 1 ? kTile + 1 : (int)d;
+                rel[i] = d < 0 ? 0 : d > kImageTile + 1 ? kImageTile + 1 : (int)d;
                 if (i < cnt)
                     delta[i] = src_off[rb0 + i] - o;
             }
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(kThreads) void sample_gather_kernel(
             const int p_lo = rel[0] > e_begin ? rel[0] : e_begin; // the batch's share of the image: [p_lo, p_hi)
             const int p_hi = rel[cnt] < e_end ? rel[cnt] : e_end;
 #pragma unroll
-            for (int k = 0; k < kTile / (4 * kThreads); ++k) {
+            for (int k = 0; k < kImageTile / (4 * kThreads); ++k) {
                 const int p = 4 * (tid + kThreads * k);
                 if (p + 4 <= p_lo || p >= p_hi)
                     continue;
@@ -338,14 +338,7 @@ __global__ __launch_bounds__(kThreads) void sample_gather_kernel(
         }
         __syncthreads(); // the image is whole; the table is free
 
-        const int q = 16 * tid;
-        if (q >= e_begin && q + 16 <= e_end) {
-            *reinterpret_cast<uint4 *>(out + (t_begin + q)) = *reinterpret_cast<const uint4 *>(image + q);
-        } else {
-            for (int b = 0; b < 16; ++b)
-                if (q + b >= e_begin && q + b < e_end)
-                    out[t_begin + q + b] = image[q + b];
-        }
+        store_image(out, image, span, tid);
     }
 }
 
@@ -367,7 +360,7 @@ hipError_t launch_sample_reads(const unsigned char *bases, const int64_t *offset
     const int64_t n_blocks = (n_reads + kThreads - 1) / kThreads;
     long long *pairs = static_cast<long long *>(scratch), *src_off = pairs + 2 * n_blocks;
     const long long *offs = reinterpret_cast<const long long *>(offsets);
-    const uint32_t key0 = (uint32_t)seed, key1 = (uint32_t)(seed >> 32);
+    const uint32_t key0 = philox_key(seed).k0, key1 = philox_key(seed).k1;
     for (int64_t b0 = 0; b0 < n_blocks; b0 += kBlocksPerLaunch) {
         const dim3 grid((unsigned)std::min(n_blocks - b0, kBlocksPerLaunch));
         hipLaunchKernelGGL(sample_flags_kernel, grid, dim3(kThreads), 0, stream, offs, (long long)read_len, (long long)n_reads,
@@ -396,8 +389,8 @@ hipError_t launch_sample_reads(const unsigned char *bases, const int64_t *offset
     // itself, the upper bound, has fewer tiles)
     int64_t n_groups = kSampleGatherGroups;
     if (!offsets)
-        n_groups = std::min<int64_t>(n_groups, (n_reads * read_len + 15 + kTile - 1) / kTile);
-    const int lead = (int)((uintptr_t)out_bases & 15u);
+        n_groups = std::min<int64_t>(n_groups, image_tiles(n_reads * read_len, 15));
+    const int lead = image_lead(out_bases);
     hipLaunchKernelGGL(sample_gather_kernel, dim3((unsigned)n_groups), dim3(kThreads), 0, stream, bases,
                        reinterpret_cast<const long long *>(counts), offsets ? reinterpret_cast<const long long *>(out_offsets) : nullptr,
                        (long long)read_len, src_off, out_bases, lead);

@@ -1,6 +1,7 @@
-// sim_philox.h -- the random stream of the read simulator (sim_reads.hip): Philox4x32-10 as in
-// Random123 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC 2011).  Plain C++ for
-// device and host: the known answers are checked on the host too.
+// sim_philox.h -- the random stream and the base code of the generators (sim_reads.hip, sample_reads.hip,
+// sim_repeats.hip, abi_repeat.cpp): Philox4x32-10 as in Random123 (Salmon, Moraes, Dror, Shaw:
+// "Parallel random numbers: as easy as 1, 2, 3", SC 2011), the table of its streams, and A, C, G, T = 0, 1, 2, 3.
+// Plain C++ for device and host: the known answers are checked on the host too (tests/tile_image_check.cpp).
 #pragma once
 #include <cstdint>
 
@@ -42,6 +43,52 @@ COVEST_HD uint32_t mod3(uint32_t w)
 {
     const uint32_t d = (uint32_t)__builtin_popcount(w & 0x55555555u) + 2u * (uint32_t)__builtin_popcount(w & 0xAAAAAAAAu);
     return d - 3u * ((d * 171u) >> 9);
+}
+
+// THE STREAMS.  A block's counter is (lo32(index), hi32(index), c2, stream) and its key (lo32(seed), hi32(seed)): the
+// code-side twin of the table in include/covest_amd.h, which the numpy restatements under tests/ check.
+//   stream      index             c2                            words used
+//   read        read r            0: the header                 w0 | w1 << 32 the position, w2 & 1 the strand
+//                                 1 + j: bases 4j .. 4j + 3     one a base: substituted()
+//   genome      base i >> 2       0                             one a base: "ACGT"[w >> 30]
+//   keep        read r            0                             w0 < thr: the sampler keeps the read
+//   family      family base g>>2  0                             one a base: "ACGT"[w >> 30]
+//   copies      family f          0                             w0 against the copy-number thresholds
+//   shuffle     unit-list entry j 0                             w0 | w1 << 32 the sort key, w2 & 1 the orientation
+//   divergence  genome base i>>2  0                             one a base: substituted()
+// A new generator takes the next free number (and a row here and in the header); c2 is free in all but `read`.
+constexpr uint32_t kStreamRead = 0, kStreamGenome = 1, kStreamKeep = 2, kStreamFamily = 3, kStreamCopies = 4,
+                   kStreamShuffle = 5, kStreamDivergence = 6;
+
+struct PhiloxKey { uint32_t k0, k1; };
+COVEST_HD PhiloxKey philox_key(uint64_t seed) { return PhiloxKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
+COVEST_HD void philox_block(uint64_t index, uint32_t c2, uint32_t stream, PhiloxKey key, uint32_t out[4])
+{
+    philox4x32_10((uint32_t)index, (uint32_t)(index >> 32), c2, stream, key.k0, key.k1, out);
+}
+
+// THE BASE CODE.  A, C, G, T = 0, 1, 2, 3, the complement of c is 3 - c.  ASCII a/c/g/t in either case: (byte >> 1) & 3
+// gives 0, 1, 3, 2, and the Gray step puts G and T in order.  Any other byte gives SOME code: nothing is indexed by it.
+constexpr uint32_t kAcgt = 0x54474341u; // "ACGT", code 0 in the low byte
+COVEST_HD uint32_t code_of(uint32_t byte)
+{
+    const uint32_t c = (byte >> 1) & 3u;
+    return c ^ (c >> 1);
+}
+
+COVEST_HD uint32_t char_of(uint32_t code) { return (kAcgt >> (8 * code)) & 0xffu; }
+// the characters of four codes, the first in the low byte
+COVEST_HD uint32_t pack_chars(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3)
+{
+    return char_of(c0) | (char_of(c1) << 8) | (char_of(c2) << 16) | (char_of(c3) << 24);
+}
+
+// The substitution rule of reads and of divergence: the base changes iff its word w is below thr = floor(rate * 2^32),
+// to one of the three others -- which, w % 3 says (other() of the reference's read_simulator.py:16-20).
+COVEST_HD uint32_t other_base(uint32_t code, uint32_t w) { return (code + 1u + mod3(w)) & 3u; }
+COVEST_HD uint32_t substituted(uint32_t code, uint32_t w, uint64_t thr)
+{
+    return (uint64_t)w < thr ? other_base(code, w) : code;
 }
 
 } // namespace covest

@@ -20,14 +20,8 @@ static int thin_histogram_impl(int32_t device, int64_t n, const int32_t *keys, c
         *kernel_ms = 0.0;
     if (out_len == 0)
         return COVEST_OK;
-    {
-        const int drc = resolve_device(device, "covest_thin_histogram", &device);
-        if (drc != COVEST_OK)
-            return drc;
-    }
-    DeviceGuard dev_guard(device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    DeviceCall call(device, "covest_thin_histogram");
+    COVEST_TRY(call.status());
     const int64_t top = std::max<int64_t>(max_key, out_len);
     std::vector<double> lgam((size_t)top + 1);
     for (int64_t v = 0; v <= top; ++v)

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _capi
 from .kmer_hist import NS_IGNORE, KmerCounts, ReadBatches
-from .simulate import SimulatedReads
+from .simulate import SimulatedReads, _check_seed
 
 
 def _check(factor, seed, first_read):
@@ -32,8 +32,7 @@ def _check(factor, seed, first_read):
         raise ValueError("factor must be a number")
     if not (factor >= 1.0) or not math.isfinite(factor):  # (NaN fails the first)
         raise ValueError("factor must be a finite number, at least 1")
-    if int(seed) != seed or not (0 <= seed < 1 << 64):
-        raise ValueError("seed must fit 64 bits")
+    _check_seed(seed, whole=True)
     if int(first_read) != first_read or first_read < 0:
         raise ValueError("first_read must not be negative")
     return factor, int(seed), int(first_read)

@@ -46,6 +46,12 @@ def _genome_bytes(genome):
     return np.ascontiguousarray(a)
 
 
+def _check_seed(seed, whole=False):
+    """A seed is the 64-bit key of the stream; `whole`: a number that is no integer is refused too, not truncated."""
+    if (whole and int(seed) != seed) or not (0 <= seed < 1 << 64):
+        raise ValueError("seed must fit 64 bits")
+
+
 def _check(read_length, genome_len, n_reads, first_read, error_rate, seed):
     """The argument rules of covest_simulate_reads, before the library is asked (ValueError, as the models' arguments)."""
     if int(read_length) != read_length or read_length < 1:
@@ -56,8 +62,7 @@ def _check(read_length, genome_len, n_reads, first_read, error_rate, seed):
         raise ValueError("n_reads and first_read must not be negative")
     if not (0.0 <= error_rate <= 1.0):  # (NaN fails both)
         raise ValueError("error_rate must be in [0, 1]")
-    if not (0 <= seed < 1 << 64):
-        raise ValueError("seed must fit 64 bits")
+    _check_seed(seed)
 
 
 def _n_reads(coverage, genome_len, read_length, n_reads):
@@ -75,8 +80,7 @@ def random_genome(n, seed, device=-1):
     n, seed = int(n), int(seed)
     if n < 0:
         raise ValueError("n must not be negative")
-    if not (0 <= seed < 1 << 64):
-        raise ValueError("seed must fit 64 bits")
+    _check_seed(seed)
     out = np.empty(n, dtype=np.uint8)
     _capi.check(_capi.lib().covest_random_genome(int(device), n, seed, out.ctypes.data), "covest_random_genome")
     return out
@@ -187,11 +191,6 @@ def simulate_reads(genome, read_length, coverage=None, error_rate=0.0, seed=0, n
 
 # ---- repeat-bearing genomes ---------------------------------------------------------------------
 MAX_COPIES_LIMIT = 1 << 20
-
-
-def _check_seed(seed):
-    if not (0 <= seed < 1 << 64):
-        raise ValueError("seed must fit 64 bits")
 
 
 def _check_plan_args(n_units, q1, q2, q, seed, max_copies):

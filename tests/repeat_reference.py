@@ -17,14 +17,6 @@ import numpy as np
 
 import sim_reference as sr
 
-MASK = np.uint64(sr.MASK)
-S32 = np.uint64(32)
-
-
-def _split(x):
-    x = np.asarray(x, dtype=np.uint64)
-    return x & MASK, x >> S32
-
 
 def thresholds(q1, q2, q, max_copies):
     """[t_1 .. t_{max_copies - 1}] as Python integers."""
@@ -45,7 +37,7 @@ def thresholds(q1, q2, q, max_copies):
 
 def copy_numbers(first, count, q1, q2, q, max_copies, seed):
     """o_f of families first .. first + count (an int64 array)."""
-    lo, hi = _split(np.arange(first, first + count, dtype=np.uint64))
+    lo, hi = sr.split64(np.arange(first, first + count, dtype=np.uint64))
     u = sr.philox(lo, hi, 0, 4, *sr._key(seed))[0]
     t = np.array(thresholds(q1, q2, q, max_copies), dtype=np.uint64)
     return 1 + np.searchsorted(t, u, side="right").astype(np.int64)  # t ascends: the number of t_o <= u
@@ -66,9 +58,9 @@ def plan(n_units, q1, q2, q, seed, max_copies=64, both_orientations=True):
         first += o.size
     family = np.concatenate(fams)[:n_units]
     n_families = int(family[-1]) + 1
-    lo, hi = _split(np.arange(n_units, dtype=np.uint64))
+    lo, hi = sr.split64(np.arange(n_units, dtype=np.uint64))
     w0, w1, w2, _ = sr.philox(lo, hi, 0, 5, *sr._key(seed))
-    order = np.argsort(w0 | (w1 << S32), kind="stable")
+    order = np.argsort(w0 | (w1 << np.uint64(32)), kind="stable")
     forward = (w2 & np.uint64(1)).astype(np.int64) if both_orientations else np.ones(n_units, dtype=np.int64)
     return (family[order] << 1) | forward[order], n_families
 
@@ -76,7 +68,7 @@ def plan(n_units, q1, q2, q, seed, max_copies=64, both_orientations=True):
 def family_codes(g, seed):
     """Codes 0..3 of the family bases at the 64-bit places g (Python integers or an object/uint64 array)."""
     g = np.asarray(g, dtype=np.uint64)
-    lo, hi = _split(g >> np.uint64(2))
+    lo, hi = sr.split64(g >> np.uint64(2))
     out = sr.philox(lo, hi, 0, 3, *sr._key(seed))
     return (sr._words(out, g & np.uint64(3)) >> np.uint64(30)).astype(np.int64)
 
@@ -96,7 +88,7 @@ def genome_parts(plan_, unit_len, n, divergence, seed):
     hit = np.zeros(n, dtype=bool)
     out = code
     if thr:
-        lo, hi = _split(i.astype(np.uint64) >> np.uint64(2))
+        lo, hi = sr.split64(i.astype(np.uint64) >> np.uint64(2))
         w = sr._words(sr.philox(lo, hi, 0, 6, *sr._key(seed)), i & 3)
         hit = w < np.uint64(thr)
         out = np.where(hit, (code + 1 + (w % np.uint64(3)).astype(np.int64)) & 3, code)

@@ -26,8 +26,7 @@ def counter(r):
 def words(first_read, n, seed):
     """Word 0 of reads first_read .. first_read + n (uint64 array holding 32-bit words)."""
     r = [int(first_read) + i for i in range(int(n))]
-    lo = np.array([x & sr.MASK for x in r], dtype=np.uint64)
-    hi = np.array([x >> 32 for x in r], dtype=np.uint64)
+    lo, hi = sr.split64(r)
     return sr.philox(lo, hi, 0, 2, int(seed) & sr.MASK, int(seed) >> 32)[0]
 
 

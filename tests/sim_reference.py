@@ -50,6 +50,12 @@ def _key(seed):
     return seed & MASK, seed >> 32
 
 
+def split64(x):
+    """(lo32, hi32) of 64-bit indices (Python integers, a list of them or an array): two uint64 arrays."""
+    x = np.asarray(x, dtype=np.uint64)
+    return x & np.uint64(MASK), x >> np.uint64(32)
+
+
 def _words(blocks, word):
     """Pick out[word] per element from the four arrays of philox()."""
     return np.choose(np.asarray(word, dtype=np.intp), blocks)
@@ -57,8 +63,7 @@ def _words(blocks, word):
 
 def random_genome(n, seed):
     i = np.arange(int(n), dtype=np.uint64)
-    blk = i >> np.uint64(2)
-    out = philox(blk & np.uint64(MASK), blk >> np.uint64(32), 0, 1, *_key(seed))
+    out = philox(*split64(i >> np.uint64(2)), 0, 1, *_key(seed))
     w = _words(out, (i & np.uint64(3)))
     return ACGT[(w >> np.uint64(30)).astype(np.intp)]
 
@@ -66,8 +71,7 @@ def random_genome(n, seed):
 def headers(genome_len, read_len, first_read, n_reads, seed, both_strands=True):
     """(pos, forward) of reads first_read .. first_read + n_reads: int64 and bool arrays."""
     r = [int(first_read) + i for i in range(int(n_reads))]
-    lo = np.array([x & MASK for x in r], dtype=np.uint64)
-    hi = np.array([x >> 32 for x in r], dtype=np.uint64)
+    lo, hi = split64(r)
     w0, w1, w2, _ = philox(lo, hi, 0, 0, *_key(seed))
     span = int(genome_len) - int(read_len)
     pos = np.array([((int(a) | (int(b) << 32)) * span) >> 64 for a, b in zip(w0, w1)], dtype=np.int64)
