@@ -40,6 +40,7 @@ EXPORTS = (
     "covest_random_genome", "covest_random_genome_device", "covest_simulate_reads", "covest_simulate_reads_device",
     "covest_sample_reads", "covest_sample_reads_device",
     "covest_repeat_plan", "covest_repeat_genome", "covest_repeat_genome_device",
+    "covest_draw_thresholds", "covest_draw_histograms", "covest_draw_histograms_device",
 )
 
 
@@ -232,6 +233,12 @@ def lib():
     L.covest_repeat_genome.argtypes = [i32, vp, i64, i32, i64, ctypes.c_double, u64, vp]
     L.covest_repeat_genome_device.restype = ctypes.c_int
     L.covest_repeat_genome_device.argtypes = [i32, vp, i64, i32, i64, ctypes.c_double, u64, vp, vp]
+    L.covest_draw_thresholds.restype = ctypes.c_int
+    L.covest_draw_thresholds.argtypes = [i64, vp, vp]
+    L.covest_draw_histograms.restype = ctypes.c_int
+    L.covest_draw_histograms.argtypes = [i32, i64, vp, i64, i64, i64, u64, vp]
+    L.covest_draw_histograms_device.restype = ctypes.c_int
+    L.covest_draw_histograms_device.argtypes = [i32, i64, vp, i64, i64, i64, u64, vp, vp]
     L.covest_grid_diag.restype = i64
     L.covest_grid_diag.argtypes = [vp, ctypes.POINTER(i64), i64]
     L.covest_grid_launch_record.restype = i64

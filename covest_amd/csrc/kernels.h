@@ -285,4 +285,17 @@ hipError_t launch_sim_reads(const unsigned char *genome, int64_t genome_len, int
 hipError_t launch_repeat_genome(const int64_t *plan, int unit_len, int64_t n, uint64_t thr, uint64_t seed,
                                 unsigned char *out, hipStream_t stream);
 
+// ---- K-draw: replicate histograms drawn from a weight vector (draw_hist.hip) ----
+// out[n_rep * m] (int64, overwritten: zeroed on `stream` first): row b - first_rep counts the draws d < n of replicate
+// b by cell, the cell of a draw being #{i <= m - 2 : thr[i] <= u} (include/covest_amd.h).  thr[m] ascending, on the
+// device.  1 <= m <= kDrawMaxCells, first_rep + n_rep <= 2^32; nothing outside out[0 .. n_rep * m) is written.
+constexpr int kDrawMaxCells = 65536;      // the cap on m (COVEST_DRAW_MAX_CELLS of the header)
+constexpr int kDrawLdsBothCells = 12288;  // up to here thresholds AND counters live in LDS (12 bytes a cell)
+constexpr int kDrawLdsThrCells = 16384;   // up to here the thresholds do; beyond, they are read through L2
+constexpr int kDrawGuideBits = 11;        // the guide table is indexed by the top 11 bits of a 63-bit draw
+constexpr int kDrawGuide = 1 << kDrawGuideBits;
+constexpr long long kDrawChunk = 1 << 17; // draws a workgroup takes
+hipError_t launch_draw_hist(const uint64_t *thr, int64_t m, int64_t n, uint64_t first_rep, int64_t n_rep, uint64_t seed,
+                            int64_t *out, hipStream_t stream);
+
 } // namespace covest

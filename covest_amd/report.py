@@ -26,7 +26,7 @@ def _finite_int(x):
 
 def print_output(hist_orig, model, success, sample_factor, estimated=None, guess=None, orig=None,
                  reads_size=None, silent=False, orig_sample_factor=1, starting_points=1,
-                 use_grid_search=False, intervals=None, information=None):
+                 use_grid_search=False, intervals=None, information=None, bootstrap=None):
     """`intervals`: the dict covest_amd.profile.coverage_interval returns; the record then carries the likelihood-ratio
     interval of the coverage, of the genome size and its level.  Without it the record is the reference's, key for key.
     `information`: the dict covest_amd.information.observed_information returns (a key 'level' in it chooses the Wald
@@ -36,7 +36,12 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
     1e7..1e8, so they are very small.  Without it the record is unchanged.  When the dict is
     covest_amd.information.sandwich_covariance's (it carries 'robust_standard_errors') the record adds
     robust_standard_errors, robust_wald_intervals and genome_size_robust_se, scaled like their neighbours: corrected
-    for misfit of the mixture, NOT for dependence between overlapping k-mers; otherwise it does not."""
+    for misfit of the mixture, NOT for dependence between overlapping k-mers; otherwise it does not.
+    `bootstrap`: the dict covest_amd.bootstrap.parametric_bootstrap returns; the record then carries
+    bootstrap_replicates, bootstrap_failed and, per free parameter, bootstrap_bias_<param>, bootstrap_se_<param> and
+    bootstrap_interval_<param> (the coverage's times sample_factor, like its neighbours), and
+    bootstrap_interval_genome_size where the bootstrap was given hist_orig.  They share the model's independence
+    assumption.  Without it the record is unchanged."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -105,6 +110,23 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
                 name: (None if iv is None else [float(v * scale if name == first else v) for v in iv])
                 for name, iv in wald_intervals(information, level, robust=True).items()}
             record['genome_size_robust_se'] = None if robust['genome_size_se'] is None else float(robust['genome_size_se'])
+    if bootstrap is not None:
+        scale = 1 if sample_factor is None else sample_factor
+        first = model.params[0]
+        record['bootstrap_replicates'] = int(bootstrap['replicates'])
+        record['bootstrap_failed'] = int(bootstrap['failed'])
+        for name in model.params:
+            by = scale if name == first else 1
+            for key, source in (('bias', 'bias'), ('se', 'standard_errors')):
+                value = bootstrap[source].get(name)
+                if value is not None:
+                    record['bootstrap_%s_%s' % (key, name)] = float(value * by)
+            interval = bootstrap['percentile_intervals'].get(name)
+            if interval is not None:
+                record['bootstrap_interval_%s' % name] = [float(v * by) for v in interval]
+        size = bootstrap.get('genome_size')
+        if size is not None and size.get('interval') is not None:
+            record['bootstrap_interval_genome_size'] = [float(v) for v in size['interval']]
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

@@ -473,6 +473,39 @@ int covest_sample_reads(int32_t device, const uint8_t *bases, const int64_t *off
                         uint8_t *out_bases, int64_t *out_offsets, int64_t *kept_index,
                         int64_t *n_kept, int64_t *bases_kept);
 
+/* ---- replicate histograms drawn from a weight vector: the parametric bootstrap's generator ----
+ * INPUT: m >= 1 weights w_0 .. w_{m-1} (doubles, finite, >= 0, sum > 0) and a number of draws n >= 0.  A call covers
+ * the replicates first_rep .. first_rep + n_rep - 1, every replicate index < 2^32, under a 64-bit seed.
+ * THRESHOLDS, by basic IEEE double operations only, in this order (no pow, no compensated sum, no reordering; numpy's
+ * cumsum of a one-dimensional double array restates it bit for bit):
+ *   cdf_0 = w_0, cdf_i = cdf_{i-1} + w_i strictly left to right; total = cdf_{m-1}; r_i = cdf_i / total;
+ *   t_i = floor(r_i * 2^63) as a uint64 -- the product is an exact scaling, and r_i <= 1, so t_i <= 2^63.
+ * DRAWS: Philox4x32-10 as above, key = (lo32(seed), hi32(seed)).  Draw d of replicate b takes the block
+ *   (lo32(d>>1), hi32(d>>1), b, 7) = w0..w3; an even d uses u = (w0 | w1 << 32) >> 1, an odd d u = (w2 | w3 << 32) >> 1.
+ *   The draw's cell is the number of i in 0 .. m - 2 with t_i <= u.  u < 2^63, so a cell whose r_i is 1, and every
+ *   cell after it, is never reached from above; a cell of weight 0 (t_i == t_{i-1}) never counts.
+ * The streams of the generators, by the counter's last word (the key is always the seed's two words):
+ *   0 read (c2: 0 the header, 1 + j the bases 4j .. 4j + 3)   1 genome   2 keep (the sampler)   3 family   4 copies
+ *   5 shuffle   6 divergence   7 draw (c2: the replicate) -- c2 is 0 in all but `read` and `draw`.
+ * OUTPUT: counts[b - first_rep][i] (int64, row-major n_rep x m) = the number of draws d < n of replicate b in cell i.
+ * The call OVERWRITES the output: the caller does not zero it.  A run of replicates [a, a + k) equals the same rows
+ * of a larger run, and the row for n equals the row for n' > n restricted to its first n draws.  All arithmetic on the
+ * device is integer and every atomic an integer one: the counts are exact, whatever the order.
+ * COVEST_E_INVALID, before any device work: a weight that is negative, NaN or infinite; a total that is 0 or not
+ * finite; m < 1; n_draws < 0; n_rep < 0; first_rep < 0 or a replicate index >= 2^32 (first_rep + n_rep > 2^32); a NULL
+ * buffer; and, for covest_draw_histograms*, m > COVEST_DRAW_MAX_CELLS.  n_rep == 0: COVEST_OK, nothing written;
+ * n_draws == 0: COVEST_OK, all-zero rows.
+ * covest_draw_thresholds is host arithmetic and needs no device (any m).  covest_draw_histograms takes HOST buffers,
+ * forms the thresholds, copies and waits (COVEST_E_NOMEM where its device buffers do not fit); the _device form takes
+ * DEVICE buffers -- d_thresholds[m] ascending, as covest_draw_thresholds gives them; d_out[n_rep * m] --, is
+ * asynchronous on `stream` and writes nothing outside d_out.  device < 0 = the calling thread's current device. */
+#define COVEST_DRAW_MAX_CELLS 65536
+int covest_draw_thresholds(int64_t m, const double *weights, uint64_t *out_thresholds);
+int covest_draw_histograms(int32_t device, int64_t m, const double *weights, int64_t n_draws, int64_t first_rep,
+                           int64_t n_rep, uint64_t seed, int64_t *out_counts);
+int covest_draw_histograms_device(int32_t device, int64_t m, const uint64_t *d_thresholds, int64_t n_draws,
+                                  int64_t first_rep, int64_t n_rep, uint64_t seed, int64_t *d_out, void *stream);
+
 /* ---- histogram down-sampling: covest/histogram.py:47-70 sample_histogram ----
  * Expected counts of the histogram after keeping every read with probability 1/factor, BEFORE the
  * reference's randomised rounding (:71-74, host side): out[j-1] = sum_i counts_i * pmf_i(j) for
