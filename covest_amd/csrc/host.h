@@ -342,6 +342,19 @@ struct covest_grid {
 };
 
 
+// What the partitioned path (kmer_bulk.hip) keeps in a counter: its buffers, from call to call, and what it found.
+struct BulkState {
+    DevBuf sampled, cursor, fill, tile_reads, lists, partial, recs, ovf, ctl, hist, big; // (ctl: BulkControl, lists: BulkLists)
+    unsigned long long stats[4] = {0, 0, 0, 0}; // BulkControl::stats of the last call
+    int64_t info[5] = {0, 0, 0, 0, 0}; // buckets, m, sample, records there was room for, records that found none
+    unsigned later_n = 0;              // buckets a workgroup (not a wave) counted
+    unsigned long long to_table_n = 0; // buckets counted through the table in HBM
+    bool table_used = false;           // ... and whether the table holds anything of the result
+    int64_t mem_limit = 0; // covest_kmer_memory_limit: bytes the buckets' records may take (0: what the device has free)
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // start, placed, scattered, counted, done
+    float ms[4] = {0, 0, 0, 0};
+};
+
 struct covest_kmer {
     int device = 0;
     int k = 20;
@@ -350,17 +363,8 @@ struct covest_kmer {
     KmerWideTable wtable{};
     KmerTable table{};
     DevBuf slots, flag, stats, hist, ws_bases, ws_offsets;
-    // the partitioned path (kmer_bulk.hip): its buffers, kept from call to call, and what it found
     bool bulk = false; // the counter holds the result of covest_kmer_count_reads_device (until covest_kmer_clear)
-    DevBuf bulk_sampled, bulk_cursor, bulk_fill, bulk_tile_reads, bulk_later, bulk_partial, bulk_recs, bulk_ovf, bulk_ctl, bulk_hist, bulk_big;
-    unsigned long long bulk_stats[4] = {0, 0, 0, 0};
-    int64_t bulk_info[5] = {0, 0, 0, 0, 0}; // buckets, m, sample, records there was room for, records that found none
-    unsigned bulk_later_n = 0;              // buckets a workgroup (not a wave) counted
-    unsigned long long bulk_to_table_n = 0; // buckets counted through the table in HBM
-    bool bulk_table_used = false;           // ... and whether the table holds anything of the result
-    int64_t bulk_mem_limit = 0; // covest_kmer_memory_limit: bytes the buckets' records may take (0: what the device has free)
-    hipEvent_t bulk_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // start, placed, scattered, counted, done
-    float bulk_ms[4] = {0, 0, 0, 0};
+    BulkState part;
     std::mutex lock;
 };
 

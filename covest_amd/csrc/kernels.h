@@ -3,8 +3,11 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <cstddef>
+
 #include "device_model.h"
 #include "direct_point.h"
+#include "kmer_plan.h"
 #include "tiles.h"
 
 namespace covest {
@@ -192,7 +195,6 @@ hipError_t launch_kmer_histogram(const KmerTable &t, unsigned long long *hist, u
                                  hipStream_t stream);
 
 // ---- K-kmer, partitioned (kmer_bulk.hip): minimizer buckets of super-k-mer records in HBM, counted in LDS ----
-constexpr int kOvfShards = 64, kOvfStride = 16;
 struct KmerBulk {
     int k, m, w;          // k-mer length, minimizer length, m-mers per k-mer (k - m + 1)
     int canonical;
@@ -211,10 +213,35 @@ struct KmerBulk {
                                    // caller starts over); a counter per 128-byte line
     unsigned long long overflow_cap; // per part
 };
-int kmer_bulk_block_bytes(const KmerBulk &p); // bytes of reads of one length a workgroup of pass 0/1 answers for
+// The two control blocks of a call, as the host reserves and names them (the launch functions take pointers to their
+// members).  BulkControl: zeroed before pass 0; the one-length probe of reads with offsets borrows its first word before.
+struct BulkControl {
+    unsigned long long one_length;   // the probe's flag: 1 on entry, 0 unless every read is as long as the first
+    unsigned long long pad0_;
+    unsigned long long room;         // pass 0: records the buckets were given places for, in all
+    unsigned long long pad1_;
+    unsigned long long stats[4];     // pass 2: see launch_kmer_bucket_count
+    unsigned long long pad2_[8];
+    unsigned long long ovf_count[kOvfShards * kOvfStride]; // KmerBulk::ovf_count, on 128-byte lines of their own
+};
+static_assert(offsetof(BulkControl, one_length) == 0 && offsetof(BulkControl, room) == 16 &&
+                  offsetof(BulkControl, stats) == 32 && offsetof(BulkControl, ovf_count) == 128 &&
+                  sizeof(BulkControl) == (16 + kOvfShards * kOvfStride) * 8,
+              "BulkControl: the layout kmer_bulk.hip's kernels were measured with");
+// BulkLists: the head is zeroed before pass 2; the two lists of bucket numbers, [buckets] words each, lie behind it.
+struct BulkLists {
+    unsigned later_n;                // buckets the wave-per-bucket kernel left to the workgroup-per-bucket one
+    unsigned pad0_;
+    unsigned long long to_table[2];  // buckets no LDS table could hold, and their k-mer occurrences
+    unsigned pad1_[2];
+    unsigned *later_list() { return reinterpret_cast<unsigned *>(this + 1); }
+    unsigned *to_table_list(size_t n_buckets) { return later_list() + n_buckets; }
+    static size_t bytes(size_t n_buckets) { return sizeof(BulkLists) + 2 * n_buckets * sizeof(unsigned); }
+};
+static_assert(offsetof(BulkLists, later_n) == 0 && offsetof(BulkLists, to_table) == 8 && sizeof(BulkLists) == 32,
+              "BulkLists: later_list at byte 32, to_table_list at 32 + 4 * buckets");
 // offsets != nullptr: reads of any length -- base0 = offsets[0], total_bytes = offsets[n_reads] - base0, first_read: room
-// for kmer_bulk_ragged_tiles(p, total_bytes) words
-int64_t kmer_bulk_ragged_tiles(const KmerBulk &p, int64_t total_bytes);
+// for kmer_plan::ragged_tiles(total_bytes, p.w) words
 hipError_t launch_kmer_scatter(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t fixed_len,
                                int64_t base0, int64_t total_bytes, unsigned *first_read, const KmerBulk &p, bool count_only,
                                hipStream_t stream);

@@ -43,8 +43,8 @@ namespace {
 using namespace kmer;
 typedef unsigned long long u64;
 
-constexpr int kTile = 256;            // bytes (threads) of a tile of pass 0/1
-constexpr int kTilesPerBlock = 8;     // consecutive tiles a workgroup works through (the unit of the sample)
+using kmer_plan::kTile;          // bytes (threads) of a tile of pass 0/1
+using kmer_plan::kTilesPerBlock; // consecutive tiles a workgroup works through (the unit of the sample)
 constexpr unsigned kNoBucket = ~0u;
 #ifndef KMER_TILES_AT_ONCE
 #define KMER_TILES_AT_ONCE 1
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(kTile) void kmer_tile_kernel(const unsigned char *_
     __shared__ unsigned bk[U][kTile]; // bucket of the window that starts at the byte
     __shared__ u64 hmask[U][kTile / kWave], vmask[U][kTile / kWave];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const int n_win = kTile - max(16, p.w - 1);
+    const int n_win = kTile - max(16, p.w - 1); // kmer_plan::tile_windows(p.w), in the form this kernel was measured with
     const unsigned mm = (1u << (2 * p.m)) - 1u;
     const unsigned block = COUNT ? blockIdx.x * (unsigned)p.sample : blockIdx.x;
     for (int tt = 0; tt < kTilesPerBlock; tt += U) {
@@ -458,15 +458,11 @@ __global__ __launch_bounds__(256) void kmer_caps_place_kernel(const KmerBulk p, 
 __device__ __forceinline__ void record_to_table(ulonglong2 rec, const KmerBulk &p, const KmerTable &t, int *overflow)
 {
     const int n_k = (int)rec.y - p.k + 1;
-    const u64 kmask = p.k < 32 ? (1ull << (2 * p.k)) - 1ull : ~0ull;
+    const u64 kmask = kmer_mask(p.k);
     for (int j = 0; j < n_k; ++j) {
         u64 h, rc;
         codes_from_le((rec.x >> (2 * j)) & kmask, p.k, h, rc);
-        if (p.canonical && rc < h) {
-            const u64 x = h;
-            h = rc;
-            rc = x;
-        }
+        canonical_pair(h, rc, p.canonical);
         table_add(t, h, rc, 1ull, overflow);
     }
 }
@@ -608,7 +604,7 @@ __global__ __launch_bounds__(256) void kmer_wave_count_kernel(const KmerBulk p, 
     u64 n_records = 0;
     const unsigned n_groups = (1u << p.log2_buckets) / kWave; // (at least 2^10 buckets)
     const unsigned n_waves = gridDim.x * (blockDim.x / kWave);
-    const u64 kmask = p.k < 32 ? (1ull << (2 * p.k)) - 1ull : ~0ull;
+    const u64 kmask = kmer_mask(p.k);
     for (unsigned g = blockIdx.x * (blockDim.x / kWave) + wave; g < n_groups; g += n_waves) {
         // 64 buckets' cursors at once, a lane each
         const unsigned b_lane = g * kWave + lane;
@@ -707,7 +703,7 @@ __global__ __launch_bounds__(256) void kmer_bucket_count_kernel(const KmerBulk p
     __syncthreads();
     SweepAcc acc;
     const unsigned n_later = later[0];
-    const u64 kmask = p.k < 32 ? (1ull << (2 * p.k)) - 1ull : ~0ull;
+    const u64 kmask = kmer_mask(p.k);
     for (unsigned at = blockIdx.x; at < n_later; at += gridDim.x) {
         const unsigned b = later_list[at];
         const ulonglong2 c = p.ctl[b];
@@ -814,45 +810,37 @@ __global__ __launch_bounds__(256) void kmer_one_length_kernel(const int64_t *__r
 template <bool COUNT>
 hipError_t launch_tiles(const unsigned char *bases, int64_t n_reads, int64_t len, const KmerBulk &p, hipStream_t stream)
 {
-    const int n_win = kTile - std::max(16, p.w - 1);
-    // whole reads per launch, their bytes (and the tiles' halo) below 2^32
-    const int64_t reads_per_launch = std::max<int64_t>(1, (((int64_t)1 << 31)) / len);
-    for (int64_t first = 0; first < n_reads; first += reads_per_launch) {
-        const int64_t n = std::min(n_reads - first, reads_per_launch);
-        const uint64_t positions = (uint64_t)(n * len);
-        const uint64_t avail = (uint64_t)((n_reads - first) * len);
-        const uint64_t n_tiles = (positions + n_win - 1) / n_win;
-        uint64_t blocks = (n_tiles + kTilesPerBlock - 1) / kTilesPerBlock;
+    for (int64_t first = 0; first < n_reads; first += kmer_plan::fixed_reads_per_launch(len)) {
+        const kmer_plan::FixedLaunch l = kmer_plan::fixed_launch(first, n_reads, len, p.w);
+        uint64_t blocks = (l.n_tiles + kTilesPerBlock - 1) / kTilesPerBlock;
         if (COUNT)
             blocks = (blocks + p.sample - 1) / p.sample;
         hipLaunchKernelGGL((kmer_tile_kernel<COUNT, kTilesAtOnce, false>), dim3((unsigned)blocks), dim3(kTile), 0, stream,
-                           bases + first * len, (unsigned)positions, (u64)avail, (unsigned)len, (unsigned)n_tiles, p, RaggedReads{});
+                           bases + first * len, (unsigned)l.positions, (u64)l.avail, (unsigned)len, (unsigned)l.n_tiles, p,
+                           RaggedReads{});
     }
     return hipGetLastError();
 }
 
 // Reads of any length: the byte run offsets[0] .. offsets[n_reads] in launches of whole blocks of tiles (below 2^31
 // bytes each; a launch need not end with a read: a window belongs to the launch its first byte is in).  first_read:
-// room for a word per tile of the largest launch (kmer_bulk_ragged_tiles).
+// room for a word per tile of the largest launch (kmer_plan::ragged_tiles).
 template <bool COUNT>
 hipError_t launch_ragged(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t base0, int64_t total,
                          unsigned *first_read, const KmerBulk &p, hipStream_t stream)
 {
-    const int n_win = kTile - std::max(16, p.w - 1);
-    const int64_t block_bytes = (int64_t)kTilesPerBlock * n_win;
-    const int64_t per_launch = (((int64_t)1 << 31) / block_bytes) * block_bytes;
-    for (int64_t pos0 = 0; pos0 < total; pos0 += per_launch) {
-        const int64_t positions = std::min(total - pos0, per_launch);
-        const uint64_t n_tiles = (uint64_t)((positions + n_win - 1) / n_win);
+    for (int64_t pos0 = 0; pos0 < total; pos0 += kmer_plan::ragged_bytes_per_launch(p.w)) {
+        const kmer_plan::RaggedLaunch l = kmer_plan::ragged_launch(pos0, total, p.w);
+        const uint64_t n_tiles = l.n_tiles;
         uint64_t blocks = (n_tiles + kTilesPerBlock - 1) / kTilesPerBlock;
         RaggedReads src{offsets, n_reads, base0, pos0, first_read};
         // (both passes make the table again: a launch's table is gone once the next launch has made its own)
         hipLaunchKernelGGL(kmer_tile_first_read_kernel, dim3((unsigned)((n_tiles + 255) / 256)), dim3(256), 0, stream, src,
-                           (unsigned)n_tiles, n_win, first_read);
+                           (unsigned)n_tiles, kmer_plan::tile_windows(p.w), first_read);
         if (COUNT)
             blocks = (blocks + p.sample - 1) / p.sample;
         hipLaunchKernelGGL((kmer_tile_kernel<COUNT, kTilesAtOnce, true>), dim3((unsigned)blocks), dim3(kTile), 0, stream,
-                           bases + base0 + pos0, (unsigned)positions, (u64)(total - pos0), 0u, (unsigned)n_tiles, p, src);
+                           bases + base0 + pos0, (unsigned)l.positions, (u64)(total - pos0), 0u, (unsigned)n_tiles, p, src);
     }
     const int64_t step = COUNT ? p.sample : 1;
     const int64_t threads = (n_reads + step - 1) / step;
@@ -866,19 +854,6 @@ hipError_t launch_ragged(const unsigned char *bases, const int64_t *offsets, int
 }
 
 } // namespace
-
-int kmer_bulk_block_bytes(const KmerBulk &p)
-{
-    return kTilesPerBlock * (kTile - std::max(16, p.w - 1));
-}
-
-int64_t kmer_bulk_ragged_tiles(const KmerBulk &p, int64_t total_bytes)
-{
-    const int n_win = kTile - std::max(16, p.w - 1);
-    const int64_t block_bytes = (int64_t)kTilesPerBlock * n_win;
-    const int64_t per_launch = (((int64_t)1 << 31) / block_bytes) * block_bytes;
-    return (std::min(total_bytes, per_launch) + n_win - 1) / n_win + 1;
-}
 
 hipError_t launch_kmer_scatter(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t fixed_len,
                                int64_t base0, int64_t total_bytes, unsigned *first_read, const KmerBulk &p, bool count_only,

@@ -35,11 +35,7 @@ __device__ __forceinline__ void count_window(const unsigned char *__restrict__ s
 {
     unsigned long long h, rc;
     window_codes(seq, s, len, k, h, rc);
-    if (canonical && rc < h) {
-        const unsigned long long x = h;
-        h = rc;
-        rc = x;
-    }
+    canonical_pair(h, rc, canonical);
     table_add(t, h, rc, 1ull, overflow);
 }
 
@@ -65,11 +61,7 @@ __global__ __launch_bounds__(256) void kmer_count_kernel(const unsigned char *__
                 h = (h << 2) | c;
             }
             rc = revcomp_code(h, k);
-            if (canonical && rc < h) {
-                const unsigned long long x = h;
-                h = rc;
-                rc = x;
-            }
+            canonical_pair(h, rc, canonical);
             table_add(t, h, rc, 1ull, overflow);
         }
         return;
@@ -165,12 +157,6 @@ __global__ __launch_bounds__(256) void kmer_histogram_kernel(const KmerTable t, 
     for (int i = threadIdx.x; i < kLdsBins; i += blockDim.x)
         if (bins[i] != 0u && (unsigned long long)i < hist_len)
             atomicAdd(&hist[i], (unsigned long long)bins[i]);
-}
-
-unsigned grid_for(unsigned long long n, unsigned cap = 256 * 16)
-{
-    const unsigned long long blocks = (n + 255) / 256;
-    return (unsigned)(blocks < cap ? (blocks ? blocks : 1) : cap);
 }
 
 } // namespace

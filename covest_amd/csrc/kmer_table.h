@@ -19,6 +19,29 @@ __device__ __forceinline__ unsigned base_code(unsigned char ch)
     return x ^ (x >> 1);
 }
 
+// the low 2k bits: a k-mer's code
+__device__ __forceinline__ unsigned long long kmer_mask(int k)
+{
+    return k < 32 ? (1ull << (2 * k)) - 1ull : ~0ull;
+}
+
+// canonical keys: the smaller of a code and its reverse complement's comes first
+__device__ __forceinline__ void canonical_pair(unsigned long long &h, unsigned long long &rc, int canonical)
+{
+    if (canonical && rc < h) {
+        const unsigned long long x = h;
+        h = rc;
+        rc = x;
+    }
+}
+
+// workgroups of 256 threads for n items, `cap` at most (the kernels stride over the rest)
+inline unsigned grid_for(unsigned long long n, unsigned cap = 256 * 16)
+{
+    const unsigned long long blocks = (n + 255) / 256;
+    return (unsigned)(blocks < cap ? (blocks ? blocks : 1) : cap);
+}
+
 __device__ __forceinline__ unsigned long long slot_of(unsigned long long key, int log2_slots)
 {
     return (key * 0x9E3779B97F4A7C15ull) >> (64 - log2_slots); // Fibonacci hashing
@@ -107,7 +130,6 @@ __device__ __forceinline__ void table_add(const KmerTable t, unsigned long long 
     *overflow = 1;
 }
 
-
 // The window starting at seq[s] of a read of `len` bases as 2-bit codes, little-endian (base i of the window at bits
 // 2i) -- that IS the reverse complement's code once complemented -- and mirrored (first base in the highest bits:
 // hash_kmer, bin/kmer_hist.py:18-23).  Four bases per (unaligned) 32-bit load where the read has them.
@@ -115,7 +137,7 @@ __device__ __forceinline__ void window_codes(const unsigned char *__restrict__ s
                                              unsigned long long &h, unsigned long long &rc)
 {
     const int n_words = (k + 3) >> 2; // 32-bit words of 4 bases that cover a window
-    const unsigned long long kmask = k < 32 ? (1ull << (2 * k)) - 1ull : ~0ull;
+    const unsigned long long kmask = kmer_mask(k);
     h = 0;
     rc = 0;
     if (s + 4 * n_words <= len) {
@@ -145,7 +167,7 @@ __device__ __forceinline__ void window_codes(const unsigned char *__restrict__ s
 // reverse complement's
 __device__ __forceinline__ void codes_from_le(unsigned long long le, int k, unsigned long long &h, unsigned long long &rc)
 {
-    const unsigned long long kmask = k < 32 ? (1ull << (2 * k)) - 1ull : ~0ull;
+    const unsigned long long kmask = kmer_mask(k);
     rc = ~le & kmask;
     unsigned long long r = __brevll(le);
     r = ((r & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((r & 0x5555555555555555ull) << 1);

@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "kmer_table.h"
 #include "wave.h"
 
 namespace covest {
@@ -35,11 +36,8 @@ constexpr u64 kLocked = 1ull << 63;
 constexpr int kWideMaxProbe = 1 << 16;
 constexpr int kWideMaxSpin = 1 << 20;
 
-__device__ __forceinline__ unsigned wide_base_code(unsigned char ch)
-{
-    const unsigned x = (ch >> 1) & 3u; // a=0 c=1 t=2 g=3; x ^ (x >> 1) swaps g and t
-    return x ^ (x >> 1);
-}
+using kmer::base_code;
+using kmer::grid_for;
 
 template <int W>
 struct WideKey {
@@ -185,7 +183,7 @@ __global__ __launch_bounds__(256) void kmer_wide_count_kernel(const unsigned cha
             WideKey<W> h;
             h.clear();
             for (int i = 0; i < (int)len; ++i)
-                h.push(wide_base_code(seq[i]));
+                h.push(base_code(seq[i]));
             if (canonical) {
                 const WideKey<W> rc = wide_revcomp(h, k);
                 if (rc.less_than(h))
@@ -201,7 +199,7 @@ __global__ __launch_bounds__(256) void kmer_wide_count_kernel(const unsigned cha
         h.clear();
         rc.clear();
         for (int i = 0; i < k; ++i) {
-            const u64 c = wide_base_code(seq[s + i]);
+            const u64 c = base_code(seq[s + i]);
             h.push(c);              // hash_kmer, :18-23 (rehash :26-31 yields the same window code)
             rc.set(i, 3ull - c);    // reverse complement, built back to front
         }
@@ -271,12 +269,6 @@ __global__ __launch_bounds__(256) void kmer_wide_histogram_kernel(const KmerWide
     }
 }
 
-unsigned wide_grid_for(u64 n, unsigned cap = 256 * 16)
-{
-    const u64 blocks = (n + 255) / 256;
-    return (unsigned)(blocks < cap ? (blocks ? blocks : 1) : cap);
-}
-
 template <int W>
 hipError_t count_w(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t fixed_len, int canonical,
                    const KmerWideTable &t, int *overflow, hipStream_t stream)
@@ -299,7 +291,7 @@ hipError_t count_w(const unsigned char *bases, const int64_t *offsets, int64_t n
 hipError_t launch_kmer_wide_clear(const KmerWideTable &t, hipStream_t stream)
 {
     const u64 n = (t.mask + 1) * (u64)t.stride;
-    hipLaunchKernelGGL(kmer_wide_clear_kernel, dim3(wide_grid_for(n)), dim3(256), 0, stream, t.words, n);
+    hipLaunchKernelGGL(kmer_wide_clear_kernel, dim3(grid_for(n)), dim3(256), 0, stream, t.words, n);
     return hipGetLastError();
 }
 
@@ -319,7 +311,7 @@ hipError_t launch_kmer_wide_count(const unsigned char *bases, const int64_t *off
 
 hipError_t launch_kmer_wide_rehash(const KmerWideTable &src, const KmerWideTable &dst, int *overflow, hipStream_t stream)
 {
-    const dim3 grid(wide_grid_for(src.mask + 1));
+    const dim3 grid(grid_for(src.mask + 1));
     if (src.w == 2)
         hipLaunchKernelGGL((kmer_wide_rehash_kernel<2>), grid, dim3(256), 0, stream, src, dst, overflow);
     else if (src.w == 4)
@@ -333,14 +325,14 @@ hipError_t launch_kmer_wide_rehash(const KmerWideTable &src, const KmerWideTable
 
 hipError_t launch_kmer_wide_stats(const KmerWideTable &t, unsigned long long *stats, hipStream_t stream)
 {
-    hipLaunchKernelGGL(kmer_wide_stats_kernel, dim3(wide_grid_for(t.mask + 1)), dim3(256), 0, stream, t, stats);
+    hipLaunchKernelGGL(kmer_wide_stats_kernel, dim3(grid_for(t.mask + 1)), dim3(256), 0, stream, t, stats);
     return hipGetLastError();
 }
 
 hipError_t launch_kmer_wide_histogram(const KmerWideTable &t, unsigned long long *hist, unsigned long long hist_len,
                                       hipStream_t stream)
 {
-    hipLaunchKernelGGL(kmer_wide_histogram_kernel, dim3(wide_grid_for(t.mask + 1)), dim3(256), 0, stream, t, hist, hist_len);
+    hipLaunchKernelGGL(kmer_wide_histogram_kernel, dim3(grid_for(t.mask + 1)), dim3(256), 0, stream, t, hist, hist_len);
     return hipGetLastError();
 }
 
