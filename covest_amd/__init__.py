@@ -13,6 +13,8 @@ from .profile import profile_negll, likelihood_interval, coverage_interval  # no
 from .information import observed_information, sandwich_covariance, wald_intervals, genome_size_se  # noqa: F401,E402
 from . import bootstrap  # noqa: F401,E402
 from .bootstrap import parametric_bootstrap, draw_histograms, draw_thresholds, model_cells  # noqa: F401,E402
+from . import batch  # noqa: F401,E402
+from .batch import HistogramBatch  # noqa: F401,E402
 from . import poisson  # noqa: F401,E402
 from .poisson import truncated_poisson, truncated_poisson_many, truncated_poisson_table  # noqa: F401,E402
 from . import simulate  # noqa: F401,E402

@@ -41,6 +41,8 @@ EXPORTS = (
     "covest_sample_reads", "covest_sample_reads_device",
     "covest_repeat_plan", "covest_repeat_genome", "covest_repeat_genome_device",
     "covest_draw_thresholds", "covest_draw_histograms", "covest_draw_histograms_device",
+    "covest_batch_create", "covest_batch_draw", "covest_batch_counts", "covest_batch_eval_cross", "covest_batch_eval_pairs",
+    "covest_batch_argmin_cross", "covest_batch_info", "covest_batch_destroy",
 )
 
 
@@ -239,6 +241,22 @@ def lib():
     L.covest_draw_histograms.argtypes = [i32, i64, vp, i64, i64, i64, u64, vp]
     L.covest_draw_histograms_device.restype = ctypes.c_int
     L.covest_draw_histograms_device.argtypes = [i32, i64, vp, i64, i64, i64, u64, vp, vp]
+    L.covest_batch_create.restype = ctypes.c_int
+    L.covest_batch_create.argtypes = [vp, i64, vp, vp, ctypes.POINTER(vp)]
+    L.covest_batch_draw.restype = ctypes.c_int
+    L.covest_batch_draw.argtypes = [vp, dp, i64, i64, i64, u64, ctypes.POINTER(vp)]
+    L.covest_batch_counts.restype = ctypes.c_int
+    L.covest_batch_counts.argtypes = [vp, vp, vp]
+    L.covest_batch_eval_cross.restype = ctypes.c_int
+    L.covest_batch_eval_cross.argtypes = [vp, i64, vp, vp]
+    L.covest_batch_eval_pairs.restype = ctypes.c_int
+    L.covest_batch_eval_pairs.argtypes = [vp, i64, vp, vp, vp]
+    L.covest_batch_argmin_cross.restype = ctypes.c_int
+    L.covest_batch_argmin_cross.argtypes = [vp, i64, vp, vp, vp]
+    L.covest_batch_info.restype = ctypes.c_int
+    L.covest_batch_info.argtypes = [vp, i64p]
+    L.covest_batch_destroy.restype = None
+    L.covest_batch_destroy.argtypes = [vp]
     L.covest_grid_diag.restype = i64
     L.covest_grid_diag.argtypes = [vp, ctypes.POINTER(i64), i64]
     L.covest_grid_launch_record.restype = i64

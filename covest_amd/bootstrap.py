@@ -133,6 +133,42 @@ def _refit(model, keys, counts, tail, estimate, fix, estimator_options):
         twin.close()
 
 
+def _refit_lockstep(model, estimate, replicates, seed, n_draws, fix, estimator_options):
+    """(estimates, success, log-likelihoods) of all replicates refitted TOGETHER: the histograms are drawn into a
+    HistogramBatch and never leave the device, one CoverageEstimator._optimize per replicate runs under the estimator's
+    _LockStep, and a merged round -- every replicate's point and its finite-difference neighbours -- is ONE
+    loglikelihood_pairs call, each request tagged with its replicate.  No model per replicate."""
+    from .batch import HistogramBatch
+    from .estimator import CoverageEstimator, _LockStep
+    est = CoverageEstimator(model, fix=fix, **estimator_options)
+    if not est.batched or est.reference_specials:
+        raise ValueError('refit="lockstep" goes with neither batched=False nor reference_specials=True')
+    batch = HistogramBatch.draw(model, estimate, replicates, seed=seed, n_draws=n_draws)
+    try:
+        def evaluate_merged(requests):  # [(replicate, optimiser-space vector)] of one round
+            index = [b for b, _ in requests]
+            points = np.array([est._model_args(x) for _, x in requests], dtype=np.float64)
+            return -batch.loglikelihood_pairs(index, points)
+
+        start = list(estimate)
+        start[est.ERROR_RATE] *= est.err_scale
+
+        def refine(b, evaluate):
+            return est._optimize(start, lambda xs: evaluate([(b, x) for x in xs]))
+
+        results = _LockStep(evaluate_merged, replicates).map(refine, list(range(replicates)))
+        estimates = np.empty((replicates, len(estimate)), dtype=np.float64)
+        for b, res in enumerate(results):
+            x = [float(v) for v in res.x]
+            x[est.ERROR_RATE] /= est.err_scale
+            estimates[b] = x
+        success = np.array([bool(res.success) for res in results], dtype=bool)
+        loglik = batch.loglikelihood_pairs(np.arange(replicates), estimates) if replicates else np.empty(0)
+        return estimates, success, loglik
+    finally:
+        batch.close()
+
+
 def _on_bound(values, bounds):
     return [(lo is not None and v <= lo) or (hi is not None and v >= hi) for v, (lo, hi) in zip(values, bounds)]
 
@@ -166,9 +202,14 @@ def summarize(estimates, success, estimate, names, fix=None, level=0.95):
 
 
 def parametric_bootstrap(model, estimate, replicates=100, seed=0, fix=None, level=0.95, hist_orig=None, sample_factor=1,
-                         **estimator_options):
+                         refit="sequential", **estimator_options):
     """`replicates` histograms of round(sum(counts) + tail) draws from `model` at `estimate` (model_cells), each
     refitted by CoverageEstimator(model_b, fix=fix, **estimator_options) started at `estimate`, one after the other.
+
+    refit="lockstep": the same replicates (the same draws) as a HistogramBatch on the device, all refits advancing
+    together, one loglikelihood_pairs launch per round and no model per replicate (_refit_lockstep).  Finite-difference
+    gradients only: with gradient="analytic" it raises ValueError -- a batch has no gradient.  The two routes evaluate
+    with different kernels, so a refit may stop an L-BFGS-B step apart; the result has the same keys, and `refit`.
 
     Returns a dict: replicates, seed, n_draws; estimates (B x P), success (B), loglikelihood (B), at_bound (B x P: the
     refit ended on a bound of the model); mean, bias (mean - estimate), standard_errors and percentile_intervals at
@@ -181,21 +222,31 @@ def parametric_bootstrap(model, estimate, replicates=100, seed=0, fix=None, leve
     names = list(model.params)
     if len(estimate) != len(names):
         raise ValueError("parametric_bootstrap: %d parameters expected, %d given" % (len(names), len(estimate)))
-    keys, weights, has_tail = model_cells(model, estimate)
+    if refit not in ("sequential", "lockstep"):
+        raise ValueError('refit must be "sequential" or "lockstep"')
+    if refit == "lockstep" and estimator_options.get('gradient', 'fd') != 'fd':
+        raise ValueError('refit="lockstep" goes with gradient="fd" only: a histogram batch has no gradient')
     n_draws = int(round(float(sum(model.hist.values())) + float(model.tail)))
-    counts = draw_histograms(weights, n_draws, replicates, seed=seed, device=model.device)
-    n_keys = len(keys)
     estimates = np.full((replicates, len(names)), np.nan)
     success = np.zeros(replicates, dtype=bool)
     loglik = np.full(replicates, np.nan)
     at_bound = np.zeros((replicates, len(names)), dtype=bool)
-    for b in range(replicates):
-        tail_b = int(counts[b, n_keys]) if has_tail else 0
-        x, ok, ll = _refit(model, keys, counts[b, :n_keys], tail_b, estimate, fix, estimator_options)
-        estimates[b], success[b], loglik[b] = x, ok, ll
-        at_bound[b] = _on_bound(x, model.bounds)
+    if refit == "lockstep":
+        estimates, success, loglik = _refit_lockstep(model, estimate, replicates, seed, n_draws, fix, estimator_options)
+        for b in range(replicates):
+            at_bound[b] = _on_bound(estimates[b], model.bounds)
+    else:
+        keys, weights, has_tail = model_cells(model, estimate)
+        counts = draw_histograms(weights, n_draws, replicates, seed=seed, device=model.device)
+        n_keys = len(keys)
+        for b in range(replicates):
+            tail_b = int(counts[b, n_keys]) if has_tail else 0
+            x, ok, ll = _refit(model, keys, counts[b, :n_keys], tail_b, estimate, fix, estimator_options)
+            estimates[b], success[b], loglik[b] = x, ok, ll
+            at_bound[b] = _on_bound(x, model.bounds)
     out = {'replicates': replicates, 'seed': seed, 'n_draws': n_draws, 'level': float(level), 'params': names,
-           'estimate': estimate, 'estimates': estimates, 'success': success, 'loglikelihood': loglik, 'at_bound': at_bound}
+           'estimate': estimate, 'estimates': estimates, 'success': success, 'loglikelihood': loglik, 'at_bound': at_bound,
+           'refit': refit}
     out.update(summarize(estimates, success, estimate, names, fix=fix, level=level))
     if hist_orig is not None:
         occurrences = sum(i * h for i, h in hist_orig.items())

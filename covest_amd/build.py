@@ -25,7 +25,8 @@ SOURCES = [("host_common.cpp", (), "host_common"), ("tiles_host.cpp", (), "tiles
            ("tp_eval.hip", (), "tp_eval"), ("abi_sim.cpp", (), "abi_sim"), ("sim_reads.hip", (), "sim_reads"),
            ("abi_sample.cpp", (), "abi_sample"), ("sample_reads.hip", (), "sample_reads"),
            ("abi_repeat.cpp", (), "abi_repeat"), ("sim_repeats.hip", (), "sim_repeats"),
-           ("abi_draw.cpp", (), "abi_draw"), ("draw_hist.hip", (), "draw_hist")]
+           ("abi_draw.cpp", (), "abi_draw"), ("draw_hist.hip", (), "draw_hist"),
+           ("abi_batch.cpp", (), "abi_batch"), ("ll_batch.hip", (), "ll_batch")]
 SOURCES += [("ll_factored.hip", ("-DCOVEST_FACTORED_VARIANT=%d" % v,), "ll_factored_v%d" % v) for v in range(10)]
 SOURCES += [("ll_basic.hip", ("-DCOVEST_BASIC_VARIANT=%d" % v,), "ll_basic_v%d" % v) for v in range(8)]
 MAX_PARALLEL = 8

@@ -16,6 +16,27 @@ int refuse(const char *who, const char *what) { return fail(COVEST_E_INVALID, st
 
 } // namespace
 
+namespace covest {
+
+// The host side of a draw whose rows STAY on the device (covest_draw_histograms copies them back; covest_batch_draw,
+// abi_batch.cpp, turns them into a batch): thresholds of the checked weights, up through the staging block, and the
+// launch on the null stream of the current device.  d_out holds n_rep * m int64 afterwards; d_thr must live until the
+// kernels are done.
+int draw_histograms_resident(const char *who, int64_t m, const double *weights, int64_t n_draws, int64_t first_rep,
+                             int64_t n_rep, uint64_t seed, DevBuf &d_thr, DevBuf &d_out)
+{
+    std::vector<uint64_t> thr((size_t)m);
+    draw_thresholds(m, weights, thr.data());
+    HIP_TRY(d_thr.reserve(thr.size() * sizeof(uint64_t)));
+    HIP_TRY(d_out.reserve((size_t)n_rep * (size_t)m * sizeof(int64_t)));
+    COVEST_TRY(stage_upload(d_thr.ptr, thr.data(), thr.size() * sizeof(uint64_t),
+                            (std::string(who) + ": upload of the thresholds").c_str()));
+    HIP_TRY(launch_draw_hist(d_thr.as<uint64_t>(), m, n_draws, (uint64_t)first_rep, n_rep, seed, d_out.as<int64_t>(), nullptr));
+    return COVEST_OK;
+}
+
+} // namespace covest
+
 extern "C" {
 
 int covest_draw_thresholds(int64_t m, const double *weights, uint64_t *out)
@@ -60,15 +81,10 @@ int covest_draw_histograms(int32_t device, int64_t m, const double *weights, int
         std::fill(out_counts, out_counts + cells, (int64_t)0);
         return COVEST_OK;
     }
-    std::vector<uint64_t> thr((size_t)m);
-    draw_thresholds(m, weights, thr.data());
     DeviceCall call(device, "covest_draw_histograms");
     COVEST_TRY(call.status());
     DevBuf d_thr, d_out; // (go with the call; the copy back has waited for the kernels by then)
-    HIP_TRY(d_thr.reserve(thr.size() * sizeof(uint64_t)));
-    HIP_TRY(d_out.reserve(cells * sizeof(int64_t)));
-    COVEST_TRY(stage_upload(d_thr.ptr, thr.data(), thr.size() * sizeof(uint64_t), "covest_draw_histograms: upload of the thresholds"));
-    HIP_TRY(launch_draw_hist(d_thr.as<uint64_t>(), m, n_draws, (uint64_t)first_rep, n_rep, seed, d_out.as<int64_t>(), nullptr));
+    COVEST_TRY(draw_histograms_resident("covest_draw_histograms", m, weights, n_draws, first_rep, n_rep, seed, d_thr, d_out));
     HIP_TRY(hipMemcpy(out_counts, d_out.ptr, cells * sizeof(int64_t), hipMemcpyDeviceToHost));
     return COVEST_OK;
 }

@@ -10,6 +10,8 @@
 //   abi_tp.cpp        covest_truncated_poisson, covest_truncated_poisson_table
 //   abi_sim.cpp       covest_random_genome*, covest_simulate_reads*
 //   abi_repeat.cpp    covest_repeat_plan, covest_repeat_genome*
+//   abi_draw.cpp      covest_draw_thresholds, covest_draw_histograms*
+//   abi_batch.cpp     covest_batch_*
 // ).  Nothing here is part of the C ABI (include/covest_amd.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -417,6 +419,10 @@ int build_factored_plan(covest_grid *g, const double *const *axes, const int64_t
                         const std::vector<int32_t> &t_table);
 int build_list_plan(covest_model *m, int64_t n, const double *params, const std::vector<int32_t> &t_list,
                     const std::vector<int32_t> *o_base_list, DevBuf &buf, FactoredPlan &pl, bool in_place = false);
+
+// ---- abi_draw.cpp: a draw whose rows stay on the device (shared with abi_batch.cpp)
+int draw_histograms_resident(const char *who, int64_t m, const double *weights, int64_t n_draws, int64_t first_rep,
+                             int64_t n_rep, uint64_t seed, DevBuf &d_thr, DevBuf &d_out);
 
 // ---- abi_model.cpp: kernel dispatch shared with the grid entry points; the in-place limit shared with abi_tp.cpp
 constexpr int64_t kInPlaceMaxPoints = 256; // lists (of points, of pmf pairs) up to this size: read and written in mapped host memory

@@ -325,4 +325,38 @@ constexpr long long kDrawChunk = 1 << 17; // draws a workgroup takes
 hipError_t launch_draw_hist(const uint64_t *thr, int64_t m, int64_t n, uint64_t first_rep, int64_t n_rep, uint64_t seed,
                             int64_t *out, hipStream_t stream);
 
+// ---- K-batch: many histograms on one key set (ll_batch.hip) ----
+// LL_b(theta_i) = sum_j h_bj log p_j(theta_i) + tail_b [sp_i < 1] log(1 - sp_i): p is evaluated once per point, into a
+// table of log p over ALL keys, and the histograms enter through one fp64 contraction (v_mfma_f64_16x16x4_f64).
+constexpr int64_t kBatchTableBytes = (int64_t)256 << 20; // the table of one chunk of points (the host loops over chunks)
+constexpr int64_t kBatchMaxHist = (int64_t)1 << 20;      // histograms of a batch (the contraction's grid y stays < 65536)
+// The table of n points (a list: src.params, src.t_list): one wave a point runs direct_point_ll<P, true> on `m`, whose
+// bins must be the all-keys view with a zero count array and whose tail must be 1.  table[i][j] (row-major, n_keys a
+// row) = log p_ij, +0.0 where p_ij <= 0 (such keys counted in dead[i]; a p_ij of exactly 1 is stored as -0.0, so that
+// the bits of +0.0 mean "dead" and nothing else), NaN where p_ij is NaN; tl[i] = log(1 - sp_i) or 0.  keep_p: the row
+// stays p_ij itself (what covest_probabilities(clamp = 1) returns), dead and tl as above.
+hipError_t launch_batch_table(const DevModel &m, const PointSource &src, int64_t n, double *table, double *tl,
+                              int32_t *dead, bool keep_p, hipStream_t stream);
+// out[b * ld + i] = sum_j H[b][j] table[i][j] + tails[b] tl[i] for b < n_hist, i < n; H is n_hist x n_keys, row-major.
+// Returns in *tiles (nullptr: not wanted) the 16 x 16 output tiles the launches cover.
+hipError_t launch_batch_cross(const double *H, const double *tails, int64_t n_hist, const double *table, const double *tl,
+                              int64_t n, int64_t n_keys, double *out, int64_t ld, int64_t *tiles, hipStream_t stream);
+// One wave per (b, k): point i = dead_list[k] of the table has keys with p <= 0; where histogram b counts one of them
+// (h_bj != 0), out[b * ld + i] = -inf unless it is NaN already.
+hipError_t launch_batch_fix_dead(const double *H, int64_t n_hist, const double *table, int64_t n_keys,
+                                 const int32_t *dead_list, int64_t n_dead, double *out, int64_t ld, hipStream_t stream);
+// out[i] = sum_j H[index[i]][j] table[i][j] + tails[index[i]] tl[i], the dead-key rule applied inline; a wave a request.
+hipError_t launch_batch_pairs(const double *H, const double *tails, const int64_t *index, const double *table,
+                              const double *tl, int64_t n, int64_t n_keys, double *out, hipStream_t stream);
+// Per histogram b, over ll[b * ld + i], i < n: the first i with the strictly smallest -ll (NaN never wins) against the
+// running (run_val[b], run_idx[b]) of the chunks before, which a later chunk only beats with a strictly smaller value;
+// a winner is stored as first + i.  Start the running pair at (+inf, -1).
+hipError_t launch_batch_argmin(const double *ll, int64_t ld, int64_t n_hist, int64_t n, int64_t first, double *run_val,
+                               int64_t *run_idx, hipStream_t stream);
+hipError_t launch_batch_argmin_init(int64_t n_hist, double *run_val, int64_t *run_idx, hipStream_t stream);
+// The rows of a draw (draw_hist.hip: n_hist x m int64, m = n_keys + has_tail) as double counts H[n_hist][n_keys] and
+// tails[n_hist] (the last cell with a tail, else 0).
+hipError_t launch_batch_from_draw(const int64_t *draw, int64_t n_hist, int64_t n_keys, bool has_tail, double *H,
+                                  double *tails, hipStream_t stream);
+
 } // namespace covest

@@ -1,0 +1,363 @@
+// ll_batch.hip -- K-batch: many histograms on ONE key set, scored in one pass.
+//
+// For a fixed key set p_j(theta) does not depend on the counts, and all of the likelihood's expensive work is in p_j
+// (n_keys * S * (T - 1) pmf terms a point, ~30 fp64 instructions each in K-direct).  The counts enter through one dot
+// product per histogram:
+//     LL_b(theta_i) = sum_j h_bj log p_j(theta_i) + tail_b [sp_i < 1] log(1 - sp_i)
+// so B histograms at n points are n evaluations of p and a B x n_keys x n contraction, not B n evaluations.
+//
+//   batch_table_kernel    one wave a point: direct_point_ll<P, true> (K-direct's arithmetic after clamp_point, bit for
+//                         bit what covest_probabilities(clamp = 1) returns) writes p_ij into the point's table row, and
+//                         the same wave turns the row into log p_ij.  Each lane re-reads exactly the elements it wrote
+//                         itself (index = lane mod 64 in both loops), so no fence stands between the two passes.
+//   batch_cross_kernel    out = H L^T by v_mfma_f64_16x16x4_f64.  Both operands are K-contiguous (H is B x n_keys, L is
+//                         n x n_keys): a lane (r = lane & 15, kq = lane >> 4) loads FOUR consecutive keys
+//                         j0 + 4 kq .. + 3 of row r of either operand -- 32 bytes a lane, 128 contiguous bytes a row
+//                         per 16 keys -- and feeds them to four MFMA steps: step s contracts the keys j0 + 4 k + s,
+//                         k = 0..3, the same permutation of the key order in A and in B.  A wave owns 16 histograms x
+//                         64 points: one A fragment against four B fragments, four independent accumulators (the
+//                         instruction's dependent latency is longer than its issue interval).  No LDS: every element
+//                         is used by one lane only.  Padding of B, n and n_keys is a select IN THE LOAD (0 in both
+//                         operands: 0 x garbage could be NaN).
+//                         Operand maps (A[r][k = kq], B[k = kq][c = lane & 15], D: col = lane & 15, row = kq + 4 reg).
+//   batch_fix_dead_kernel the reference's h * safe_log(0) = -inf: a key with p_ij <= 0 carries +0.0 in the table (so the
+//                         contraction adds nothing for it) and the point is listed; one wave per (histogram, listed
+//                         point) sets -inf where the histogram counts such a key.  A key with h_bj = 0 contributes
+//                         nothing (covest/models.py:105-107, `if h`).
+//   batch_pairs_kernel    histogram index[i] at point i, one wave a request, the dead-key rule inline.
+//   batch_argmin_kernel   per histogram the first index of the strictly smallest -LL (covest/grid.py:65-70), carried
+//                         across table chunks on the device.
+//   batch_from_draw_kernel  int64 rows of draw_hist.hip to double counts and tails.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "batch_host.h"
+#include "direct_point.h"
+#include "kernels.h"
+
+namespace covest {
+
+namespace {
+
+typedef double double4_t __attribute__((ext_vector_type(4)));
+
+constexpr int kWavesPerBlock = 4;
+constexpr int64_t kMaxBlocks = kBatchHostMaxBlocks; // HIP wraps a grid of more than 2^32 threads silently; the cuts are
+                                                    // batch_host.h's (checked without a device)
+
+__device__ __forceinline__ bool is_dead_entry(double l) { return __double_as_longlong(l) == 0ll; } // the bits of +0.0
+
+template <int P>
+__global__ __launch_bounds__(256) void batch_table_kernel(const DevModel m, const PointSource src, const int64_t n,
+                                                          double *table, double *__restrict__ tl,
+                                                          int32_t *__restrict__ dead, const int keep_p)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t pt = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x / kWave);
+    if (pt >= n)
+        return; // wave-uniform
+    const int64_t nk = m.bins.n;
+    double *row = table + pt * nk;
+    // counts 0 and tail 1 (the launcher's DevModel): the value IS log(1 - sp), or 0 where sp is not < 1
+    const double t = direct_point_ll<P, true>(m, src, pt, row);
+    int n_dead = 0;
+    for (int64_t j = lane; j < nk; j += kWave) { // (the lane's own elements: see the head of the file)
+        const double p = row[j];
+        if (p <= 0.0) {
+            ++n_dead;
+            if (!keep_p)
+                row[j] = 0.0;
+        } else if (!keep_p) { // (NaN comes here and stays NaN)
+            const double l = log(p);
+            row[j] = l == 0.0 ? -0.0 : l; // p == 1: the bits of +0.0 are the dead keys' alone
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+        n_dead += __shfl_xor(n_dead, off, kWave);
+    if (lane == 0) {
+        tl[pt] = t;
+        dead[pt] = n_dead;
+    }
+}
+
+// grid: x = groups of 64 points (from x0 on), y = groups of 4 histogram tiles; a wave = one tile of 16 histograms
+__global__ __launch_bounds__(256) void batch_cross_kernel(const double *__restrict__ H, const double *__restrict__ tails,
+                                                          const int64_t n_hist, const double *__restrict__ L,
+                                                          const double *__restrict__ tl, const int64_t n, const int64_t nk,
+                                                          double *__restrict__ out, const int64_t ld, const int64_t x0)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int r = lane & 15, kq = lane >> 4;
+    const int64_t b0 = ((int64_t)blockIdx.y * kWavesPerBlock + (threadIdx.x / kWave)) * 16;
+    const int64_t i0 = (x0 + (int64_t)blockIdx.x) * 64;
+    if (b0 >= n_hist || i0 >= n)
+        return; // wave-uniform: the MFMAs below run with every lane
+    const bool b_ok = b0 + r < n_hist;
+    const double *hrow = H + (b_ok ? b0 + r : 0) * nk;
+    bool i_ok[4];
+    const double *lrow[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int64_t i = i0 + t * 16 + r;
+        i_ok[t] = i < n;
+        lrow[t] = L + (i_ok[t] ? i : 0) * nk;
+    }
+    double4_t acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        acc[t] = double4_t{0.0, 0.0, 0.0, 0.0};
+    for (int64_t j0 = 0; j0 < nk; j0 += 16) {
+        const int64_t j = j0 + 4 * kq;
+        double a[4], b[4][4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const bool in = j + s < nk;
+            a[s] = (b_ok && in) ? hrow[j + s] : 0.0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                b[t][s] = (i_ok[t] && in) ? lrow[t][j + s] : 0.0;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[t][s], acc[t], 0, 0, 0);
+    }
+    // D: column (point) = lane & 15, row (histogram) = kq + 4 * reg
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int64_t i = i0 + t * 16 + r;
+        if (i >= n)
+            continue;
+        const double tl_i = tl[i];
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int64_t b = b0 + kq + 4 * reg;
+            if (b < n_hist)
+                out[b * ld + i] = acc[t][reg] + tails[b] * tl_i;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void batch_fix_dead_kernel(const double *__restrict__ H, const int64_t n_hist,
+                                                             const double *__restrict__ L, const int64_t nk,
+                                                             const int32_t *__restrict__ dead_list, const int64_t n_dead,
+                                                             double *out, const int64_t ld, const int64_t w0)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t w = w0 + (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x / kWave);
+    if (w >= n_hist * n_dead)
+        return; // wave-uniform
+    const int64_t b = w / n_dead, i = dead_list[w % n_dead];
+    const double *hrow = H + b * nk, *lrow = L + i * nk;
+    bool hit = false;
+    for (int64_t j = lane; j < nk; j += kWave)
+        hit = hit || (hrow[j] != 0.0 && is_dead_entry(lrow[j]));
+    if (__any(hit) && lane == 0) {
+        const double v = out[b * ld + i];
+        if (v == v) // (a NaN stays: NaN + -inf is NaN in the reference's sum)
+            out[b * ld + i] = -INFINITY;
+    }
+}
+
+__global__ __launch_bounds__(256) void batch_pairs_kernel(const double *__restrict__ H, const double *__restrict__ tails,
+                                                          const int64_t *__restrict__ index, const double *__restrict__ L,
+                                                          const double *__restrict__ tl, const int64_t n, const int64_t nk,
+                                                          double *__restrict__ out, const int64_t w0)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t i = w0 + (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x / kWave);
+    if (i >= n)
+        return; // wave-uniform
+    const int64_t b = index[i];
+    const double *hrow = H + b * nk, *lrow = L + i * nk;
+    double acc = 0.0;
+    bool hit = false;
+    for (int64_t j = lane; j < nk; j += kWave) {
+        const double h = hrow[j], l = lrow[j];
+        acc += h * l;
+        hit = hit || (h != 0.0 && is_dead_entry(l));
+    }
+    double v = wave_sum(acc) + tails[b] * tl[i];
+    if (__any(hit) && v == v)
+        v = -INFINITY;
+    if (lane == 0)
+        out[i] = v;
+}
+
+__global__ void batch_argmin_init_kernel(const int64_t n_hist, double *run_val, int64_t *run_idx)
+{
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < n_hist) {
+        run_val[b] = INFINITY;
+        run_idx[b] = -1;
+    }
+}
+
+__global__ __launch_bounds__(256) void batch_argmin_kernel(const double *__restrict__ ll, const int64_t ld,
+                                                           const int64_t n_hist, const int64_t n, const int64_t first,
+                                                           double *run_val, int64_t *run_idx, const int64_t w0)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t b = w0 + (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x / kWave);
+    if (b >= n_hist)
+        return; // wave-uniform
+    double best = INFINITY;
+    long long at = -1;
+    for (int64_t i = lane; i < n; i += kWave) { // ascending per lane: the first of equal values stays
+        const double v = -ll[b * ld + i];
+        if (v < best) { // (NaN never wins; +inf neither)
+            best = v;
+            at = i;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ov = __shfl_xor(best, off, kWave);
+        const long long oa = __shfl_xor(at, off, kWave);
+        if (oa >= 0 && (ov < best || (ov == best && oa < at))) { // (at >= 0 wherever best < +inf)
+            best = ov;
+            at = oa;
+        }
+    }
+    if (lane == 0 && at >= 0 && best < run_val[b]) { // an earlier chunk keeps a tie: its index is the lower
+        run_val[b] = best;
+        run_idx[b] = first + at;
+    }
+}
+
+__global__ __launch_bounds__(256) void batch_from_draw_kernel(const int64_t *__restrict__ draw, const int64_t n_hist,
+                                                              const int64_t nk, const int has_tail, double *__restrict__ H,
+                                                              double *__restrict__ tails)
+{
+    const int64_t m = nk + (has_tail ? 1 : 0), total = n_hist * m;
+    for (int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; at < total; at += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = at / m, c = at - b * m;
+        if (c < nk)
+            H[b * nk + c] = (double)draw[at];
+        else
+            tails[b] = (double)draw[at];
+        if (!has_tail && c == 0)
+            tails[b] = 0.0;
+    }
+}
+
+} // namespace
+
+hipError_t launch_batch_table(const DevModel &m, const PointSource &src, int64_t n, double *table, double *tl, int32_t *dead,
+                              bool keep_p, hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    const int P = m.kind == 0 ? 2 : 5;
+    const int64_t per_launch = kWavesPerBlock * kMaxBlocks;
+    for (int64_t k = 0; k < batch_launch_parts(n, per_launch); ++k) {
+        int64_t first, cnt;
+        batch_launch_part(n, per_launch, k, &first, &cnt);
+        const dim3 grid((unsigned)((cnt + kWavesPerBlock - 1) / kWavesPerBlock)), block(kWavesPerBlock * kWave);
+        PointSource part = src;
+        part.params = src.params + first * P;
+        part.t_list = src.t_list ? src.t_list + first : nullptr;
+        double *rows = table + first * m.bins.n;
+        if (m.kind == 0)
+            hipLaunchKernelGGL((batch_table_kernel<2>), grid, block, 0, stream, m, part, cnt, rows, tl + first, dead + first,
+                               keep_p ? 1 : 0);
+        else
+            hipLaunchKernelGGL((batch_table_kernel<5>), grid, block, 0, stream, m, part, cnt, rows, tl + first, dead + first,
+                               keep_p ? 1 : 0);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_cross(const double *H, const double *tails, int64_t n_hist, const double *table, const double *tl,
+                              int64_t n, int64_t n_keys, double *out, int64_t ld, int64_t *tiles, hipStream_t stream)
+{
+    if (tiles)
+        *tiles = 0;
+    if (n_hist <= 0 || n <= 0)
+        return hipSuccess;
+    if (n_hist > kBatchMaxHist)
+        return hipErrorInvalidValue;
+    const int64_t tiles_y = (n_hist + 15) / 16, gy = batch_cross_groups_y(n_hist), gx = batch_cross_groups_x(n);
+    const int64_t x_per = batch_cross_x_per_launch(gy, kMaxBlocks);
+    for (int64_t k = 0; k < batch_launch_parts(gx, x_per); ++k) {
+        int64_t x0, cnt;
+        batch_launch_part(gx, x_per, k, &x0, &cnt);
+        hipLaunchKernelGGL(batch_cross_kernel, dim3((unsigned)cnt, (unsigned)gy), dim3(kWavesPerBlock * kWave), 0, stream, H,
+                           tails, n_hist, table, tl, n, n_keys, out, ld, x0);
+    }
+    if (tiles)
+        *tiles = tiles_y * ((n + 15) / 16);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_fix_dead(const double *H, int64_t n_hist, const double *table, int64_t n_keys,
+                                 const int32_t *dead_list, int64_t n_dead, double *out, int64_t ld, hipStream_t stream)
+{
+    const int64_t waves = n_hist * n_dead;
+    if (waves <= 0)
+        return hipSuccess;
+    const int64_t per_launch = kWavesPerBlock * kMaxBlocks;
+    for (int64_t k = 0; k < batch_launch_parts(waves, per_launch); ++k) {
+        int64_t w0, cnt;
+        batch_launch_part(waves, per_launch, k, &w0, &cnt);
+        hipLaunchKernelGGL(batch_fix_dead_kernel, dim3((unsigned)((cnt + kWavesPerBlock - 1) / kWavesPerBlock)),
+                           dim3(kWavesPerBlock * kWave), 0, stream, H, n_hist, table, n_keys, dead_list, n_dead, out, ld, w0);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_pairs(const double *H, const double *tails, const int64_t *index, const double *table,
+                              const double *tl, int64_t n, int64_t n_keys, double *out, hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    const int64_t per_launch = kWavesPerBlock * kMaxBlocks;
+    for (int64_t k = 0; k < batch_launch_parts(n, per_launch); ++k) {
+        int64_t w0, cnt;
+        batch_launch_part(n, per_launch, k, &w0, &cnt);
+        hipLaunchKernelGGL(batch_pairs_kernel, dim3((unsigned)((cnt + kWavesPerBlock - 1) / kWavesPerBlock)),
+                           dim3(kWavesPerBlock * kWave), 0, stream, H, tails, index, table, tl, n, n_keys, out, w0);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_argmin_init(int64_t n_hist, double *run_val, int64_t *run_idx, hipStream_t stream)
+{
+    if (n_hist <= 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(batch_argmin_init_kernel, dim3((unsigned)((n_hist + 255) / 256)), dim3(256), 0, stream, n_hist,
+                       run_val, run_idx);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_argmin(const double *ll, int64_t ld, int64_t n_hist, int64_t n, int64_t first, double *run_val,
+                               int64_t *run_idx, hipStream_t stream)
+{
+    if (n_hist <= 0 || n <= 0)
+        return hipSuccess;
+    const int64_t per_launch = kWavesPerBlock * kMaxBlocks;
+    for (int64_t k = 0; k < batch_launch_parts(n_hist, per_launch); ++k) {
+        int64_t w0, cnt;
+        batch_launch_part(n_hist, per_launch, k, &w0, &cnt);
+        hipLaunchKernelGGL(batch_argmin_kernel, dim3((unsigned)((cnt + kWavesPerBlock - 1) / kWavesPerBlock)),
+                           dim3(kWavesPerBlock * kWave), 0, stream, ll, ld, n_hist, n, first, run_val, run_idx, w0);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_from_draw(const int64_t *draw, int64_t n_hist, int64_t n_keys, bool has_tail, double *H,
+                                  double *tails, hipStream_t stream)
+{
+    const int64_t total = n_hist * (n_keys + (has_tail ? 1 : 0));
+    if (total <= 0)
+        return hipSuccess;
+    const int64_t blocks = std::min<int64_t>((total + 255) / 256, (int64_t)1 << 16);
+    hipLaunchKernelGGL(batch_from_draw_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, draw, n_hist, n_keys,
+                       has_tail ? 1 : 0, H, tails);
+    return hipGetLastError();
+}
+
+} // namespace covest

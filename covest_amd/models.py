@@ -212,6 +212,11 @@ class BasicModel:
         self._grids = [g for g in self._grids if g() is not None]
         self._grids.append(weakref.ref(grid))
 
+    def _register_batch(self, batch):
+        """A histogram batch borrows its model as a grid does (HistogramBatch calls this): closed with the grids,
+        before the model's handle goes."""
+        self._register_grid(batch)
+
     def close(self):
         for ref in getattr(self, '_grids', []):
             grid = ref()

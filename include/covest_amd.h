@@ -506,6 +506,46 @@ int covest_draw_histograms(int32_t device, int64_t m, const double *weights, int
 int covest_draw_histograms_device(int32_t device, int64_t m, const uint64_t *d_thresholds, int64_t n_draws,
                                   int64_t first_rep, int64_t n_rep, uint64_t seed, int64_t *d_out, void *stream);
 
+/* ---- histogram batches: many histograms on ONE model's key set, scored in one pass ----
+ * A batch is n_hist histograms (rows of n_keys counts in the model's key order, and a tail each) that share the model's
+ * keys, k, r, comb, bounds and threshold.  For a fixed key set p_j(theta) does not depend on the counts, so
+ *   LL_b(theta_i) = sum_j h_bj log p_j(theta_i) + tail_b [sp_i < 1] log(1 - sp_i),   sp_i = min(1, fsum(p_j(theta_i)))
+ * is ONE evaluation of p per point -- K-direct's arithmetic at the point after fit_to_bounds, bit for bit what
+ * covest_probabilities(clamp = 1) returns -- and a contraction with the counts.  Every key of the model enters sp_i,
+ * whatever the model's own tail is; a key with h_bj = 0 contributes nothing; a key with h_bj != 0 and p_j <= 0 makes the
+ * value -inf (the reference's h * safe_log(0); NaN where another counted key's p_j is NaN).
+ *   covest_batch_create     counts[n_hist * n_keys] and tails[n_hist] (NULL: all 0) are HOST doubles, finite and >= 0.
+ *   covest_batch_draw       n_hist replicates (first_rep .. of the stream of `seed`) of n_draws draws over the model's
+ *                           cells at `params`: p_j at every key and, where the model's tail != 0, one more cell
+ *                           max(0, 1 - fsum(p)) whose count becomes the replicate's tail -- the rows covest_draw_histograms
+ *                           gives for these weights, bit for bit.  The histograms never leave the device.
+ *   covest_batch_counts     the histograms back: out_counts[n_hist * n_keys], out_tails[n_hist].
+ *   covest_batch_eval_cross every histogram at every point: out_ll[b * n + i], row-major [n_hist][n].
+ *   covest_batch_eval_pairs histogram hist_index[i] at point i: out_ll[n].  One launch pair for many requests.
+ *   covest_batch_argmin_cross  per histogram the first index with the strictly smallest -LL over the points (NaN never
+ *                           wins: covest/grid.py:65-70) and that value; (-1, +inf) where nothing is below +inf.  The
+ *                           values never leave the device.
+ *   covest_batch_info       out[8], of the last evaluation on the batch: points tabled, table chunks, 16 x 16 output
+ *                           tiles the cross contraction covered, points with keys of p <= 0, fix-up waves launched
+ *                           (one per such point and histogram), pairs requests, and the device time in nanoseconds of
+ *                           the table kernels and of the contraction kernels.
+ * params is [n][param_count] as for covest_eval_points.  The table of log p is built for at most 256 MiB of points at
+ * a time; the chunking changes no value.  A batch has NO gradient.
+ * A batch borrows its model: destroy the batch first.  Every call takes the model's lock and runs on the model's
+ * device.  COVEST_E_INVALID: a NULL argument, a negative size, a count or tail that is negative, NaN or infinite, more
+ * than 2^20 histograms, an index outside 0 .. n_hist - 1, a model without keys, and for covest_batch_draw what
+ * covest_draw_histograms refuses.  An empty point list or an empty batch: COVEST_OK, nothing written. */
+typedef struct covest_batch covest_batch; /* opaque */
+int covest_batch_create(covest_model *m, int64_t n_hist, const double *counts, const double *tails, covest_batch **out);
+int covest_batch_draw(covest_model *m, const double *params, int64_t n_draws, int64_t first_rep, int64_t n_hist,
+                      uint64_t seed, covest_batch **out);
+int covest_batch_counts(covest_batch *b, double *out_counts, double *out_tails);
+int covest_batch_eval_cross(covest_batch *b, int64_t n, const double *params, double *out_ll);
+int covest_batch_eval_pairs(covest_batch *b, int64_t n, const int64_t *hist_index, const double *params, double *out_ll);
+int covest_batch_argmin_cross(covest_batch *b, int64_t n, const double *params, double *out_min_negll, int64_t *out_arg);
+int covest_batch_info(covest_batch *b, int64_t *out);
+void covest_batch_destroy(covest_batch *b);
+
 /* ---- histogram down-sampling: covest/histogram.py:47-70 sample_histogram ----
  * Expected counts of the histogram after keeping every read with probability 1/factor, BEFORE the
  * reference's randomised rounding (:71-74, host side): out[j-1] = sum_i counts_i * pmf_i(j) for
