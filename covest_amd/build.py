@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libcovest_amd.so")
 SOURCES = [("host_common.cpp", (), "host_common"), ("tiles_host.cpp", (), "tiles_host"), ("plan_factored.cpp", (), "plan_factored"),
            ("abi_model.cpp", (), "abi_model"), ("abi_grid.cpp", (), "abi_grid"), ("kmer_host.cpp", (), "kmer_host"),
            ("thin_host.cpp", (), "thin_host"), ("abi_tp.cpp", (), "abi_tp"), ("reads_io.cpp", (), "reads_io"), ("ll_direct.hip", (), "ll_direct"),
-           ("ll_basic.hip", (), "ll_basic"), ("ll_factored.hip", (), "ll_factored"), ("argmin.hip", (), "argmin"), ("axis_min.hip", (), "axis_min"), ("ll_deriv.hip", (), "ll_deriv"),
+           ("ll_basic.hip", (), "ll_basic"), ("ll_factored.hip", (), "ll_factored"), ("argmin.hip", (), "argmin"), ("ll_fix.hip", (), "ll_fix"), ("axis_min.hip", (), "axis_min"), ("ll_deriv.hip", (), "ll_deriv"),
            ("kmer_count.hip", (), "kmer_count"), ("kmer_wide.hip", (), "kmer_wide"), ("kmer_bulk.hip", (), "kmer_bulk"), ("thin_hist.hip", (), "thin_hist"),
            ("tp_eval.hip", (), "tp_eval"), ("abi_sim.cpp", (), "abi_sim"), ("sim_reads.hip", (), "sim_reads"),
            ("abi_sample.cpp", (), "abi_sample"), ("sample_reads.hip", (), "sample_reads"),

@@ -273,14 +273,14 @@ SubList sub_list_of(const covest_model *m, int t_max, void *index, void *word, v
     l.index = static_cast<int64_t *>(index);
     l.word = static_cast<unsigned long long *>(word);
     l.index_offset = 0;
-#ifdef COVEST_DIAG // diagnostic builds only (direct_point.h SubList::diag_class): the shipped library has no knobs
+#ifdef COVEST_DIAG // diagnostic builds only (handback.h SubList::diag_class): the shipped library has no knobs
     const char *dc = std::getenv("COVEST_DIAG_BASIC_CLASS");
     l.diag_class = dc ? std::atoi(dc) : 0;
 #endif
     return l;
 }
 
-// `sub`: the queue the recurrence kernels append the points they hand back to (direct_point.h) -- drained right
+// `sub`: the queue the recurrence kernels append the points they hand back to (handback.h) -- drained right
 // behind them by the fix pass; K-direct has nothing to hand back.  The queue must be empty (counter 0) on entry.
 hipError_t launch_ll(const covest_model *m, int kernel, const PointSource &src, int64_t n, double *out, const SubList &sub,
                      hipStream_t st, const char **name, const covest_grid *g)
@@ -305,7 +305,7 @@ hipError_t launch_ll(const covest_model *m, int kernel, const PointSource &src, 
 
 constexpr int64_t kInPlaceMaxListPoints = 4; // repeats model, list mode: tables read in place (13 KB a point, 8 workgroups each)
 
-// The queue a point-list launch hands points back through (direct_point.h): room for n entries, empty.  The counter is
+// The queue a point-list launch hands points back through (handback.h): room for n entries, empty.  The counter is
 // zeroed without waiting for it: whatever touches it afterwards -- the kernels, the blocking copies of fix_points_host
 // -- is work of the same null stream and comes behind the fill, and the host never reads it.
 static int reserve_point_queue(covest_model *m, int64_t n)
@@ -534,7 +534,7 @@ static int list_points_direct(covest_model *m, const double *params, const std::
     return download_values(m, idx, out_ll);
 }
 
-// Add the strict evaluation of the keys list mode 1 handed back (words[i] != 0, direct_point.h) to out_ll[i].
+// Add the strict evaluation of the keys list mode 1 handed back (words[i] != 0, handback.h) to out_ll[i].
 static int fix_points_host(covest_model *m, int64_t n, const double *params, const std::vector<int32_t> &t, double *out_ll,
                            const std::vector<unsigned long long> &words)
 {
@@ -586,7 +586,7 @@ static int eval_points_list(covest_model *m, int64_t n, const double *params, do
     HIP_TRY(m->ws_params.reserve((size_t)n * 5 * sizeof(double)));
     HIP_TRY(m->ws_t.reserve((size_t)n * sizeof(int32_t)));
     const SubList none = sub_list_of(m, kListLanes + 1, nullptr, nullptr, nullptr); // (list mode and K-direct hand nothing back)
-    std::vector<unsigned long long> words((size_t)n, 0ull); // keys handed back per point (direct_point.h)
+    std::vector<unsigned long long> words((size_t)n, 0ull); // keys handed back per point (handback.h)
     int rc = fits.empty() ? COVEST_OK : list_points_fitting(m, params, t, fits, none, out_ll, words);
     if (rc == COVEST_OK && !big.empty())
         rc = list_points_chunked(m, params, t, big, none, out_ll);

@@ -1,5 +1,5 @@
 // cand.h -- the candidate of the selection scan of covest/grid.py:65-70 and its comparison, shared by the kernels
-// that restate it (argmin.hip over a whole block, axis_min.hip per cell of the kept axes).
+// that restate it (argmin.hip over a whole block, axis_min.hip per cell of the kept axes, ll_batch.hip per histogram of a batch).
 #pragma once
 #include <hip/hip_runtime.h>
 

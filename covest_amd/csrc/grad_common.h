@@ -1,5 +1,6 @@
 // grad_common.h -- what the derivative kernels (K-grad and K-hess, ll_deriv.hip) need beside the walk: the derivatives of the
-// log of the truncated Poisson's normaliser inside each of its pieces, and the compensated (hi, lo) sums a segment leaves.
+// log of the truncated Poisson's normaliser inside each of its pieces.  (The compensated (hi, lo) sums a segment leaves:
+// wave.h comp_merge, wave_comp_reduce.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,25 +53,6 @@ __device__ __forceinline__ void trunc_norm_dlog2(double x, double &d1, double &d
         d1 = -1.0 / em;
         d2 = -(em + 1.0) * d1 * d1;
     }
-}
-
-// (hi, lo) += (ohi, olo), as wave_comp_sum's step
-__device__ __forceinline__ void comp_merge(CompSum &v, double ohi, double olo)
-{
-    double e;
-    two_sum(v.hi, ohi, v.hi, e);
-    v.lo += olo + e;
-}
-
-__device__ __forceinline__ CompSum wave_comp_reduce(CompSum v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double ohi = __shfl_xor(v.hi, off, kWave);
-        const double olo = __shfl_xor(v.lo, off, kWave);
-        comp_merge(v, ohi, olo);
-    }
-    return v;
 }
 
 } // namespace covest

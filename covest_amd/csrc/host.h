@@ -31,7 +31,7 @@
 
 #include "../../include/covest_amd.h"
 #include "device_model.h"
-#include "direct_point.h"
+#include "handback.h"
 #include "kernels.h"
 
 namespace covest {
@@ -278,7 +278,7 @@ struct covest_model {
     // list mode keeps its parameters out of it.  ws_result: what a short list's kernels write for the host in place --
     // values (and gradients, Hessians), or list mode 1's parts.
     HostBuf ws_stage, ws_result;
-    DevBuf ws_sub_index, ws_sub_word, ws_sub_ctl; // the queue of handed-back points of a point-list launch (direct_point.h)
+    DevBuf ws_sub_index, ws_sub_word, ws_sub_ctl; // the queue of handed-back points of a point-list launch (handback.h)
     LaunchRecord record; // what the last covest_eval_points launched (covest_model_launch_record)
     std::mutex lock;
 };
@@ -400,7 +400,7 @@ struct HostBin {
 int upload_bins(DevBuf &buf, BinView &view, const std::vector<double> &key, const std::vector<double> &lgam,
                 const std::vector<double> &cnt);
 int build_tiles(covest_model *m, std::vector<HostBin> bins);
-double clamp_for(const covest_model *m, int t_max); // p_clamp of direct_point.h for a launch whose largest threshold_o is t_max
+double clamp_for(const covest_model *m, int t_max); // p_clamp of handback.h for a launch whose largest threshold_o is t_max
 
 // ---- abi_grid.cpp: staging of a grid handle's uploads (see covest_grid::stage)
 struct StageSlot {

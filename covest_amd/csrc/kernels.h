@@ -6,7 +6,7 @@
 #include <cstddef>
 
 #include "device_model.h"
-#include "direct_point.h"
+#include "handback.h"
 #include "kmer_plan.h"
 #include "tiles.h"
 
@@ -16,7 +16,7 @@ namespace covest {
 // Host bookkeeping only.  A launcher notes the instantiation it picked and how many launches it took into the record
 // of the evaluation in progress on the calling thread (LaunchRecordScope; none: nothing is noted).  Nothing is read from
 // the device and nothing waits for it.  The names come from the tables beside the instantiation lists (kVariantNames of
-// ll_factored.hip, ll_basic.hip, argmin.hip and ll_deriv.hip); covest_compiled_variants lists those tables.
+// ll_factored.hip, ll_basic.hip, ll_fix.hip, argmin.hip and ll_deriv.hip); covest_compiled_variants lists those tables.
 struct LaunchRecord {
     struct Entry {
         const char *name;
@@ -44,7 +44,7 @@ constexpr int kFactoredVariants = 10, kBasicVariants = 8, kFixVariants = 6, kArg
 extern const char *const kFactoredVariantNames[kFactoredVariants]; // ll_factored.hip
 extern const char *const kFactoredFinishNames[2];                   // ll_factored.hip: ll_finish_dense, ll_finish_partials
 extern const char *const kBasicVariantNames[kBasicVariants];       // ll_basic.hip
-extern const char *const kFixVariantNames[kFixVariants];           // argmin.hip
+extern const char *const kFixVariantNames[kFixVariants];           // ll_fix.hip
 extern const char *const kArgminVariantNames[kArgminVariants];     // argmin.hip
 extern const char *const kDerivVariantNames[kDerivVariants];       // ll_deriv.hip: six ll_deriv<P,mode>, then ll_deriv_finish
 
@@ -57,13 +57,13 @@ hipError_t launch_ll_direct(const DevModel &m, const PointSource &src, int64_t n
 
 // K-basic: basic model, one lane per grid point, pmf recurrence (ll_basic.hip).
 // Needs n_err == 8 and a tile table (keys in 1..16384).
-// sub_list: the queue of points handed back (direct_point.h); run launch_ll_fix_list after this.
+// sub_list: the queue of points handed back (handback.h); run launch_ll_fix_list after this.
 hipError_t launch_ll_basic(const DevModel &m, const TileView &tv, const PointSource &src, int64_t n,
                            double *out_ll, const SubList &sub_list, hipStream_t stream);
 
 // K-factored: repeats model on a dense grid, one workgroup per (c, e)
 // (ll_factored.hip).  out_ll is the block's LL buffer (index flat - plan.flat_begin).
-// sub_list: the queue of points handed back (direct_point.h; dense grids -- list mode 1 hands the side words over
+// sub_list: the queue of points handed back (handback.h; dense grids -- list mode 1 hands the side words over
 // in `partial`, list mode 2 leaves the strict evaluation to ll_finish_partials); run launch_ll_fix_list after this.
 hipError_t launch_ll_factored(const DevModel &m, const TileView &tv, const FactoredPlan &plan,
                               double *out_ll, const SubList &sub_list, hipStream_t stream);
@@ -82,7 +82,7 @@ hipError_t launch_ll_finish_dense(const DevModel &m, const TileView &tv, const P
                                   int64_t ce_first, int64_t n_ce, int64_t n_cols, const int32_t *q_orig, int64_t n_q,
                                   int64_t flat_end, double *out_ll, hipStream_t stream);
 
-// The pass after every K-basic / K-factored launch: one wave per point of the queue `list` (direct_point.h) adds
+// The pass after every K-basic / K-factored launch (ll_fix.hip): one wave per point of the queue `list` (handback.h) adds
 // the strict evaluation of the rows named in its side word to ll[], in place.  The queue's counter must be zero
 // before the NEXT recurrence launch: launch_argmin resets it (grids), the host does for point lists.
 // n_points: how many points the launch before evaluated (the queue cannot be longer; 0: unknown) -- sizes the launch.

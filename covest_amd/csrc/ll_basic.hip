@@ -21,7 +21,7 @@
 
 #include <type_traits>
 
-#include "direct_point.h"
+#include "handback.h"
 #include "fastmath.h"
 #include "kernels.h"
 #include "point_fetch.h"
@@ -98,13 +98,13 @@ __device__ __forceinline__ void ll_basic_body(const DevModel &m, const int32_t n
 
     double acc_ll = 0.0;
     uint64_t dead = 0; // lanes that met a p_j <= 0 with h_j != 0
-    unsigned long long subw = 0; // the rows this lane hands back (direct_point.h): first and last
+    unsigned long long subw = 0; // the rows this lane hands back (handback.h): first and last
     const double p_clamp = sub_list.p_clamp;
     CompSum acc_sp = {0.0, 0.0};
 
     // one key's p_j, TIMES 2^64 (tiles.h kBasicShift: the scales of the tile table carry the factor, so the product
     // of the streams' sum and the key's scale does not flush to 0 below half a grid step of the doubles -- the
-    // reference's own roundings keep a p_j alive down to a quarter of one, direct_point.h kZeroSteps): into sp_j, and
+    // reference's own roundings keep a p_j alive down to a quarter of one, handback.h kZeroSteps): into sp_j, and
     // its log, the 2^-64 folded into the log's exponent arithmetic (all branches wave-uniform)
     const double clamp_s = p_clamp * kBasicScale;
     const double zero_s = zero_steps_scaled(kBasicScale);
@@ -119,7 +119,7 @@ __device__ __forceinline__ void ll_basic_body(const DevModel &m, const int32_t n
             tile_sp += ps; // (filler keys have scale 0: p == 0)
         if (h != 0.0) { // filler keys and zero counts: no log (`if h`, covest/models.py:106)
             // log(max(p_j, p_clamp)): what a p_j deep in the subnormal range contributes is then a known constant,
-            // which the strict evaluation of that key replaces later (direct_point.h); p_j = 0 is remembered below
+            // which the strict evaluation of that key replaces later (handback.h); p_j = 0 is remembered below
             const double xs[1] = {max_raw(ps, clamp_s)};
             double lg[1];
             fast_log_bits_n<1, 5, kBasicShift>(xs, lg, log_tab);
@@ -256,7 +256,7 @@ __device__ __forceinline__ void ll_basic_body(const DevModel &m, const int32_t n
     // and the rest of the sum over the counted keys is three multiply-adds against sums the host made once per
     // histogram (tiles.h suf_*):  c_0 sum h_j + ln x_0 sum j h_j - sum h_j ln j!.  It stands where every p_j is an
     // ordinary double: log p_j is concave in j, so its smallest value over the remaining counted keys is at the first
-    // or the last of them, and that is compared with the clamp of direct_point.h.  Below e^-746 at either end p_j is 0
+    // or the last of them, and that is compared with the clamp of handback.h.  Below e^-746 at either end p_j is 0
     // in the reference (its cast to double flushes below 2^-1075 = e^-745.13, c_src/covest_poissonmodule.c:32, and
     // a_0 <= 1) and the sum -inf (utils.safe_log).  A lane in between -- a p_j near or in the subnormal range -- sends
     // its WAVE through the key-by-key walk, which names the rows for the strict evaluation; in a grid that is a band
@@ -398,7 +398,7 @@ __device__ __forceinline__ void ll_basic_body(const DevModel &m, const int32_t n
 #endif
     if (live) {
         out_ll[pt] = ll;
-        if (subw != 0) // (rare) queue the point for ll_fix_list_kernel
+        if (subw != 0) // (rare) queue the point for the strict pass (ll_fix.hip)
             sub_list.push(pt + sub_list.index_offset, subw);
     }
 }

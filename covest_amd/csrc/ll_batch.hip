@@ -33,6 +33,7 @@
 #include <algorithm>
 
 #include "batch_host.h"
+#include "cand.h"
 #include "direct_point.h"
 #include "kernels.h"
 
@@ -204,27 +205,20 @@ __global__ __launch_bounds__(256) void batch_argmin_kernel(const double *__restr
     const int64_t b = w0 + (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x / kWave);
     if (b >= n_hist)
         return; // wave-uniform
-    double best = INFINITY;
-    long long at = -1;
+    Cand c;
+    c.v = INFINITY;
+    c.i = INT64_MAX; // none yet (cand.h)
     for (int64_t i = lane; i < n; i += kWave) { // ascending per lane: the first of equal values stays
         const double v = -ll[b * ld + i];
-        if (v < best) { // (NaN never wins; +inf neither)
-            best = v;
-            at = i;
+        if (v < c.v) { // (NaN never wins; +inf neither)
+            c.v = v;
+            c.i = i;
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double ov = __shfl_xor(best, off, kWave);
-        const long long oa = __shfl_xor(at, off, kWave);
-        if (oa >= 0 && (ov < best || (ov == best && oa < at))) { // (at >= 0 wherever best < +inf)
-            best = ov;
-            at = oa;
-        }
-    }
-    if (lane == 0 && at >= 0 && best < run_val[b]) { // an earlier chunk keeps a tie: its index is the lower
-        run_val[b] = best;
-        run_idx[b] = first + at;
+    c = wave_best(c);
+    if (lane == 0 && c.i != INT64_MAX && c.v < run_val[b]) { // an earlier chunk keeps a tie: its index is the lower
+        run_val[b] = c.v;
+        run_idx[b] = first + c.i; // (run_idx stays at the host's -1 while nothing is < +inf)
     }
 }
 

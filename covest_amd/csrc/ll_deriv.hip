@@ -147,7 +147,8 @@ __global__ __launch_bounds__(kDerivWaves *kWave) void ll_deriv_kernel(const DevM
         double inner = 0.0, inner_c = 0.0, inner_e = 0.0, inner_cc = 0.0, inner_ce = 0.0, inner_ee = 0.0;
 
         for (int o0 = 1; o0 < T; o0 += OT) {
-            // ---- lane-parallel preparation of up to OT*S mixture components (as direct_point_ll) ----
+            // ---- lane-parallel preparation of up to OT*S mixture components (as prepare_mix_lot, mix_lot.h, with the
+            // derivatives of tot summed in the same shuffle loop) ----
             const int o = o0 + og;
             const bool live = lane_in_tile && o < T;
             const double od = (double)o;

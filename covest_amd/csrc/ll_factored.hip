@@ -33,8 +33,8 @@
 //     only; below the tile's smallest cut-off the contraction is then beta_col times a sum that does not depend
 //     on the column -- summed once per key on the vector unit (Horner in (1-q)^-4) and brought in by ONE MFMA;
 //   * the four logs of a unit go through fast_log_n stage by stage (their table reads in flight together);
-//   * a p_j deep in the subnormal range is clamped and its row recorded: ll_fix_list_kernel (argmin.hip) redoes
-//     those rows with K-direct's arithmetic (direct_point.h).
+//   * a p_j deep in the subnormal range is clamped and its row recorded: ll_fix_list_kernel (ll_fix.hip) redoes
+//     those rows with K-direct's arithmetic (mix_lot.h).
 //
 // The unit of phases B/C is (q-tile of 16 weight vectors, half of the key tile);
 // the host deals units to waves longest-first, balanced per SIMD (tiles.h), and a
@@ -53,7 +53,8 @@
 #include <mutex>
 #include <type_traits>
 
-#include "direct_point.h"
+#include "direct_point.h" // strict_pj_wave, for finish_point
+#include "handback.h"
 #include "fastmath.h"
 #include "kernels.h"
 #include "point_fetch.h"
@@ -67,7 +68,7 @@ namespace {
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 // The chunks' shares of p_j (list modes 2 and 3, tiles.h) travel through HBM TIMES 2^128: p_j <= 2.5, so nothing
-// overflows, and a p_j below half a grid step -- which the reference's roundings may still keep alive, direct_point.h
+// overflows, and a p_j below half a grid step -- which the reference's roundings may still keep alive, handback.h
 // kZeroSteps -- does not flush to 0 on the way: finish_point decides on the exact value.
 constexpr double kShareScale = 0x1p128;
 
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     const FactoredLds lay{NT, plan.n_buf, LD, SPO}; // every offset into Gs (tiles.h)
     extern __shared__ double Gs[]; // G's buffers; reused for the final per-q combine
     __shared__ __attribute__((aligned(16))) double log_tab[kLogTableDoubles];
-    // rows handed back (direct_point.h), per accumulator slot and weight vector: first unit, last unit + 1 (0: none;
+    // rows handed back (handback.h), per accumulator slot and weight vector: first unit, last unit + 1 (0: none;
     // a unit = the 16 rows of a half tile: index 2 * tile + half).  One writer per entry: the lane with kq == 0.
     __shared__ unsigned sub_rec[NE * 2];
     // per row of the key tile being logged and of the next one: {h_j, p_clamp in the row's units (0: no count -- such
@@ -161,8 +162,8 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-    const double p_clamp = plan.p_clamp; // direct_point.h
-    const double zero_frac = kZeroSteps * (kGridStep / p_clamp); // direct_point.h kZeroSteps, in units of p_clamp
+    const double p_clamp = plan.p_clamp; // handback.h
+    const double zero_frac = kZeroSteps * (kGridStep / p_clamp); // handback.h kZeroSteps, in units of p_clamp
     const int list_mode = PLAIN ? 0 : plan.list_mode;
 
     // ---- the (c, e) of this workgroup ----
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     const int n_pass = PLAIN ? 1 : plan.n_pass; // lanes per copy number: one per 8 error classes (1 when max_error <= 8)
     // (by multiplication, as K-basic forms them -- point_fetch.h error_class_rate_mul, round 5: the device library's two
     // pows were 420 dependent instructions that every wave of the workgroup waited for at the barrier below; the strict
-    // re-evaluation of the rows handed back, argmin.hip, forms the same products)
+    // re-evaluation of the rows handed back, ll_fix.hip, forms the same products)
     if (tid < 8 * n_pass)
         Gs[lay.rates() + tid] = error_class_rate_mul(m, par[0], par[1], tid, m.n_err);
     if (wave == NW - 1) { // the items' constants: one load per lane and 64 items, added in a fixed order
@@ -916,7 +917,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                 // (a dead unit's bit of m_first is cleared: nothing it could add changes its -inf)
                 if (((m_first >> k) & 1u) && !COVEST_SKIP_PHASE(plan, 4)) { // wave-uniform: first slot of a unit
                     // Everything out of the ordinary -- p_j <= 0, or deep in the subnormal range (below p_clamp,
-                    // direct_point.h), at a key with h_j != 0 -- is caught by ONE compare per row against the clamp in
+                    // handback.h), at a key with h_j != 0 -- is caught by ONE compare per row against the clamp in
                     // the row's own units (0 for a row without a count: filler keys, a tile's padding, zero counts
                     // with a tail -- never "low"), made BEFORE the logs, and sorted out in a branch the wave takes
                     // for one unit in twenty.  Rows without a count add 0 * log below.
@@ -947,7 +948,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                             // p_j = 0 in the reference: every term of its sum is at most the sum, and a term below
                             // 2^-1075 is flushed by the extension's cast to double (c_src/covest_poissonmodule.c:32) --
                             // so a row whose p_j (row value x scale) is safely below 1/8 of a grid step (the roundings
-                            // on the reference's way can keep anything above that alive: direct_point.h kZeroSteps) is a
+                            // on the reference's way can keep anything above that alive: handback.h kZeroSteps) is a
                             // zero, not a candidate for the strict evaluation.  (The unscaled row value itself never
                             // underflows: half of the C3 grid is -inf this way, and would otherwise queue up for the
                             // strict kernel.)
@@ -955,7 +956,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                             zero |= z;
                             subm |= low[r] & ~z;
                             // log(max(p_j, p_clamp)): what a p_j deep in the subnormal range contributes is then a
-                            // known constant, which the strict evaluation of that key replaces (direct_point.h).  In
+                            // known constant, which the strict evaluation of that key replaces (handback.h).  In
                             // place: the accumulator is of no further use, and a copy would cost every unit a move.
                             acc[k][r] = max_raw(acc[k][r], c4[r]);
                         }
@@ -967,7 +968,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                         newly_dead = newly_dead || zc != 0; // (wave-uniform: look for dead units after this item's logs)
                         // p_j DEEP IN THE SUBNORMAL RANGE: the unit (this half tile) is recorded for every weight vector
                         // (column) concerned -- first and last unit met; one writer per entry, the lane of row group 0.
-                        // The strict evaluation of its counted rows follows in ll_fix_list_kernel (argmin.hip)
+                        // The strict evaluation of its counted rows follows in ll_fix_list_kernel (ll_fix.hip)
                         const uint64_t cm = (subm | (subm >> 16) | (subm >> 32) | (subm >> 48)) & 0xFFFFull;
                         if (kq == 0 && ((cm >> col) & 1)) {
                             const unsigned u = 2u * (unsigned)(TAIL ? tv.item_first[t] : t) + (unsigned)uhalf[k];
@@ -1205,7 +1206,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
 // One wave finishes ONE point whose p_j lie in HBM, summed over chunks of copy numbers (tiles.h list modes 2, 3):
 // LL = sum_j h_j log p_j + tail log(1 - sp), covest/models.py:100-107.  read_pj(row): the p_j of row `row` of the
 // items (tiles.h: a key, or the sum over a count-less tile), TIMES kShareScale.  A subnormal p_j at a key with h_j != 0
-// -- down to kZeroSteps of a grid step, below which it is 0 in the reference whatever the roundings (direct_point.h) -- is
+// -- down to kZeroSteps of a grid step, below which it is 0 in the reference whatever the roundings (handback.h) -- is
 // replaced on the spot by its strict evaluation (direct_point.h: the whole wave, K-direct's arithmetic).  par: the
 // point's parameters, clamped; every lane returns the value.
 template <class ReadPj>

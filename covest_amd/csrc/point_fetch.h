@@ -64,7 +64,7 @@ __device__ __forceinline__ double error_class_rate(const DevModel &m, double c, 
     return v;
 }
 
-// ONE class's rate by multiplication, for a kernel whose lanes are classes (ll_fix_basic_packed_kernel): the products of
+// ONE class's rate by multiplication, for a kernel whose lanes are classes (ll_fix_basic_packed_kernel, ll_fix.hip): the products of
 // error_class_rates<S> below in the same order -- (1 - e)^max(k - S + 1, 0) by squaring, one more factor a class down to
 // s, e^s factor by factor -- so the strict re-evaluation of a K-basic point works with the very rates K-basic had.
 __device__ __forceinline__ double error_class_rate_mul(const DevModel &m, double c, double err, int s, int S)
@@ -131,7 +131,7 @@ __device__ __forceinline__ double copy_number_weight(double q1, double q2, doubl
 }
 
 // The same weight with (1 - q)^(o - 3) by squaring (at most 14 squarings for o <= 16384: about 1e-15 relative) instead
-// of the device library's pow (210 instructions): for the strict re-evaluation of handed-back rows (argmin.hip), where
+// of the device library's pow (210 instructions): for the strict re-evaluation of handed-back rows (ll_fix.hip), where
 // every lane of every lot wants one and the terms are rounded onto the 4.9e-324 grid anyway.
 __device__ __forceinline__ double copy_number_weight_by_squaring(double q1, double q2, double q, int o)
 {

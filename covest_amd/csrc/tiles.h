@@ -13,7 +13,7 @@ constexpr double kScaleLn = 540.0 * 0.693147180559945309417232121458; // ln 2^SC
 constexpr double kWindowLn = -760.0; // terms below e^-760 are 0 in double
 // TileView::scal carries 2^kBasicShift on top: K-basic's p_j (streams' sum x key's scale) are p_j 2^64 -- nothing
 // overflows (p_j <= 2.5), and a p_j below half a grid step of the doubles does not flush to 0 in the product, so the
-// kernel can tell a zero of the reference from a row for the strict evaluation (direct_point.h kZeroSteps)
+// kernel can tell a zero of the reference from a row for the strict evaluation (handback.h kZeroSteps)
 constexpr int kBasicShift = 64;
 constexpr double kBasicScale = 0x1p64;
 
@@ -75,7 +75,7 @@ struct TileView {
     const int32_t *item_ntiles; // [n_items] 1 for a plain item, 1..32 (rows in use) for a sum item
     const int32_t *item_sum;   // [n_items] 1 = sum item
     const int32_t *row_bin;    // [n_tiles][32] index of the row's key in DevModel::bins (-1: filler / padding): how a
-                               //   recurrence kernel names a key it hands back (direct_point.h)
+                               //   recurrence kernel names a key it hands back (handback.h)
     const TileRec *rec;        // [n_tiles] the per-tile values above, gathered (64-byte aligned: tile_dbl_count)
 };
 
@@ -213,7 +213,7 @@ struct FactoredPlan {
                                    //   point's copy numbers, o = item_obase[i] + 1 .. + 512 (threshold_o beyond one
                                    //   workgroup's lanes); the workgroup stores its share of p_j to `partial` and
                                    //   ll_finish_partials adds the chunks and takes the logs
-    double p_clamp;                // (S + max threshold_o) * 7e-317: below it a p_j is handed back (direct_point.h)
+    double p_clamp;                // (S + max threshold_o) * 7e-317: below it a p_j is handed back (handback.h)
     int32_t n_seg;                 // list modes: key tiles are cut into n_seg contiguous segments, workgroup
                                    //   blockIdx.x = unit * n_seg + segment (unit = point or chunk); a segment starts
                                    //   like a run (streams anchored).  list_mode 1 then writes {LL part, sp part hi, lo}

@@ -355,7 +355,7 @@ int build_tiles(covest_model *m, std::vector<HostBin> bins)
     return COVEST_OK;
 }
 
-// p_clamp of direct_point.h for a launch whose largest threshold_o is t_max.
+// p_clamp of handback.h for a launch whose largest threshold_o is t_max.
 double clamp_for(const covest_model *m, int t_max)
 {
     return (double)(m->dm.n_err + std::max(t_max, 2)) * kClampPerTerm;

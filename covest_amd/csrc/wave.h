@@ -47,16 +47,28 @@ struct CompSum {
     }
 };
 
-__device__ __forceinline__ double wave_comp_sum(CompSum v)
+// (hi, lo) += (ohi, olo): one step of the reduction below
+__device__ __forceinline__ void comp_merge(CompSum &v, double ohi, double olo)
+{
+    double e;
+    two_sum(v.hi, ohi, v.hi, e);
+    v.lo += olo + e;
+}
+
+__device__ __forceinline__ CompSum wave_comp_reduce(CompSum v)
 {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
         const double ohi = __shfl_xor(v.hi, off, kWave);
         const double olo = __shfl_xor(v.lo, off, kWave);
-        double e;
-        two_sum(v.hi, ohi, v.hi, e);
-        v.lo += olo + e;
+        comp_merge(v, ohi, olo);
     }
+    return v;
+}
+
+__device__ __forceinline__ double wave_comp_sum(CompSum v)
+{
+    v = wave_comp_reduce(v);
     return v.hi + v.lo;
 }
 

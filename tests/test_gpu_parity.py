@@ -714,7 +714,7 @@ def test_round4_shortcuts_on_awkward_shapes(hip_lib, oracle):
     """The work the round-4 kernels leave OUT must never change a value.  K-factored takes the LAST key tile first (a
     unit whose weight vectors all end at -inf dies in the first interval, ll_factored.hip `last_first`); K-basic lets a
     wave whose points are all -inf by a sufficient bound at the last counted key leave before its prologue
-    (ll_basic.hip); the strict kernel of the basic model takes 64 / S points a wave (argmin.hip).  Histograms chosen
+    (ll_basic.hip); the strict kernel of the basic model takes 64 / S points a wave (ll_fix.hip).  Histograms chosen
     for what those shortcuts could trip over -- one partial tile, a full and a partial one, a gap between two runs with
     the last tile a run of its own, a lone far key that dooms most of the grid, a subnormal key with 8, 16 and 24 error
     classes -- each on a grid that holds finite points, -inf points and the border between them: the recurrence kernel

@@ -9,8 +9,13 @@ then compared: nothing may differ.  A set that does not show the plan feature it
   * the bench workloads c3 and c3t (bench.workload);
   * one handle re-configured through DenseGrid.reset over the grids of two optimize_grid searches on the 15-key
     histogram -- grids of at most kArgminSmall = 16384 points, which a reset handle reads in place, with several
-    workgroups per (c, e) -- the second search started next to the bounds, so that its axes are cut by them;
+    workgroups per (c, e) -- the second search started next to the bounds, so that its axes are cut by them.  (A grid
+    the bounds cut down to under a thousand points goes to K-direct under kernel="auto": it is compared like the others
+    and not asked for K-factored's features, and most of the grids must be K-factored's);
   * ragged flat_range blocks of the sets in RAGGED, against the other library's and against the own whole grid.
+
+  * the basic model's hand-back: the grid with a subnormal key of every entry of tests/test_gpu_variants.py BASIC_CASES
+    (K-basic queues points, the strict pass patches them: every fix_basic_packed<S>, and fix_list<2,1> at 22 classes).
 
     python tools/compare_grid_libs.py --new covest_amd/lib/libcovest_amd.so --parent /path/lib_parent.so \
         [--work DIR] [--out profiles/plan_ab.txt]
@@ -37,7 +42,8 @@ def _launched(prefixes):
 
 
 def grid_sets():
-    """(name, model arguments, axes, kernel, check): check(record) -> what the set missed (empty: on its route)."""
+    """(name, model arguments, axes, kernel, check): check(record) -> what the set missed (empty: on its route).  Model
+    arguments: (k, r, histogram, tail, max_error), the repeats model's; with "basic" in front, the basic model's."""
     import test_gpu_variants as tv
     from bench import load_hist, workload, workload_tail
     out = []
@@ -51,6 +57,11 @@ def grid_sets():
         n = sum(c for name, c in rec["launches"].items() if name.startswith("ll_factored<"))
         return ([] if tv._plan(n_qblocks=1)(rec["plans"]) else ["n_qblocks=1"]) + ([] if n > 1 else ["more than one launch"])
     out.append(("launch split", (21, 100, tv._falling(range(1, 21), 5000), 0, 8), axes, "factored", split))
+    for k, S, basic, fix in tv.BASIC_CASES:
+        for tail in (0, 9):
+            launches = [basic % (",tail" if tail else ""), fix]
+            out.append(("basic k%d S%d%s" % (k, S, " tail" if tail else ""), ("basic", k, 100, tv.SUB_HIST, tail, S),
+                        tv._basic_axes(k), "recur", lambda rec, launches=launches: sorted(set(launches) - set(rec["launches"]))))
     for w in ("c3", "c3t"):
         kind, hname, axes = workload(w, 1)
         out.append(("bench " + w, (21, 100, load_hist(hname), workload_tail(w), 8), axes, "auto", _launched(["ll_factored<"])))
@@ -94,17 +105,19 @@ def search_grids(m):
 
 def dump(work):
     from bench import load_hist
-    from covest_amd import DenseGrid, RepeatsModel, constants
+    from covest_amd import BasicModel, DenseGrid, RepeatsModel, constants
     records = {}
 
     def keep(name, ll, best, rec, missed):
         np.save(os.path.join(work, "%s.ll.npy" % name), ll)
         np.save(os.path.join(work, "%s.best.npy" % name), best)
         records[name] = {"launches": sorted(rec["launches"].items()), "plans": rec["plans"], "missed": missed}
+        print("done: %s" % name, file=sys.stderr, flush=True)  # (progress, for a caller that watches the run)
 
     for name, margs, axes, kernel, check in grid_sets():
-        k, r, hist, tail, S = margs
-        m = RepeatsModel(k, r, hist, tail, max_error=S)
+        cls = BasicModel if margs[0] == "basic" else RepeatsModel
+        k, r, hist, tail, S = margs[-5:]
+        m = cls(k, r, hist, tail, max_error=S)
         g = DenseGrid(m, axes)
         ll, best, rec = _evaluate(g, kernel)
         keep(name, ll, best, rec, check(rec))
@@ -117,19 +130,22 @@ def dump(work):
         m.close()
     m = RepeatsModel(21, 100, load_hist("sim_c10_e0.05"), 0, max_error=8)
     grids = search_grids(m)
-    g, n_cut = None, 0
+    g, n_cut, n_direct = None, 0, 0
     for i, axes in enumerate(grids):
         g = DenseGrid(m, axes) if g is None else g.reset(axes)
         ll, best, rec = _evaluate(g, "auto")
         cut = any(1 < len(a) < 2 * constants.GRID_DEPTH for a in axes) or any(len(a) == 0 for a in axes)
         n_cut += cut
-        missed = _launched(["ll_factored<"])(rec)
+        direct = "ll_direct" in rec["launches"] and not rec["plans"]  # (too few points for K-factored: see the head)
+        n_direct += direct
+        missed = [] if direct else _launched(["ll_factored<"])(rec)
         if i and len(ll) > IN_PLACE_MAX:
             missed.append("%d points: not read in place" % len(ll))
-        if not any(p["n_qblocks"] > 1 and p["list_mode"] == 0 for p in rec["plans"]):
+        if not direct and not any(p["n_qblocks"] > 1 and p["list_mode"] == 0 for p in rec["plans"]):
             missed.append("several workgroups per (c, e)")
         keep("reset %02d%s" % (i, " cut" if cut else ""), ll, best, rec, missed)
-    records["resets"] = {"launches": [], "plans": [], "missed": [] if n_cut and len(grids) - n_cut > 1 else ["a grid cut by the bounds and two uncut ones"]}
+    records["resets"] = {"launches": [], "plans": [], "missed": ([] if n_cut and len(grids) - n_cut > 1 else ["a grid cut by the bounds and two uncut ones"]) +
+                         ([] if 2 * n_direct < len(grids) else ["%d of %d grids went to K-direct" % (n_direct, len(grids))])}
     g.close()
     m.close()
     with open(os.path.join(work, "records.json"), "w") as f:

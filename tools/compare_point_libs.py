@@ -177,6 +177,7 @@ def dump(work):
                         "kinds": {str(k): int(c) for k, c in zip(*np.unique(kinds, return_counts=True))},
                         "missed": route_misses(want, kinds, rec) + ([] if len(points) else ["empty"])}
         m.close()
+        print("done: %s" % name, file=sys.stderr, flush=True)  # (progress, for a caller that watches the run)
     with open(os.path.join(work, "routes.json"), "w") as f:
         json.dump(routes, f)
     for name, case, points in sets():
@@ -186,6 +187,7 @@ def dump(work):
         for what, arr in (("g_ll", g_ll), ("g_grad", g_grad), ("h_ll", h_ll), ("h_grad", h_grad), ("h_hess", h_hess)):
             np.save(os.path.join(work, "%s.%s.npy" % (name, what)), np.asarray(arr, dtype=np.float64))
         m.close()
+        print("done: %s" % name, file=sys.stderr, flush=True)
 
 
 class Exact:

@@ -11,7 +11,7 @@ Writes gpurun_out/c2_classes.json: per class the flat indices where the REFERENC
   neginf_edge   -inf-by-bound lanes closest to the bound (largest log p_min below -746.5)
   neginf_far    -inf-by-bound lanes, seeded
   flush_edge    walking lanes whose smallest p_j is closest to HALF A GRID STEP of the doubles (2^-1075): where a product
-                rounded once flushes to 0 and the reference's term-by-term roundings may not (direct_point.h kZeroSteps;
+                rounded once flushes to 0 and the reference's term-by-term roundings may not (handback.h kZeroSteps;
                 flat index 826002 is the point that was -inf here and finite in the reference until round 4)
 Only indices (and the class counts) leave this script: every value of the fixture is the reference's."""
 import json
