@@ -6,11 +6,16 @@ include/covest_amd.h).
     ll = batch.loglikelihood_cross(points)                # (B, n): every histogram at every point
     ll = batch.loglikelihood_pairs(index, points)         # (n,): histogram index[i] at point i
     best, arg = batch.argmin_cross(points)                # per histogram: min -LL over the points and where
+    ll, grad = batch.loglikelihood_gradient_cross(points) # (B, n), (B, n, P): value and analytic gradient
+    ll, grad = batch.loglikelihood_gradient_pairs(index, points)   # (n,), (n, P)
+    log_p, score, tail = batch.score_table(points)        # the table behind the two: (n, n_keys), (n, P, n_keys), (n, P + 1)
 
 For a fixed key set p_j(theta) does not depend on the counts, so B histograms at n points cost n evaluations of p and
-one B x n_keys x n contraction instead of B n evaluations.  What a batch is not: its histograms share the model's keys,
-k, r, comb, bounds and threshold -- only the counts and the tail differ --, and it has no gradient.  There is no CPU
-path: without the library or a HIP device the constructor raises CovestHipError.
+one B x n_keys x n contraction instead of B n evaluations.  The per-key score d_k p_j / p_j does not depend on them
+either, so the gradient costs n walks of the derivative kernel and a contraction against P + 1 rows a point (DESIGN.md
+section 6u).  What a batch is not: its histograms share the model's keys, k, r, comb, bounds and threshold -- only the
+counts and the tail differ.  There is no CPU path: without the library or a HIP device the constructor raises
+CovestHipError.
 """
 import ctypes
 
@@ -144,6 +149,45 @@ class HistogramBatch:
         _capi.check(_capi.lib().covest_batch_eval_pairs(self._open(), len(pts), idx.ctypes.data, pts.ctypes.data,
                                                         out.ctypes.data), "covest_batch_eval_pairs")
         return out
+
+    def loglikelihood_gradient_cross(self, points):
+        """(ll (B, n), grad (B, n, P)): every histogram's log-likelihood and its analytic gradient at every point, at
+        the point after fit_to_bounds (a component whose parameter the clamp moved is 0; where the value is not finite
+        every component is NaN).  Value and gradient come from ONE table, the derivative kernel's: a line search gets a
+        value and a gradient of one function.  That value agrees with loglikelihood_cross (K-direct's table) to 1e-11
+        relative, not to the bit."""
+        pts = self._points(points)
+        out = np.empty((self._n, len(pts), self.model.param_count + 1), dtype=np.float64)
+        _capi.check(_capi.lib().covest_batch_eval_cross_grad(self._open(), len(pts), pts.ctypes.data, out.ctypes.data),
+                    "covest_batch_eval_cross_grad")
+        return np.ascontiguousarray(out[:, :, 0]), np.ascontiguousarray(out[:, :, 1:])
+
+    def loglikelihood_gradient_pairs(self, index, points):
+        """(ll (n,), grad (n, P)): histogram index[i] at points[i], value and analytic gradient from one table as in
+        loglikelihood_gradient_cross (the value is the derivative kernel's: loglikelihood_pairs' to 1e-11 relative, not
+        to the bit).  A request's result does not depend on what else is in the call."""
+        pts = self._points(points)
+        idx = _index_array(index, self._n)
+        if len(idx) != len(pts):
+            raise ValueError("one histogram index per point")
+        out = np.empty((len(pts), self.model.param_count + 1), dtype=np.float64)
+        _capi.check(_capi.lib().covest_batch_eval_pairs_grad(self._open(), len(pts), idx.ctypes.data, pts.ctypes.data,
+                                                             out.ctypes.data), "covest_batch_eval_pairs_grad")
+        return np.ascontiguousarray(out[:, 0]), np.ascontiguousarray(out[:, 1:])
+
+    def score_table(self, points):
+        """(log_p (n, n_keys), score (n, P, n_keys), tail (n, P + 1)): the table the gradient methods contract with, as
+        the device holds it.  log_p is +0.0 where p_ij <= 0 and nowhere else (p = 1 is -0.0; NaN stays NaN);
+        score[i, k, j] = d_k p_ij / p_ij, +0.0 at such a key and throughout where the clamp moved parameter k;
+        tail[i] = [log(1 - sp_i), -S_k / (1 - sp_i) ...], all 0 where sp_i is not < 1.  It does not depend on the
+        histograms."""
+        pts = self._points(points)
+        R = self.model.param_count + 1
+        rows = np.empty((len(pts), R, self._n_keys), dtype=np.float64)
+        tail = np.empty((len(pts), R), dtype=np.float64)
+        _capi.check(_capi.lib().covest_batch_score_table(self._open(), len(pts), pts.ctypes.data, rows.ctypes.data,
+                                                         tail.ctypes.data), "covest_batch_score_table")
+        return np.ascontiguousarray(rows[:, 0, :]), np.ascontiguousarray(rows[:, 1:, :]), tail
 
     def argmin_cross(self, points):
         """(min_negll (B,), arg (B,)): per histogram the smallest -LL over the points and the first index that attains

@@ -133,21 +133,33 @@ def _refit(model, keys, counts, tail, estimate, fix, estimator_options):
         twin.close()
 
 
-def _refit_lockstep(model, estimate, replicates, seed, n_draws, fix, estimator_options):
+def _refit_lockstep(model, estimate, replicates, seed, n_draws, fix, estimator_options, analytic=False, batch=None):
     """(estimates, success, log-likelihoods) of all replicates refitted TOGETHER: the histograms are drawn into a
     HistogramBatch and never leave the device, one CoverageEstimator._optimize per replicate runs under the estimator's
     _LockStep, and a merged round -- every replicate's point and its finite-difference neighbours -- is ONE
-    loglikelihood_pairs call, each request tagged with its replicate.  No model per replicate."""
+    loglikelihood_pairs call, each request tagged with its replicate.  No model per replicate.
+
+    analytic (refit="lockstep-gradient"): the estimators run with gradient="analytic", a round holds ONE request per live
+    replicate instead of P + 1, and is ONE loglikelihood_gradient_pairs call whose values and gradients go back as the
+    rows negll_gradient_points returns (optimiser space: CoverageEstimator._optimiser_rows).  `batch`: the histograms,
+    where the caller has them already (it stays the caller's)."""
     from .batch import HistogramBatch
     from .estimator import CoverageEstimator, _LockStep
+    route = "lockstep-gradient" if analytic else "lockstep"
+    if analytic:
+        estimator_options = dict(estimator_options, gradient="analytic")
     est = CoverageEstimator(model, fix=fix, **estimator_options)
     if not est.batched or est.reference_specials:
-        raise ValueError('refit="lockstep" goes with neither batched=False nor reference_specials=True')
-    batch = HistogramBatch.draw(model, estimate, replicates, seed=seed, n_draws=n_draws)
+        raise ValueError('refit="%s" goes with neither batched=False nor reference_specials=True' % route)
+    own = batch is None
+    if own:
+        batch = HistogramBatch.draw(model, estimate, replicates, seed=seed, n_draws=n_draws)
     try:
         def evaluate_merged(requests):  # [(replicate, optimiser-space vector)] of one round
             index = [b for b, _ in requests]
             points = np.array([est._model_args(x) for _, x in requests], dtype=np.float64)
+            if analytic:
+                return est._optimiser_rows(*batch.loglikelihood_gradient_pairs(index, points))
             return -batch.loglikelihood_pairs(index, points)
 
         start = list(estimate)
@@ -166,7 +178,8 @@ def _refit_lockstep(model, estimate, replicates, seed, n_draws, fix, estimator_o
         loglik = batch.loglikelihood_pairs(np.arange(replicates), estimates) if replicates else np.empty(0)
         return estimates, success, loglik
     finally:
-        batch.close()
+        if own:
+            batch.close()
 
 
 def _on_bound(values, bounds):
@@ -208,8 +221,13 @@ def parametric_bootstrap(model, estimate, replicates=100, seed=0, fix=None, leve
 
     refit="lockstep": the same replicates (the same draws) as a HistogramBatch on the device, all refits advancing
     together, one loglikelihood_pairs launch per round and no model per replicate (_refit_lockstep).  Finite-difference
-    gradients only: with gradient="analytic" it raises ValueError -- a batch has no gradient.  The two routes evaluate
+    gradients only: with gradient="analytic" it raises ValueError -- that is the next route's.  The two routes evaluate
     with different kernels, so a refit may stop an L-BFGS-B step apart; the result has the same keys, and `refit`.
+
+    refit="lockstep-gradient": the same draws and the same lock step, each refit a CoverageEstimator(gradient="analytic"):
+    a round holds one request per live replicate, not P + 1, and is one loglikelihood_gradient_pairs call -- the batch's
+    analytic gradient (DESIGN.md section 6u), without the 1e-8 differencing step.  It honours `fix` and err_scale;
+    gradient="fd" with it raises ValueError.
 
     Returns a dict: replicates, seed, n_draws; estimates (B x P), success (B), loglikelihood (B), at_bound (B x P: the
     refit ended on a bound of the model); mean, bias (mean - estimate), standard_errors and percentile_intervals at
@@ -222,17 +240,20 @@ def parametric_bootstrap(model, estimate, replicates=100, seed=0, fix=None, leve
     names = list(model.params)
     if len(estimate) != len(names):
         raise ValueError("parametric_bootstrap: %d parameters expected, %d given" % (len(names), len(estimate)))
-    if refit not in ("sequential", "lockstep"):
-        raise ValueError('refit must be "sequential" or "lockstep"')
+    if refit not in ("sequential", "lockstep", "lockstep-gradient"):
+        raise ValueError('refit must be "sequential", "lockstep" or "lockstep-gradient"')
     if refit == "lockstep" and estimator_options.get('gradient', 'fd') != 'fd':
-        raise ValueError('refit="lockstep" goes with gradient="fd" only: a histogram batch has no gradient')
+        raise ValueError('refit="lockstep" goes with gradient="fd" only: the analytic gradient is refit="lockstep-gradient"')
+    if refit == "lockstep-gradient" and estimator_options.get('gradient', 'analytic') != 'analytic':
+        raise ValueError('refit="lockstep-gradient" goes with gradient="analytic" only: finite differences are refit="lockstep"')
     n_draws = int(round(float(sum(model.hist.values())) + float(model.tail)))
     estimates = np.full((replicates, len(names)), np.nan)
     success = np.zeros(replicates, dtype=bool)
     loglik = np.full(replicates, np.nan)
     at_bound = np.zeros((replicates, len(names)), dtype=bool)
-    if refit == "lockstep":
-        estimates, success, loglik = _refit_lockstep(model, estimate, replicates, seed, n_draws, fix, estimator_options)
+    if refit != "sequential":
+        estimates, success, loglik = _refit_lockstep(model, estimate, replicates, seed, n_draws, fix, estimator_options,
+                                                     analytic=refit == "lockstep-gradient")
         for b in range(replicates):
             at_bound[b] = _on_bound(estimates[b], model.bounds)
     else:

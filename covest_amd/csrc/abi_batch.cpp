@@ -21,6 +21,8 @@ struct covest_batch {
     DevBuf out;              // a chunk's values: [n_hist][points of the chunk] (cross), [points] (pairs)
     DevBuf index, dead_list; // a pairs call's histogram numbers; the chunk's points with dead keys
     DevBuf run_val, run_idx; // the running arg-min of covest_batch_argmin_cross
+    DevBuf partial, fin;     // the gradient's table: the derivative kernel's segment sums; its finishing pass's value
+                             // [points] and gradient [points][P] (the tail coefficients before they are packed into tl)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     ~covest_batch()
@@ -131,6 +133,50 @@ int reserve_chunk(covest_batch *b, int64_t nc_max)
     HIP_TRY(b->table.reserve((size_t)nc_max * (size_t)b->n_keys * sizeof(double)));
     HIP_TRY(b->tl.reserve((size_t)nc_max * sizeof(double)));
     HIP_TRY(b->dead.reserve((size_t)nc_max * sizeof(int32_t)));
+    return COVEST_OK;
+}
+
+// ---- the gradient: a table of R = P + 1 rows a point from the derivative kernel's walk ----
+int rows_per_point(const covest_batch *b) { return b->model->n_par + 1; }
+
+int reserve_grad_chunk(covest_batch *b, int64_t nc_max)
+{
+    const int64_t R = rows_per_point(b);
+    if (nc_max * R > std::numeric_limits<int32_t>::max())
+        return fail(COVEST_E_UNSUPPORTED, "covest_batch: more than 2^31 rows in a table chunk");
+    HIP_TRY(b->table.reserve((size_t)nc_max * (size_t)R * (size_t)b->n_keys * sizeof(double)));
+    HIP_TRY(b->tl.reserve((size_t)nc_max * (size_t)R * sizeof(double)));
+    HIP_TRY(b->dead.reserve((size_t)nc_max * sizeof(int32_t)));
+    HIP_TRY(b->partial.reserve(ll_deriv_partial_bytes(table_model(b), 1, nc_max)));
+    HIP_TRY(b->fin.reserve((size_t)nc_max * (size_t)R * sizeof(double)));
+    return COVEST_OK;
+}
+
+// table_chunk for the gradient: rows (P + 1) i .. of b->table are point i's, b->tl holds its P + 1 tail coefficients, and
+// dead_list names the VALUE row (P + 1) i of every point with dead keys -- what launch_batch_fix_dead indexes by.
+int grad_table_chunk(covest_batch *b, const PointSource &src, int64_t first, int64_t nc, int64_t *n_dead)
+{
+    const covest_model *m = b->model;
+    const int R = rows_per_point(b);
+    double *fin_ll = b->fin.as<double>(), *fin_grad = fin_ll + nc;
+    HIP_TRY(hipEventRecord(b->ev[0], nullptr));
+    HIP_TRY(launch_ll_deriv_table(table_model(b), points_from(src, first, m->n_par), nc, b->partial.as<double>(),
+                                  b->table.as<double>(), b->dead.as<int32_t>(), fin_ll, fin_grad, nullptr));
+    HIP_TRY(launch_batch_tail_pack(fin_ll, fin_grad, nc, R, b->tl.as<double>(), nullptr));
+    HIP_TRY(hipEventRecord(b->ev[1], nullptr));
+    std::vector<int32_t> dead((size_t)nc), list;
+    HIP_TRY(hipMemcpy(dead.data(), b->dead.ptr, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < nc; ++i)
+        if (dead[(size_t)i] > 0)
+            list.push_back((int32_t)(i * R));
+    *n_dead = (int64_t)list.size();
+    if (!list.empty()) {
+        HIP_TRY(b->dead_list.reserve(list.size() * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(b->dead_list.ptr, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    b->info[0] += nc;
+    b->info[1] += 1;
+    b->info[3] += *n_dead;
     return COVEST_OK;
 }
 
@@ -384,6 +430,120 @@ int covest_batch_eval_pairs(covest_batch *b, int64_t n, const int64_t *hist_inde
         HIP_TRY(hipMemcpy(out_ll + first, b->out.ptr, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost));
         add_elapsed(b, 6, b->ev[0], b->ev[1]);
         b->info[5] += nc;
+    }
+    return COVEST_OK;
+}
+
+int covest_batch_eval_cross_grad(covest_batch *b, int64_t n, const double *params, double *out)
+{
+    if (!b)
+        return refuse("covest_batch_eval_cross_grad", "null batch");
+    if (const char *bad = batch_check_points(n, b->n_hist, params, out))
+        return refuse("covest_batch_eval_cross_grad", bad);
+    BatchCall call(b);
+    COVEST_TRY(call.status);
+    if (n == 0 || b->n_hist == 0)
+        return COVEST_OK;
+    PointSource src;
+    COVEST_TRY(upload_points(b, n, params, src));
+    const int64_t R = rows_per_point(b);
+    const int64_t per = batch_grad_points_per_chunk(b->n_keys, R, kBatchTableBytes), nc_max = std::min(n, per);
+    COVEST_TRY(reserve_grad_chunk(b, nc_max));
+    HIP_TRY(b->out.reserve((size_t)b->n_hist * (size_t)nc_max * (size_t)R * sizeof(double)));
+    const int64_t chunks = batch_chunk_count(n, per);
+    for (int64_t c = 0; c < chunks; ++c) {
+        int64_t first, nc, n_dead = 0, tiles = 0;
+        batch_chunk(n, per, c, &first, &nc);
+        COVEST_TRY(grad_table_chunk(b, src, first, nc, &n_dead));
+        const int64_t ld = nc * R; // the contraction sees R nc rows of the table and as many tail coefficients
+        HIP_TRY(hipEventRecord(b->ev[2], nullptr));
+        HIP_TRY(launch_batch_cross(b->counts.as<double>(), b->tails.as<double>(), b->n_hist, b->table.as<double>(),
+                                   b->tl.as<double>(), ld, b->n_keys, b->out.as<double>(), ld, &tiles, nullptr));
+        b->info[2] += tiles;
+        if (n_dead > 0) {
+            HIP_TRY(launch_batch_fix_dead(b->counts.as<double>(), b->n_hist, b->table.as<double>(), b->n_keys,
+                                          b->dead_list.as<int32_t>(), n_dead, b->out.as<double>(), ld, nullptr));
+            b->info[4] += b->n_hist * n_dead;
+        }
+        HIP_TRY(launch_batch_grad_specials(b->n_hist, nc, (int)R, b->out.as<double>(), ld, nullptr));
+        HIP_TRY(hipEventRecord(b->ev[3], nullptr));
+        HIP_TRY(hipMemcpy2D(out + first * R, (size_t)n * (size_t)R * sizeof(double), b->out.ptr, (size_t)ld * sizeof(double),
+                            (size_t)ld * sizeof(double), (size_t)b->n_hist, hipMemcpyDeviceToHost));
+        HIP_TRY(hipEventSynchronize(b->ev[3]));
+        add_elapsed(b, 6, b->ev[0], b->ev[1]);
+        add_elapsed(b, 7, b->ev[2], b->ev[3]);
+    }
+    return COVEST_OK;
+}
+
+int covest_batch_eval_pairs_grad(covest_batch *b, int64_t n, const int64_t *hist_index, const double *params, double *out)
+{
+    if (!b)
+        return refuse("covest_batch_eval_pairs_grad", "null batch");
+    if (n < 0)
+        return refuse("covest_batch_eval_pairs_grad", "n must not be negative");
+    if (n > 0 && (!params || !out))
+        return refuse("covest_batch_eval_pairs_grad", "null buffer");
+    if (const char *bad = batch_check_index(n, hist_index, b->n_hist))
+        return refuse("covest_batch_eval_pairs_grad", bad);
+    BatchCall call(b);
+    COVEST_TRY(call.status);
+    if (n == 0)
+        return COVEST_OK;
+    PointSource src;
+    COVEST_TRY(upload_points(b, n, params, src));
+    HIP_TRY(b->index.reserve((size_t)n * sizeof(int64_t)));
+    COVEST_TRY(stage_upload(b->index.ptr, hist_index, (size_t)n * sizeof(int64_t),
+                            "covest_batch_eval_pairs_grad: upload of the index"));
+    const int64_t R = rows_per_point(b);
+    const int64_t per = batch_grad_points_per_chunk(b->n_keys, R, kBatchTableBytes), nc_max = std::min(n, per);
+    COVEST_TRY(reserve_grad_chunk(b, nc_max));
+    HIP_TRY(b->out.reserve((size_t)nc_max * (size_t)R * sizeof(double)));
+    const int64_t chunks = batch_chunk_count(n, per);
+    for (int64_t c = 0; c < chunks; ++c) {
+        int64_t first, nc, n_dead = 0;
+        batch_chunk(n, per, c, &first, &nc);
+        COVEST_TRY(grad_table_chunk(b, src, first, nc, &n_dead));
+        HIP_TRY(hipEventRecord(b->ev[2], nullptr));
+        HIP_TRY(launch_batch_pairs_grad(b->counts.as<double>(), b->tails.as<double>(), b->index.as<int64_t>() + first,
+                                        b->table.as<double>(), b->tl.as<double>(), nc, b->n_keys, (int)R, b->out.as<double>(),
+                                        nullptr));
+        HIP_TRY(hipEventRecord(b->ev[3], nullptr));
+        HIP_TRY(hipMemcpy(out + first * R, b->out.ptr, (size_t)nc * (size_t)R * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipEventSynchronize(b->ev[3]));
+        add_elapsed(b, 6, b->ev[0], b->ev[1]);
+        add_elapsed(b, 7, b->ev[2], b->ev[3]);
+        b->info[5] += nc;
+    }
+    return COVEST_OK;
+}
+
+int covest_batch_score_table(covest_batch *b, int64_t n, const double *params, double *out_rows, double *out_tail)
+{
+    if (!b)
+        return refuse("covest_batch_score_table", "null batch");
+    if (const char *bad = batch_check_points(n, 1, params, out_rows)) // (the table does not depend on the histograms)
+        return refuse("covest_batch_score_table", bad);
+    if (n > 0 && !out_tail)
+        return refuse("covest_batch_score_table", "null buffer");
+    BatchCall call(b);
+    COVEST_TRY(call.status);
+    if (n == 0)
+        return COVEST_OK;
+    PointSource src;
+    COVEST_TRY(upload_points(b, n, params, src));
+    const int64_t R = rows_per_point(b);
+    const int64_t per = batch_grad_points_per_chunk(b->n_keys, R, kBatchTableBytes), nc_max = std::min(n, per);
+    COVEST_TRY(reserve_grad_chunk(b, nc_max));
+    const int64_t chunks = batch_chunk_count(n, per);
+    for (int64_t c = 0; c < chunks; ++c) {
+        int64_t first, nc, n_dead = 0;
+        batch_chunk(n, per, c, &first, &nc);
+        COVEST_TRY(grad_table_chunk(b, src, first, nc, &n_dead));
+        HIP_TRY(hipMemcpy(out_rows + first * R * b->n_keys, b->table.ptr,
+                          (size_t)nc * (size_t)R * (size_t)b->n_keys * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_tail + first * R, b->tl.ptr, (size_t)nc * (size_t)R * sizeof(double), hipMemcpyDeviceToHost));
+        add_elapsed(b, 6, b->ev[0], b->ev[1]);
     }
     return COVEST_OK;
 }

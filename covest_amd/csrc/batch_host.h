@@ -65,6 +65,14 @@ inline int64_t batch_points_per_chunk(int64_t n_keys, int64_t budget_bytes)
     return per > 0 ? per : 1;
 }
 
+// ... of a table with `rows_per_point` rows a point (the gradient's table: the value row and one score row a parameter)
+inline int64_t batch_grad_points_per_chunk(int64_t n_keys, int64_t rows_per_point, int64_t budget_bytes)
+{
+    const int64_t rows = rows_per_point > 0 ? rows_per_point : 1;
+    const int64_t per = batch_points_per_chunk(n_keys, budget_bytes) / rows;
+    return per > 0 ? per : 1;
+}
+
 inline int64_t batch_chunk_count(int64_t n, int64_t per) { return n <= 0 ? 0 : (n + per - 1) / per; }
 
 // chunk c of a list of n: its first point and how many it has

@@ -156,6 +156,16 @@ size_t ll_deriv_partial_bytes(const DevModel &m, int order, int64_t n);
 hipError_t launch_ll_deriv(const DevModel &m, int order, const PointSource &src, int64_t n, double *partial, double *out_ll,
                            double *out_grad, double *out_hess, hipStream_t stream);
 
+// K-grad's walk (order 1) with its per-key quantities stored on the way: `m` is the batch's table
+// model (the all-keys view, a zero count array, tail 1).  rows: per point P + 1 rows of n_keys doubles, point-major -- row
+// (P + 1) i is log p_ij in launch_batch_table's conventions (+0.0 dead and nothing else, p = 1 as -0.0, NaN stays), rows
+// (P + 1) i + 1 + k the scores d_k p_ij / p_ij, +0.0 at a dead key and throughout where the clamp moved parameter k;
+// dead[i] the keys with p_ij <= 0.  With zero counts and tail 1 the finishing pass leaves the tail coefficients:
+// out_ll[i] = log(1 - sp_i), out_grad[i][k] = -S_k / (1 - sp_i), all 0 where sp_i is not < 1, 0 for a moved parameter.
+// partial: ll_deriv_partial_bytes(m, 1, n) bytes.  The launch cut is launch_ll_deriv's.
+hipError_t launch_ll_deriv_table(const DevModel &m, const PointSource &src, int64_t n, double *partial, double *rows,
+                                 int32_t *dead, double *out_ll, double *out_grad, hipStream_t stream);
+
 // ---- K-tp (tp_eval.hip): the truncated-Poisson pmf itself, c_src/covest_poissonmodule.c:7-35 ----
 // Modes of the pairs kernel (include/covest_amd.h COVEST_TP_*): the finite value the formula defines (0 below the
 // doubles' range, 0 at a rate that is 0 or NaN); the same with +inf where the extension's running long-double product
@@ -348,6 +358,21 @@ hipError_t launch_batch_fix_dead(const double *H, int64_t n_hist, const double *
 // out[i] = sum_j H[index[i]][j] table[i][j] + tails[index[i]] tl[i], the dead-key rule applied inline; a wave a request.
 hipError_t launch_batch_pairs(const double *H, const double *tails, const int64_t *index, const double *table,
                               const double *tl, int64_t n, int64_t n_keys, double *out, hipStream_t stream);
+// ---- the gradient of a batch: `rows` is launch_ll_deriv_table's, R = P + 1 rows a point ----
+// tc[i * R + q] from the finishing pass's out_ll[i] (q = 0) and out_grad[i][q - 1]: the array launch_batch_cross takes
+// for tl when the table has R n rows.
+hipError_t launch_batch_tail_pack(const double *fin_ll, const double *fin_grad, int64_t n, int rows_per_point, double *tc,
+                                  hipStream_t stream);
+// out[i * R + q] = sum_j H[index[i]][j] rows[i * R + q][j] + tails[index[i]] tc[i * R + q], one wave a request: the R dot
+// products in one sweep over the keys; the dead-key rule inline (value -inf), and where the value is not finite the
+// R - 1 derivative entries NaN.  R is 3 or 6.
+hipError_t launch_batch_pairs_grad(const double *H, const double *tails, const int64_t *index, const double *rows,
+                                   const double *tc, int64_t n, int64_t n_keys, int rows_per_point, double *out,
+                                   hipStream_t stream);
+// out is n_hist x (n * R) with row length ld (launch_batch_cross over R n rows, then launch_batch_fix_dead with the dead
+// points' VALUE rows listed): where out[b * ld + i * R] is not finite, the R - 1 entries behind it become NaN.
+hipError_t launch_batch_grad_specials(int64_t n_hist, int64_t n, int rows_per_point, double *out, int64_t ld,
+                                      hipStream_t stream);
 // Per histogram b, over ll[b * ld + i], i < n: the first i with the strictly smallest -ll (NaN never wins) against the
 // running (run_val[b], run_idx[b]) of the chunks before, which a later chunk only beats with a strictly smaller value;
 // a winner is stored as first + i.  Start the running pair at (+inf, -1).

@@ -25,6 +25,9 @@
 //                         point) sets -inf where the histogram counts such a key.  A key with h_bj = 0 contributes
 //                         nothing (covest/models.py:105-107, `if h`).
 //   batch_pairs_kernel    histogram index[i] at point i, one wave a request, the dead-key rule inline.
+//   batch_pairs_grad_kernel, batch_tail_pack_kernel, batch_grad_specials_kernel  the gradient of a batch (DESIGN.md
+//                         section 6u): the same contraction over the derivative kernel's score table, R = P + 1 rows a
+//                         point; the pairs form takes a request's R dot products in one sweep.
 //   batch_argmin_kernel   per histogram the first index of the strictly smallest -LL (covest/grid.py:65-70), carried
 //                         across table chunks on the device.
 //   batch_from_draw_kernel  int64 rows of draw_hist.hip to double counts and tails.
@@ -188,6 +191,74 @@ __global__ __launch_bounds__(256) void batch_pairs_kernel(const double *__restri
         out[i] = v;
 }
 
+// a wave a request: histogram index[i] against the R rows of point i (value, then the scores), one sweep over the keys
+template <int R>
+__global__ __launch_bounds__(256) void batch_pairs_grad_kernel(const double *__restrict__ H, const double *__restrict__ tails,
+                                                               const int64_t *__restrict__ index,
+                                                               const double *__restrict__ rows, const double *__restrict__ tc,
+                                                               const int64_t n, const int64_t nk, double *__restrict__ out,
+                                                               const int64_t w0)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t i = w0 + (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x / kWave);
+    if (i >= n)
+        return; // wave-uniform
+    const int64_t b = index[i];
+    const double *hrow = H + b * nk, *lrow = rows + i * R * nk;
+    double acc[R];
+#pragma unroll
+    for (int q = 0; q < R; ++q)
+        acc[q] = 0.0;
+    bool hit = false;
+    for (int64_t j = lane; j < nk; j += kWave) {
+        const double h = hrow[j], l = lrow[j];
+        acc[0] += h * l;
+        hit = hit || (h != 0.0 && is_dead_entry(l));
+#pragma unroll
+        for (int q = 1; q < R; ++q)
+            acc[q] += h * lrow[(int64_t)q * nk + j];
+    }
+    const double tail = tails[b];
+    double v = wave_sum(acc[0]) + tail * tc[i * R];
+    if (__any(hit) && v == v)
+        v = -INFINITY;
+    const bool finite = v - v == 0.0;
+    if (lane == 0)
+        out[i * R] = v;
+#pragma unroll
+    for (int q = 1; q < R; ++q) {
+        const double g = wave_sum(acc[q]) + tail * tc[i * R + q];
+        if (lane == 0)
+            out[i * R + q] = finite ? g : NAN;
+    }
+}
+
+__global__ __launch_bounds__(256) void batch_tail_pack_kernel(const double *__restrict__ fin_ll,
+                                                              const double *__restrict__ fin_grad, const int64_t n,
+                                                              const int R, double *__restrict__ tc)
+{
+    const int64_t total = n * R;
+    for (int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; at < total; at += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = at / R;
+        const int q = (int)(at - i * R);
+        tc[at] = q == 0 ? fin_ll[i] : fin_grad[i * (R - 1) + (q - 1)];
+    }
+}
+
+__global__ __launch_bounds__(256) void batch_grad_specials_kernel(const int64_t n_hist, const int64_t n, const int R,
+                                                                  double *out, const int64_t ld)
+{
+    const int64_t total = n_hist * n;
+    for (int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; at < total; at += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = at / n, i = at - b * n;
+        double *e = out + b * ld + i * R;
+        const double v = e[0];
+        if (!(v - v == 0.0))
+            for (int q = 1; q < R; ++q)
+                e[q] = NAN;
+    }
+}
+
 __global__ void batch_argmin_init_kernel(const int64_t n_hist, double *run_val, int64_t *run_idx)
 {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -315,6 +386,51 @@ hipError_t launch_batch_pairs(const double *H, const double *tails, const int64_
         hipLaunchKernelGGL(batch_pairs_kernel, dim3((unsigned)((cnt + kWavesPerBlock - 1) / kWavesPerBlock)),
                            dim3(kWavesPerBlock * kWave), 0, stream, H, tails, index, table, tl, n, n_keys, out, w0);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_tail_pack(const double *fin_ll, const double *fin_grad, int64_t n, int rows_per_point, double *tc,
+                                  hipStream_t stream)
+{
+    const int64_t total = n * rows_per_point;
+    if (total <= 0)
+        return hipSuccess;
+    const int64_t blocks = std::min<int64_t>((total + 255) / 256, (int64_t)1 << 16);
+    hipLaunchKernelGGL(batch_tail_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, fin_ll, fin_grad, n,
+                       rows_per_point, tc);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_pairs_grad(const double *H, const double *tails, const int64_t *index, const double *rows,
+                                   const double *tc, int64_t n, int64_t n_keys, int rows_per_point, double *out,
+                                   hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    if (rows_per_point != 3 && rows_per_point != 6)
+        return hipErrorInvalidValue;
+    const int64_t per_launch = kWavesPerBlock * kMaxBlocks;
+    for (int64_t k = 0; k < batch_launch_parts(n, per_launch); ++k) {
+        int64_t w0, cnt;
+        batch_launch_part(n, per_launch, k, &w0, &cnt);
+        const dim3 grid((unsigned)((cnt + kWavesPerBlock - 1) / kWavesPerBlock)), block(kWavesPerBlock * kWave);
+        if (rows_per_point == 3)
+            hipLaunchKernelGGL((batch_pairs_grad_kernel<3>), grid, block, 0, stream, H, tails, index, rows, tc, n, n_keys, out, w0);
+        else
+            hipLaunchKernelGGL((batch_pairs_grad_kernel<6>), grid, block, 0, stream, H, tails, index, rows, tc, n, n_keys, out, w0);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_grad_specials(int64_t n_hist, int64_t n, int rows_per_point, double *out, int64_t ld,
+                                      hipStream_t stream)
+{
+    const int64_t total = n_hist * n;
+    if (total <= 0)
+        return hipSuccess;
+    const int64_t blocks = std::min<int64_t>((total + 255) / 256, (int64_t)1 << 16);
+    hipLaunchKernelGGL(batch_grad_specials_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, n_hist, n, rows_per_point, out,
+                       ld);
     return hipGetLastError();
 }
 

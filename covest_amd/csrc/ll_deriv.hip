@@ -29,6 +29,7 @@
 //
 // Where a key's p_j is a subnormal double nothing is handed back: the terms are formed one by one as K-direct forms them.
 #include <hip/hip_runtime.h>
+#include <tuple>
 
 #include "direct_point.h"
 #include "grad_common.h"
@@ -74,10 +75,25 @@ __device__ __forceinline__ void hess_coef(double a, double da, double dap, doubl
     al = d2a - l1 * cross - a * l1 * d2x + a * xx * (l1 * l1 - l2);
 }
 
-template <int P, int ORDER>
+// TABLE (order 1 only) is the same walk with its per-key quantities stored on the way, before the
+// counts enter: Extra is then (double *rows, int32_t *dead) -- into row (P + 1) pt of `rows` (n_bins doubles a row) goes
+// log p_j, behind it the P rows d_k p_j / p_j, and dead[pt] (zeroed by the launcher) counts the keys with p_j <= 0.  It
+// is launched on the batch's all-keys view with zero counts and tail 1, so that the segment sums are those of the pure
+// tail term and ll_deriv_finish_kernel<P, 1> returns the tail coefficients.  The stores sit in the key epilogue behind
+// `if constexpr`; without TABLE the pack is empty and the six instantiations compile to the instructions they had.
+template <int P, int ORDER, bool TABLE = false, class... Extra>
 __global__ __launch_bounds__(kDerivWaves *kWave) void ll_deriv_kernel(const DevModel m, const PointSource src,
-                                                                      double *__restrict__ partial)
+                                                                      double *__restrict__ partial, Extra... extra)
 {
+    static_assert(!TABLE || ORDER == 1, "the score table is first order");
+    static_assert(sizeof...(Extra) == (TABLE ? 2 : 0), "TABLE takes (double *rows, int32_t *dead)");
+    double *rows = nullptr;
+    int32_t *dead = nullptr;
+    if constexpr (TABLE) {
+        const std::tuple<Extra...> table(extra...);
+        rows = std::get<0>(table);
+        dead = std::get<1>(table);
+    }
     using L = DerivLayout<P, ORDER>;
     constexpr int NQ = L::kSums, STRIDE = L::kStride, NP = L::kPairs;
     constexpr int NP1 = NP > 0 ? NP : 1; // (an array's length)
@@ -98,7 +114,19 @@ __global__ __launch_bounds__(kDerivWaves *kWave) void ll_deriv_kernel(const DevM
         double par[kMaxParams];
         int T;
         fetch_point<P>(src, pt, par, T);
-        clamp_point<P>(m, par);
+        bool moved[P]; // (TABLE) the clamp moved the parameter: its score row is 0, K-grad's rule
+        if constexpr (TABLE) {
+            double raw[P];
+#pragma unroll
+            for (int d = 0; d < P; ++d)
+                raw[d] = par[d];
+            clamp_point<P>(m, par);
+#pragma unroll
+            for (int d = 0; d < P; ++d)
+                moved[d] = par[d] != raw[d];
+        } else {
+            clamp_point<P>(m, par);
+        }
 
         const int S = m.n_err;
         const int OT = kWave / S; // copy-number classes prepared per tile
@@ -322,6 +350,24 @@ __global__ __launch_bounds__(kDerivWaves *kWave) void ll_deriv_kernel(const DevM
 #pragma unroll
             for (int q = 0; q < NP; ++q)
                 val[L::kDD + q] = p2[q];
+            if constexpr (TABLE) {
+                // the batch table's conventions (ll_batch.hip): +0.0 is a dead key's and nothing else's, p = 1 is -0.0,
+                // NaN stays NaN; a dead key's scores are +0.0, so that a histogram that does not count it adds 0
+                double *row = rows + (int64_t)pt * (P + 1) * n_bins + idx;
+                const bool is_dead = p <= 0.0;
+                double l = 0.0;
+                if (!is_dead) {
+                    l = log(p);
+                    if (l == 0.0)
+                        l = -0.0;
+                }
+                row[0] = l;
+#pragma unroll
+                for (int d = 0; d < P; ++d)
+                    row[(int64_t)(1 + d) * n_bins] = (is_dead || moved[d]) ? 0.0 : p1[d] / p;
+                if (is_dead)
+                    atomicAdd(dead + pt, 1);
+            }
             if (h != 0.0) {
                 const double term = h * ((p <= 0.0) ? -INFINITY : log(p));
                 if (term - term == 0.0) // finite
@@ -489,10 +535,16 @@ __global__ __launch_bounds__(kWave) void ll_deriv_finish_kernel(const DevModel m
 
 template <int P, int ORDER>
 void launch_part(const DevModel &m, const PointSource &part, int n_seg, int64_t cnt, double *partial, double *out_ll,
-                 double *out_grad, double *out_hess, hipStream_t stream)
+                 double *out_grad, double *out_hess, double *rows, int32_t *dead, hipStream_t stream)
 {
-    hipLaunchKernelGGL((ll_deriv_kernel<P, ORDER>), dim3((unsigned)n_seg, (unsigned)cnt), dim3(kDerivWaves * kWave), 0, stream, m,
-                       part, partial);
+    if (rows) {
+        if constexpr (ORDER == 1)
+            hipLaunchKernelGGL((ll_deriv_kernel<P, 1, true, double *, int32_t *>), dim3((unsigned)n_seg, (unsigned)cnt), dim3(kDerivWaves * kWave), 0,
+                               stream, m, part, partial, rows, dead);
+    } else {
+        hipLaunchKernelGGL((ll_deriv_kernel<P, ORDER>), dim3((unsigned)n_seg, (unsigned)cnt), dim3(kDerivWaves * kWave), 0,
+                           stream, m, part, partial);
+    }
     hipLaunchKernelGGL((ll_deriv_finish_kernel<P, ORDER>), dim3((unsigned)cnt), dim3(kWave), 0, stream, m, part, n_seg, partial,
                        out_ll, out_grad, out_hess);
 }
@@ -522,12 +574,15 @@ size_t ll_deriv_partial_bytes(const DevModel &m, int order, int64_t n)
     return (size_t)pts * (size_t)ll_deriv_segments(m) * (size_t)stride * sizeof(double);
 }
 
-hipError_t launch_ll_deriv(const DevModel &m, int order, const PointSource &src, int64_t n, double *partial, double *out_ll,
-                           double *out_grad, double *out_hess, hipStream_t stream)
+namespace {
+
+// the launches of a point list, cut at kDerivPointsPerLaunch points; rows != nullptr: the table-writing walk (order 1)
+hipError_t deriv_launches(const DevModel &m, int order, const PointSource &src, int64_t n, double *partial, double *out_ll,
+                          double *out_grad, double *out_hess, double *rows, int32_t *dead, hipStream_t stream)
 {
     if (n <= 0)
         return hipSuccess;
-    if (src.is_grid || (order != 1 && order != 2 && order != kDerivOpg))
+    if (src.is_grid || (order != 1 && order != 2 && order != kDerivOpg) || (rows && (order != 1 || !dead)))
         return hipErrorInvalidValue;
     const int n_seg = ll_deriv_segments(m);
     const int P = m.kind == 0 ? 2 : 5;
@@ -539,11 +594,32 @@ hipError_t launch_ll_deriv(const DevModel &m, int order, const PointSource &src,
         part.params = src.params + first * P;
         part.t_list = src.t_list ? src.t_list + first : nullptr;
         launch(m, part, n_seg, cnt, partial, out_ll + first, out_grad + first * P,
-               order != 1 ? out_hess + first * P * P : nullptr, stream);
-        record_launch(kDerivVariantNames[(P == 5 ? 3 : 0) + (order == 1 ? 0 : order == 2 ? 1 : 2)]);
+               order != 1 ? out_hess + first * P * P : nullptr, rows ? rows + first * (P + 1) * m.bins.n : nullptr,
+               rows ? dead + first : nullptr, stream);
+        if (!rows) // (the table-writing walk is the batch's: not a variant of the launch record)
+            record_launch(kDerivVariantNames[(P == 5 ? 3 : 0) + (order == 1 ? 0 : order == 2 ? 1 : 2)]);
         record_launch(kDerivVariantNames[kDerivVariants - 1]);
     }
     return hipGetLastError();
+}
+
+} // namespace
+
+hipError_t launch_ll_deriv(const DevModel &m, int order, const PointSource &src, int64_t n, double *partial, double *out_ll,
+                           double *out_grad, double *out_hess, hipStream_t stream)
+{
+    return deriv_launches(m, order, src, n, partial, out_ll, out_grad, out_hess, nullptr, nullptr, stream);
+}
+
+hipError_t launch_ll_deriv_table(const DevModel &m, const PointSource &src, int64_t n, double *partial, double *rows,
+                                 int32_t *dead, double *out_ll, double *out_grad, hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    const hipError_t err = hipMemsetAsync(dead, 0, (size_t)n * sizeof(int32_t), stream);
+    if (err != hipSuccess)
+        return err;
+    return deriv_launches(m, 1, src, n, partial, out_ll, out_grad, nullptr, rows, dead, stream);
 }
 
 } // namespace covest

@@ -229,9 +229,15 @@ class CoverageEstimator:
         err_scale * e); the components of `fix`-ed parameters are 0."""
         pts = np.array([self._model_args(x) for x in xs], dtype=np.float64)
         ll, grad = self.model.loglikelihood_gradient_points(pts)
-        out = np.empty((len(pts), 1 + pts.shape[1]), dtype=np.float64)
+        return self._optimiser_rows(ll, grad)
+
+    def _optimiser_rows(self, ll, grad):
+        """Model-space log-likelihoods (n,) and gradients (n, P) as the rows negll_gradient_points returns:
+        [-LL, d(-LL)/dx ...] in optimiser space (the error-rate component over err_scale, `fix`-ed components 0)."""
+        grad = np.asarray(grad, dtype=np.float64)
+        out = np.empty((grad.shape[0], 1 + grad.shape[1]), dtype=np.float64)
         out[:, 0] = -np.asarray(ll, dtype=np.float64)
-        out[:, 1:] = -np.asarray(grad, dtype=np.float64)
+        out[:, 1:] = -grad
         out[:, 1 + self.ERROR_RATE] /= self.err_scale
         if self.fix is not None:
             for i, f in enumerate(self.fix):

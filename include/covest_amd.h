@@ -529,8 +529,24 @@ int covest_draw_histograms_device(int32_t device, int64_t m, const uint64_t *d_t
  *                           tiles the cross contraction covered, points with keys of p <= 0, fix-up waves launched
  *                           (one per such point and histogram), pairs requests, and the device time in nanoseconds of
  *                           the table kernels and of the contraction kernels.
+ *   covest_batch_eval_cross_grad, covest_batch_eval_pairs_grad  the same two forms with the analytic gradient (DESIGN.md
+ *                           section 6u): per (histogram, point) param_count + 1 doubles, [0] the log-likelihood and
+ *                           [1 + k] its derivative in parameter k at the point after fit_to_bounds (0 for a parameter the
+ *                           clamp moved; every derivative NaN where the value is not finite).  The per-key score
+ *                           r_k(j) = d_k p_j / p_j does not depend on the counts either:
+ *                             d_k LL_b = sum_j h_bj r_k(j) - tail_b [sp < 1] S_k / (1 - sp),   S_k = sum_j d_k p_j,
+ *                           so the table has param_count + 1 rows a point, written by the derivative kernel's walk
+ *                           (covest_eval_points_grad's arithmetic), and the value returned here is THAT kernel's: it
+ *                           agrees with covest_batch_eval_cross / _pairs to 1e-11 relative, not to the bit.
+ *   covest_batch_score_table  that table itself: out_rows[n][param_count + 1][n_keys] -- row 0 log p_ij (+0.0 where
+ *                           p_ij <= 0 and nowhere else: p = 1 is stored as -0.0; NaN stays NaN), rows 1 + k the scores
+ *                           (+0.0 at such a key, and throughout where the clamp moved parameter k) -- and
+ *                           out_tail[n][param_count + 1]: log(1 - sp_i), then -S_k / (1 - sp_i); all 0 where sp_i is
+ *                           not < 1.  It does not depend on the histograms.
  * params is [n][param_count] as for covest_eval_points.  The table of log p is built for at most 256 MiB of points at
- * a time; the chunking changes no value.  A batch has NO gradient.
+ * a time (the gradient's table holds param_count + 1 rows a point, so a chunk has that many times fewer points); the
+ * chunking changes no value.  In covest_batch_info a gradient call counts points (not rows) as tabled and its requests
+ * as pairs requests; the time fields cover its kernels.
  * A batch borrows its model: destroy the batch first.  Every call takes the model's lock and runs on the model's
  * device.  COVEST_E_INVALID: a NULL argument, a negative size, a count or tail that is negative, NaN or infinite, more
  * than 2^20 histograms, an index outside 0 .. n_hist - 1, a model without keys, and for covest_batch_draw what
@@ -543,6 +559,12 @@ int covest_batch_counts(covest_batch *b, double *out_counts, double *out_tails);
 int covest_batch_eval_cross(covest_batch *b, int64_t n, const double *params, double *out_ll);
 int covest_batch_eval_pairs(covest_batch *b, int64_t n, const int64_t *hist_index, const double *params, double *out_ll);
 int covest_batch_argmin_cross(covest_batch *b, int64_t n, const double *params, double *out_min_negll, int64_t *out_arg);
+int covest_batch_eval_cross_grad(covest_batch *b, int64_t n, const double *params, double *out);
+    /* out: B x n x (P+1); [..][0] the log-likelihood, [..][1+k] its derivative in parameter k */
+int covest_batch_eval_pairs_grad(covest_batch *b, int64_t n, const int64_t *hist_index, const double *params, double *out);
+    /* out: n x (P+1) */
+int covest_batch_score_table(covest_batch *b, int64_t n, const double *params, double *out_rows, double *out_tail);
+    /* out_rows: n x (P+1) x n_keys as the device holds them; out_tail: n x (P+1) */
 int covest_batch_info(covest_batch *b, int64_t *out);
 void covest_batch_destroy(covest_batch *b);
 
