@@ -27,7 +27,7 @@ EXPORTS = (
     "covest_probabilities", "covest_reference_overflow", "covest_grid_create", "covest_grid_reset", "covest_grid_destroy", "covest_grid_size",
     "covest_grid_eval", "covest_grid_eval_scan", "covest_grid_scan", "covest_grid_argmin", "covest_grid_axis_min", "covest_grid_argmin_pair_device",
     "covest_grid_ll_device",
-    "covest_grid_ll_host",
+    "covest_grid_ll_host", "covest_grid_complete", "covest_grid_fix_eager", "covest_grid_ll_provisional_host",
     "covest_grid_work", "covest_grid_profile", "covest_grid_kernel_ms", "covest_grid_diag",
     "covest_grid_launch_record", "covest_model_launch_record", "covest_compiled_variants",
     "covest_kmer_create", "covest_kmer_destroy", "covest_kmer_reserve", "covest_kmer_add",
@@ -166,6 +166,12 @@ def lib():
     L.covest_grid_ll_device.argtypes = [vp]
     L.covest_grid_ll_host.restype = ctypes.c_int
     L.covest_grid_ll_host.argtypes = [vp, dp]
+    L.covest_grid_complete.restype = ctypes.c_int
+    L.covest_grid_complete.argtypes = [vp]
+    L.covest_grid_fix_eager.restype = ctypes.c_int
+    L.covest_grid_fix_eager.argtypes = [vp, ctypes.c_int32]
+    L.covest_grid_ll_provisional_host.restype = ctypes.c_int
+    L.covest_grid_ll_provisional_host.argtypes = [vp, dp]
     L.covest_grid_work.restype = ctypes.c_int
     L.covest_grid_work.argtypes = [vp, dp, dp, ctypes.POINTER(ctypes.c_char_p)]
     L.covest_grid_profile.restype = ctypes.c_int

@@ -110,7 +110,8 @@ int stage_inputs(covest_grid *g, const GridArena &a, int32_t n_axes, const doubl
                  const std::vector<int32_t> &table, int64_t n, char **inputs)
 {
     const void *arena_before = g->arena.ptr;
-    const bool counter_clean = g->counter_clean; // (the queue counter is 0: set by grid_configure, kept by every arg-min launch)
+    const bool counter_clean = g->counter_clean; // (the queue counter is 0: set by grid_configure; an evaluation clears the
+                                                 // mark and sets it again once its arg-min, which resets the counter, is launched)
     HIP_TRY(g->arena.reserve(a.bytes));
     char *base = g->arena.as<char>();
     StageSlot slot;
@@ -201,6 +202,7 @@ static int grid_configure(covest_grid *g, int32_t n_axes, const double *const *a
     g->flat_begin = flat_begin;
     g->flat_end = flat_end;
     g->evaluated = false;
+    g->fix_pending = false; // (a strict pass still owed is dropped with the values it was owed for)
     g->scan_valid = false;
     g->ev_used = 0;
     g->stage_off = 0; // (a reset waited for the stream of the last evaluation: what the last reset staged has been copied)
@@ -432,6 +434,56 @@ static int report_queue(covest_grid *g, hipStream_t st, int64_t n)
 }
 #endif
 
+// The hand-back queue as the recurrence kernel of an evaluation fills it (counter: the first word of sub_ctl) and as a
+// strict pass that was put off finds it (the second word, where the arg-min left the queue's length: argmin.hip).
+static SubList grid_queue(const covest_grid *g, bool put_off)
+{
+    return sub_list_of(g->model, g->has_plan ? g->t_max : 2, g->sub_index.ptr, g->sub_word.ptr,
+                       g->sub_ctl.as<unsigned>() + (put_off ? 1 : 0));
+}
+
+// THE STRICT RE-EVALUATION PUT OFF.  What the pass of ll_fix.hip does is correct the values of the points that were handed
+// back -- 2 962 of C3's 262 144, 7 791 of C2's 10^6 -- by adding non-positive terms to them (ll_fix.hip: value = ll[pt],
+// then value += h_j (safe_log(p_j) - log p_clamp) per row with p_j < p_clamp), and the arg-min can be had without it
+// (argmin.hip winner_unproven).  So a plain covest_grid_eval leaves it out, and whoever reads the values, or asks what was
+// launched, gets it first: the pass on the evaluation's stream, over the very queue and with the very arguments the
+// evaluation would have launched it with -- the values are the same bit for bit --, then the arg-min again, so that the
+// pair in HBM and its host mirror describe the final values.  Nothing is owed: nothing happens.  The caller holds the
+// model's lock and has the handle's device current.  *launched (or nullptr): whether anything went onto the stream.
+static int grid_complete(covest_grid *g, bool *launched = nullptr)
+{
+    if (launched)
+        *launched = false;
+    if (!g->fix_pending)
+        return COVEST_OK;
+    const covest_model *m = g->model;
+    const int64_t n = g->flat_end - g->flat_begin;
+    hipStream_t st = g->last_stream;
+    LaunchRecordScope record(g->record, true);
+    HIP_TRY(launch_ll_fix_list(m->dm, m->tv, g->src, g->ll.as<double>(), grid_queue(g, true), st, n));
+    HIP_TRY(launch_argmin(g->ll.as<double>(), n, g->flat_begin, g->partial_val.as<double>(), g->partial_idx.as<int64_t>(),
+                          g->result.as<ArgminResult>(), g->result_host, nullptr, st));
+    g->fix_pending = false;
+    if (launched)
+        *launched = true;
+    return COVEST_OK;
+}
+
+// grid_complete from an entry point that holds nothing yet
+static int grid_complete_entry(covest_grid *g, bool *launched = nullptr)
+{
+    if (launched)
+        *launched = false;
+    if (!g->fix_pending)
+        return COVEST_OK;
+    covest_model *m = g->model;
+    std::lock_guard<std::mutex> guard(m->lock);
+    DeviceGuard dev_guard(m->device);
+    if (dev_guard.status() != COVEST_OK)
+        return dev_guard.status();
+    return grid_complete(g, launched);
+}
+
 static int grid_eval(covest_grid *g, int32_t kernel, void *stream, bool scan, double scan_start)
 {
     if (!g)
@@ -452,12 +504,19 @@ static int grid_eval(covest_grid *g, int32_t kernel, void *stream, bool scan, do
     const int64_t n = g->flat_end - g->flat_begin;
     if (g->upload_pending && st != nullptr && g->upload_ev)
         HIP_TRY(hipStreamWaitEvent(st, g->upload_ev, 0)); // (covest_grid_reset's copies run on the null stream)
+    g->fix_pending = false;   // (a strict pass still owed for the last evaluation: dropped, its values are overwritten)
+    g->counter_clean = false; // (until the arg-min below is launched: a failure on the way leaves the counter as it is)
+    // The strict pass is put off where a recurrence kernel hands points back and the caller asked for no scan (its records
+    // are strict running minima: made on final values; covest_grid_eval_scan is optimize_grid's, grids of a few thousand
+    // points whose pass is 5 us)
+    const bool hands_back = kern == COVEST_KERNEL_RECUR || (kern == COVEST_KERNEL_FACTORED && g->has_short_part);
+    const bool put_off = hands_back && !scan && !g->fix_eager;
     hipEvent_t bracket_end = nullptr;
     rc = bracket_begin(g, st, &bracket_end);
     if (rc != COVEST_OK)
         return rc;
-    HIP_TRY(launch_ll(m, kern, g->src, n, g->ll.as<double>(), sub_list_of(m, g->has_plan ? g->t_max : 2, g->sub_index.ptr, g->sub_word.ptr, g->sub_ctl.ptr), st,
-                      &g->last_kernel, g));
+    HIP_TRY((put_off ? launch_ll_unfixed : launch_ll)(m, kern, g->src, n, g->ll.as<double>(), grid_queue(g, false), st,
+                                                      &g->last_kernel, g));
     g->last_kernel_id = kern;
     if (bracket_end)
         HIP_TRY(hipEventRecord(bracket_end, st));
@@ -477,8 +536,11 @@ static int grid_eval(covest_grid *g, int32_t kernel, void *stream, bool scan, do
         HIP_TRY(launch_argmin_scan(g->ll.as<double>(), n, g->flat_begin, scan_start, g->result.as<ArgminResult>(), g->result_host,
                                    g->scan_host(), g->sub_ctl.as<unsigned>(), st));
     else
-        HIP_TRY(launch_argmin(g->ll.as<double>(), n, g->flat_begin, g->partial_val.as<double>(),
-                              g->partial_idx.as<int64_t>(), g->result.as<ArgminResult>(), g->result_host, g->sub_ctl.as<unsigned>(), st));
+        HIP_TRY(launch_argmin_proving(g->ll.as<double>(), n, g->flat_begin, g->partial_val.as<double>(),
+                                      g->partial_idx.as<int64_t>(), g->result.as<ArgminResult>(), g->result_host,
+                                      g->sub_ctl.as<unsigned>(), put_off ? g->sub_index.as<int64_t>() : nullptr, st));
+    g->counter_clean = true;
+    g->fix_pending = put_off;
     g->last_stream = st;
     g->evaluated = true;
     return COVEST_OK;
@@ -489,6 +551,22 @@ int covest_grid_eval(covest_grid *g, int32_t kernel, void *stream) { return grid
 int covest_grid_eval_scan(covest_grid *g, int32_t kernel, void *stream, double start_min)
 {
     return grid_eval(g, kernel, stream, true, start_min);
+}
+
+int covest_grid_complete(covest_grid *g)
+{
+    if (!g)
+        return fail(COVEST_E_INVALID, "covest_grid_complete: null grid");
+    return grid_complete_entry(g);
+}
+
+int covest_grid_fix_eager(covest_grid *g, int32_t eager)
+{
+    if (!g)
+        return fail(COVEST_E_INVALID, "covest_grid_fix_eager: null grid");
+    COVEST_TRY(grid_complete_entry(g));
+    g->fix_eager = eager != 0;
+    return COVEST_OK;
 }
 
 int covest_grid_scan(covest_grid *g, int32_t cap, int64_t *index, double *negll, int32_t *n_records, int32_t *truncated)
@@ -522,6 +600,8 @@ int64_t covest_grid_launch_record(const covest_grid *g, char *buf, int64_t cap)
 {
     if (!g || cap < 0 || (cap > 0 && !buf))
         return fail(COVEST_E_INVALID, "covest_grid_launch_record: bad argument");
+    // (a handle is never a const object: the signature is the ABI's, the strict pass still owed belongs to the record)
+    COVEST_TRY(grid_complete_entry(const_cast<covest_grid *>(g)));
     return launch_record_text(g->record, buf, cap);
 }
 
@@ -536,6 +616,11 @@ int covest_grid_argmin(covest_grid *g, double *min_negll, int64_t *argmin_flat)
     if (rc != COVEST_OK)
         return rc;
     HIP_TRY(hipStreamSynchronize(g->last_stream));
+    if (g->fix_pending && g->result_host->unproven != 0) {
+        // a queued point's final value could change the winner (argmin.hip winner_unproven): the strict pass after all
+        COVEST_TRY(grid_complete_entry(g));
+        HIP_TRY(hipStreamSynchronize(g->last_stream));
+    }
     const ArgminResult r = *g->result_host; // (the arg-min kernel's own store: covest_grid_eval)
     *min_negll = r.min_negll;
     *argmin_flat = r.index < 0 ? -1 : g->flat_begin + r.index;
@@ -573,6 +658,7 @@ int covest_grid_axis_min(covest_grid *g, uint32_t keep_mask, int64_t n_cells, do
     double *part_v = reinterpret_cast<double *>(out_i + nc);
     int64_t *part_i = reinterpret_cast<int64_t *>(part_v + n_part);
     hipStream_t st = g->last_stream; // (behind the evaluation it reduces)
+    COVEST_TRY(grid_complete(g));
     HIP_TRY(launch_axis_min(p, g->ll.as<double>(), part_v, part_i, out_v, out_i, st));
     if (16 * nc <= ((size_t)1 << 20)) { // one copy into page-locked memory (a pageable target costs a staging per call)
         HIP_TRY(g->axis_host.reserve(16 * nc));
@@ -588,11 +674,35 @@ int covest_grid_axis_min(covest_grid *g, uint32_t keep_mask, int64_t n_cells, do
     return COVEST_OK;
 }
 
-const double *covest_grid_ll_device(const covest_grid *g) { return g ? g->ll.as<double>() : nullptr; }
+// (a handle is never a const object: the two signatures are the ABI's)
+const double *covest_grid_ll_device(const covest_grid *g)
+{
+    if (!g)
+        return nullptr;
+    // the strict pass still owed, and the wait for it: a caller that waited for the stream before it asked stays right
+    bool launched = false;
+    if (grid_complete_entry(const_cast<covest_grid *>(g), &launched) != COVEST_OK)
+        return nullptr;
+    if (launched) {
+        DeviceGuard dev_guard(g->model->device);
+        if (dev_guard.status() != COVEST_OK || hipStreamSynchronize(g->last_stream) != hipSuccess)
+            return nullptr;
+    }
+    return g->ll.as<double>();
+}
 
 const double *covest_grid_argmin_pair_device(const covest_grid *g)
 {
-    return g ? g->result.as<ArgminResult>()->pair : nullptr; // (address arithmetic only: nothing is read here)
+    if (!g)
+        return nullptr;
+    // Who takes the pair where it lies consumes it on the stream without a visit of the host (the ranks' exchange), so
+    // nobody could act on an unproven winner: the pass still owed now, and inside every evaluation of this handle from
+    // here on -- a second arg-min every step would cost more than the pass.
+    covest_grid *gm = const_cast<covest_grid *>(g);
+    if (grid_complete_entry(gm) != COVEST_OK)
+        return nullptr;
+    gm->fix_eager = true;
+    return g->result.as<ArgminResult>()->pair; // (address arithmetic only: nothing is read here)
 }
 
 int covest_grid_ll_host(covest_grid *g, double *out_ll)
@@ -601,6 +711,24 @@ int covest_grid_ll_host(covest_grid *g, double *out_ll)
         return fail(COVEST_E_INVALID, "covest_grid_ll_host: null argument");
     if (!g->evaluated)
         return fail(COVEST_E_INVALID, "covest_grid_ll_host: covest_grid_eval has not run");
+    DeviceGuard dev_guard(g->model->device);
+    int rc = dev_guard.status();
+    if (rc != COVEST_OK)
+        return rc;
+    const int64_t n = g->flat_end - g->flat_begin;
+    COVEST_TRY(grid_complete_entry(g));
+    HIP_TRY(hipStreamSynchronize(g->last_stream));
+    if (n > 0)
+        HIP_TRY(hipMemcpy(out_ll, g->ll.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return COVEST_OK;
+}
+
+int covest_grid_ll_provisional_host(covest_grid *g, double *out_ll)
+{
+    if (!g || !out_ll)
+        return fail(COVEST_E_INVALID, "covest_grid_ll_provisional_host: null argument");
+    if (!g->evaluated || !g->fix_pending)
+        return fail(COVEST_E_INVALID, "covest_grid_ll_provisional_host: no strict pass is owed for the last evaluation");
     DeviceGuard dev_guard(g->model->device);
     int rc = dev_guard.status();
     if (rc != COVEST_OK)

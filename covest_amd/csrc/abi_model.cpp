@@ -220,7 +220,9 @@ int resolve_kernel(const covest_model *m, int32_t kernel, const covest_grid *g)
 // K-factored on a dense grid: the part whose weight vectors fit a workgroup's lanes writes log-likelihoods (and is
 // followed by the pass that patches what it handed back); the long weight vectors go chunk by chunk of copy numbers
 // into an HBM buffer of p_j, one batch of (c, e) rows at a time, and ll_finish_dense takes their logs.
-static hipError_t launch_factored_grid(covest_grid *g, double *out, const SubList &sub, hipStream_t st)
+// with_fix == false: the patching pass is the caller's to launch, any time before the short part's values are read (the
+// long weight vectors are other points of the grid: nothing below reads or writes what the pass touches).
+static hipError_t launch_factored_grid(covest_grid *g, double *out, const SubList &sub, hipStream_t st, bool with_fix)
 {
     const covest_model *m = g->model;
     if (g->has_short_part) {
@@ -228,7 +230,8 @@ static hipError_t launch_factored_grid(covest_grid *g, double *out, const SubLis
         hipError_t e = launch_ll_factored(m->dm, m->tv, g->plan, out, sub, st);
         if (e != hipSuccess)
             return e;
-        e = launch_ll_fix_list(m->dm, m->tv, g->src, out, sub, st, g->flat_end - g->flat_begin);
+        if (with_fix)
+            e = launch_ll_fix_list(m->dm, m->tv, g->src, out, sub, st, g->flat_end - g->flat_begin);
         if (e != hipSuccess)
             return e;
     }
@@ -282,23 +285,38 @@ SubList sub_list_of(const covest_model *m, int t_max, void *index, void *word, v
 
 // `sub`: the queue the recurrence kernels append the points they hand back to (handback.h) -- drained right
 // behind them by the fix pass; K-direct has nothing to hand back.  The queue must be empty (counter 0) on entry.
-hipError_t launch_ll(const covest_model *m, int kernel, const PointSource &src, int64_t n, double *out, const SubList &sub,
-                     hipStream_t st, const char **name, const covest_grid *g)
+static hipError_t launch_ll_with(const covest_model *m, int kernel, const PointSource &src, int64_t n, double *out,
+                                 const SubList &sub, hipStream_t st, const char **name, const covest_grid *g, bool with_fix)
 {
     if (kernel == COVEST_KERNEL_FACTORED) {
         if (name)
             *name = "ll_factored";
-        return launch_factored_grid(const_cast<covest_grid *>(g), out, sub, st);
+        return launch_factored_grid(const_cast<covest_grid *>(g), out, sub, st, with_fix);
     }
     if (kernel == COVEST_KERNEL_RECUR) {
         if (name)
             *name = "ll_basic";
         hipError_t e = launch_ll_basic(m->dm, m->tv, src, n, out, sub, st);
-        return e != hipSuccess ? e : launch_ll_fix_list(m->dm, m->tv, src, out, sub, st, n);
+        return e != hipSuccess || !with_fix ? e : launch_ll_fix_list(m->dm, m->tv, src, out, sub, st, n);
     }
     if (name)
         *name = kernel == COVEST_KERNEL_DIRECT_REF ? "ll_direct_ref" : "ll_direct";
     return launch_ll_direct(m->dm, src, n, out, nullptr, st, kernel == COVEST_KERNEL_DIRECT_REF);
+}
+
+hipError_t launch_ll(const covest_model *m, int kernel, const PointSource &src, int64_t n, double *out, const SubList &sub,
+                     hipStream_t st, const char **name, const covest_grid *g)
+{
+    return launch_ll_with(m, kernel, src, n, out, sub, st, name, g, true);
+}
+
+// The same WITHOUT the pass that patches the handed-back points: the queue is left as the recurrence kernel filled it,
+// the queued points' values provisional (handback.h) -- a grid handle's, whose launch_ll_fix_list comes when somebody
+// reads the values (abi_grid.cpp grid_complete).
+hipError_t launch_ll_unfixed(const covest_model *m, int kernel, const PointSource &src, int64_t n, double *out,
+                             const SubList &sub, hipStream_t st, const char **name, const covest_grid *g)
+{
+    return launch_ll_with(m, kernel, src, n, out, sub, st, name, g, false);
 }
 
 } // namespace covest

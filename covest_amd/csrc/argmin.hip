@@ -65,11 +65,12 @@ __global__ __launch_bounds__(256) void argmin_stage1(const double *__restrict__ 
 // page-locked HOST mirror -- the kernel's own store, visible once the stream is synchronised: no copy launch and no
 // staging for 16 bytes.
 __device__ __forceinline__ void publish(Cand c, int64_t flat_begin, ArgminResult *__restrict__ result,
-                                        ArgminResult *__restrict__ host_mirror)
+                                        ArgminResult *__restrict__ host_mirror, bool unproven = false)
 {
     ArgminResult r;
     r.min_negll = c.v;
     r.index = (c.i == INT64_MAX) ? -1 : c.i;
+    r.unproven = unproven ? 1 : 0;
     // the same as a pair of doubles with the GLOBAL flat index, for the cross-GPU exchange (flat indices
     // stay below 2^53)
     r.pair[0] = c.v;
@@ -79,13 +80,80 @@ __device__ __forceinline__ void publish(Cand c, int64_t flat_begin, ArgminResult
         *host_mirror = r;
 }
 
-__global__ __launch_bounds__(256) void argmin_stage2(const double *__restrict__ pv,
+// The hand-back queue of the launch before, taken over by thread 0: its length goes to the control word BEHIND the
+// counter -- where a strict re-evaluation that was put off (abi_grid.cpp grid_complete) finds it -- and the counter starts
+// empty again.  Returns the length to thread 0; every thread reads it from *s_queued behind the next barrier.
+__device__ __forceinline__ void take_queue(unsigned *__restrict__ queue_count, unsigned *s_queued)
+{
+    if (threadIdx.x != 0)
+        return;
+    unsigned q = 0;
+    if (queue_count) {
+        q = queue_count[0];
+        queue_count[1] = q;
+        queue_count[0] = 0;
+    }
+    *s_queued = q;
+}
+
+// IS THE WINNER THE FINAL ONE while the queued points still hold their provisional values?  (The strict re-evaluation put
+// off: abi_grid.cpp.)  ll_fix.hip forms a queued point's final value by ADDING h_j (safe_log(p_j) - log p_clamp) <= 0, row
+// by row, to the provisional one, and touches no other point: a queued point's provisional -LL is a lower bound of its
+// final -LL, everybody else's value is final.  So the winner (v_w, i_w) over the provisional values stands under the
+// selection rule (strict <, lowest index, NaN never) unless it is queued itself or a queued point's provisional -LL
+// reaches v_w + 1e-9 |v_w| -- a safety margin, not a measurement: it covers the rounding of the pass's own adds (a
+// contribution whose device log lands an ulp above the host's log p_clamp) and exact ties.  A false alarm costs the
+// caller the strict pass and a second arg-min, nothing else.  Nothing won (every value +inf or NaN): a queued point's
+// -LL only rises, nothing can win afterwards either.  v_w = -inf: the bound is NaN and only the winner's own entry
+// counts -- a queued -inf at a lower index would have won, at a higher one it cannot.
+// `c` as block_best left it (thread 0's counts); a workgroup-wide answer.
+__device__ __forceinline__ bool winner_unproven(Cand c, const double *__restrict__ ll, const int64_t *__restrict__ queue_index,
+                                                const unsigned *s_queued)
+{
+    __shared__ double win_v;
+    __shared__ int64_t win_i;
+    if (threadIdx.x == 0) {
+        win_v = c.v;
+        win_i = c.i;
+    }
+    __syncthreads();
+    const double v_w = win_v;
+    const int64_t i_w = win_i;
+    const unsigned queued = *s_queued;
+    int threat = 0;
+    if (i_w != INT64_MAX) {
+        const double bound = v_w + 1e-9 * fabs(v_w);
+        // an entry is two dependent loads (the index, then the value): four entries' loads a thread are issued together,
+        // as small_grid_values does (one after the other, 256 threads: 0.6 us an entry and thread -- C2's 7 791 entries
+        // 18 us, more than the pass they spare the step)
+        for (unsigned base = threadIdx.x; base < queued; base += 4 * blockDim.x) {
+            int64_t i[4];
+            double v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const unsigned q = base + (unsigned)u * blockDim.x;
+                i[u] = q < queued ? queue_index[q] : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                v[u] = i[u] >= 0 ? -ll[i[u]] : INFINITY;
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                threat |= (v[u] <= bound || i[u] == i_w) ? 1 : 0;
+        }
+    }
+    return __syncthreads_or(threat) != 0;
+}
+
+// (256 threads; 1 024 where it walks the queue: launch_argmin_proving)
+__global__ __launch_bounds__(1024) void argmin_stage2(const double *__restrict__ ll, const int64_t *__restrict__ queue_index,
+                                                     const double *__restrict__ pv,
                                                      const int64_t *__restrict__ pi, int n_part, int64_t flat_begin,
                                                      ArgminResult *__restrict__ result, ArgminResult *__restrict__ host_mirror,
                                                      unsigned *__restrict__ queue_count)
 {
-    if (threadIdx.x == 0 && queue_count)
-        *queue_count = 0; // the hand-back queue of the launch before (drained by ll_fix_list_kernel) starts empty again
+    __shared__ unsigned s_queued;
+    take_queue(queue_count, &s_queued); // (drained by ll_fix_list_kernel already, or -- queue_index given -- still to be)
     Cand c;
     c.v = INFINITY;
     c.i = INT64_MAX;
@@ -96,8 +164,9 @@ __global__ __launch_bounds__(256) void argmin_stage2(const double *__restrict__ 
         c = better(c, o);
     }
     c = block_best(c);
+    const bool unproven = queue_index ? winner_unproven(c, ll, queue_index, &s_queued) : false; // (workgroup-uniform)
     if (threadIdx.x == 0)
-        publish(c, flat_begin, result, host_mirror);
+        publish(c, flat_begin, result, host_mirror, unproven);
 }
 
 // A small grid (optimize_grid's have a few thousand points, C1 2 500): both stages in ONE workgroup and one launch.
@@ -127,10 +196,10 @@ __device__ __forceinline__ void small_grid_values(const double *__restrict__ ll,
 
 __global__ __launch_bounds__(kSmallThreads) void argmin_small(const double *__restrict__ ll, int64_t n, int64_t flat_begin,
                                                              ArgminResult *__restrict__ result, ArgminResult *__restrict__ host_mirror,
-                                                             unsigned *__restrict__ queue_count)
+                                                             unsigned *__restrict__ queue_count, const int64_t *__restrict__ queue_index)
 {
-    if (threadIdx.x == 0 && queue_count)
-        *queue_count = 0;
+    __shared__ unsigned s_queued;
+    take_queue(queue_count, &s_queued);
     Cand c;
     c.v = INFINITY;
     c.i = INT64_MAX;
@@ -141,8 +210,9 @@ __global__ __launch_bounds__(kSmallThreads) void argmin_small(const double *__re
         }
     });
     c = block_best(c);
+    const bool unproven = queue_index ? winner_unproven(c, ll, queue_index, &s_queued) : false; // (workgroup-uniform)
     if (threadIdx.x == 0)
-        publish(c, flat_begin, result, host_mirror);
+        publish(c, flat_begin, result, host_mirror, unproven);
 }
 
 // The selection scan of covest/grid.py:65-70 ON THE DEVICE, for the caller that runs it every iteration
@@ -278,9 +348,19 @@ hipError_t launch_argmin_scan(const double *ll, int64_t n, int64_t flat_begin, d
 hipError_t launch_argmin(const double *ll, int64_t n, int64_t flat_begin, double *partial_val, int64_t *partial_idx,
                          ArgminResult *result, ArgminResult *host_mirror, unsigned *queue_count, hipStream_t stream)
 {
+    return launch_argmin_proving(ll, n, flat_begin, partial_val, partial_idx, result, host_mirror, queue_count, nullptr, stream);
+}
+
+hipError_t launch_argmin_proving(const double *ll, int64_t n, int64_t flat_begin, double *partial_val, int64_t *partial_idx,
+                                 ArgminResult *result, ArgminResult *host_mirror, unsigned *queue_count,
+                                 const int64_t *queue_index, hipStream_t stream)
+{
+    if (queue_index && !queue_count)
+        return hipErrorInvalidValue;
     if (n <= kArgminSmall) {
         record_launch(kArgminVariantNames[0]);
-        hipLaunchKernelGGL(argmin_small, dim3(1), dim3(kSmallThreads), 0, stream, ll, n, flat_begin, result, host_mirror, queue_count);
+        hipLaunchKernelGGL(argmin_small, dim3(1), dim3(kSmallThreads), 0, stream, ll, n, flat_begin, result, host_mirror, queue_count,
+                           queue_index);
         return hipGetLastError();
     }
     // (a small grid needs no more workgroups than it has waves of points)
@@ -290,8 +370,8 @@ hipError_t launch_argmin(const double *ll, int64_t n, int64_t flat_begin, double
     // the second launch it saves: 1 024 agent-scope fences cost more than a 4 us launch)
     record_launch(kArgminVariantNames[1]);
     hipLaunchKernelGGL(argmin_stage1, dim3(blocks), dim3(256), 0, stream, ll, n, partial_val, partial_idx);
-    hipLaunchKernelGGL(argmin_stage2, dim3(1), dim3(256), 0, stream, partial_val, partial_idx, blocks, flat_begin, result,
-                       host_mirror, queue_count);
+    hipLaunchKernelGGL(argmin_stage2, dim3(1), dim3(queue_index ? 1024 : 256), 0, stream, ll, queue_index, partial_val, partial_idx,
+                       blocks, flat_begin, result, host_mirror, queue_count);
     return hipGetLastError();
 }
 

@@ -323,7 +323,14 @@ struct covest_grid {
     ArgminResult *result_host = nullptr; // page-locked mirror of `result` (+ the scan's records: scan_host())
     ScanRecords *scan_host() const { return reinterpret_cast<ScanRecords *>(reinterpret_cast<char *>(result_host) + 64); }
     bool scan_valid = false; // the last evaluation left the records of the selection scan (covest_grid_eval_scan)
-    bool counter_clean = false; // the hand-back queue's counter (sub_ctl) is known to be 0 where it lies
+    bool counter_clean = false; // the hand-back queue's counter (sub_ctl) is known to be 0 where it lies: cleared when an
+                                // evaluation begins, set again once its arg-min (which resets the counter) is launched
+    // The strict re-evaluation of the handed-back points, put off (abi_grid.cpp grid_complete): a plain covest_grid_eval
+    // launches the recurrence kernel and an arg-min that proves its winner on the provisional values, and the patching pass
+    // runs when somebody asks for the values.  fix_pending: the last evaluation's is still owed -- its queue in sub_index /
+    // sub_word, the queue's length in the second word of sub_ctl.  fix_eager: this handle patches inside every evaluation
+    // (covest_grid_fix_eager; a handle whose arg-min pair was taken on the device).
+    bool fix_pending = false, fix_eager = false;
     // covest_grid_reset stages what it uploads in page-locked memory OF THE HANDLE and copies asynchronously (the null
     // stream; an evaluation on another stream waits for upload_ev): the kernels queue up behind the copies and an
     // optimize_grid iteration waits for the device once, when it reads its result.  The staging memory of one reset
@@ -430,5 +437,7 @@ int resolve_kernel(const covest_model *m, int32_t kernel, const covest_grid *g);
 SubList sub_list_of(const covest_model *m, int t_max, void *index, void *word, void *ctl);
 hipError_t launch_ll(const covest_model *m, int kernel, const PointSource &src, int64_t n, double *out, const SubList &sub,
                      hipStream_t st, const char **name, const covest_grid *g = nullptr);
+hipError_t launch_ll_unfixed(const covest_model *m, int kernel, const PointSource &src, int64_t n, double *out,
+                             const SubList &sub, hipStream_t st, const char **name, const covest_grid *g);
 
 } // namespace covest

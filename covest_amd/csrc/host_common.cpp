@@ -316,6 +316,12 @@ LaunchRecordScope::LaunchRecordScope(LaunchRecord &r) : prev(tls_record)
     r.clear();
     tls_record = &r;
 }
+LaunchRecordScope::LaunchRecordScope(LaunchRecord &r, bool append) : prev(tls_record)
+{
+    if (!append)
+        r.clear();
+    tls_record = &r;
+}
 LaunchRecordScope::~LaunchRecordScope() { tls_record = prev; }
 
 void record_launch(const char *name, int64_t launches)

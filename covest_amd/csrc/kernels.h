@@ -34,8 +34,9 @@ struct LaunchRecord {
 };
 void record_launch(const char *name, int64_t launches = 1);
 void record_factored_plan(const FactoredPlan &plan, int shared_tiles, bool long_part);
-struct LaunchRecordScope { // notes go to `r` (cleared) until the scope ends
+struct LaunchRecordScope { // notes go to `r` (cleared; append: kept and added to) until the scope ends
     explicit LaunchRecordScope(LaunchRecord &r);
+    LaunchRecordScope(LaunchRecord &r, bool append);
     ~LaunchRecordScope();
     LaunchRecord *prev;
 };
@@ -84,7 +85,8 @@ hipError_t launch_ll_finish_dense(const DevModel &m, const TileView &tv, const P
 
 // The pass after every K-basic / K-factored launch (ll_fix.hip): one wave per point of the queue `list` (handback.h) adds
 // the strict evaluation of the rows named in its side word to ll[], in place.  The queue's counter must be zero
-// before the NEXT recurrence launch: launch_argmin resets it (grids), the host does for point lists.
+// before the NEXT recurrence launch: launch_argmin resets it (grids), the host does for point lists.  list.count is
+// whatever word holds the queue's length when the pass runs: the counter itself, or where the arg-min copied it to.
 // n_points: how many points the launch before evaluated (the queue cannot be longer; 0: unknown) -- sizes the launch.
 hipError_t launch_ll_fix_list(const DevModel &m, const TileView &tv, const PointSource &src, double *ll,
                               const SubList &list, hipStream_t stream, int64_t n_points = 0);
@@ -96,12 +98,23 @@ struct ArgminResult {
     double min_negll;
     int64_t index;  // local index, -1 if no value is < +inf
     double pair[2]; // {min_negll, GLOBAL flat index as a double (-1 if none)}: what the ranks exchange
+    int64_t unproven; // launch_argmin_proving: 1 where the queued points' final values could still change the winner
 };
-// queue_count: the hand-back queue's counter to reset (nullptr: none).
+// queue_count: the hand-back queue's counter to reset (nullptr: none); two words: the queue's length is copied to the
+// second before the first is cleared.
 constexpr int64_t kArgminSmall = 16384; // grids up to this size: one workgroup, one launch
 // host_mirror: page-locked host memory the winner is stored to as well (nullptr: none)
 hipError_t launch_argmin(const double *ll, int64_t n, int64_t flat_begin, double *partial_val, int64_t *partial_idx,
                          ArgminResult *result, ArgminResult *host_mirror, unsigned *queue_count, hipStream_t stream);
+
+// The same over values of which the hand-back queue's points are still PROVISIONAL (the strict pass put off:
+// abi_grid.cpp): queue_index[*queue_count] names them, and the kernel that has the winner also walks the queue and sets
+// result->unproven unless no queued point's final value can change the winner (argmin.hip winner_unproven).  The
+// queue's length is left in queue_count[1] for the pass that comes later, queue_count[0] is reset as above.
+// queue_index == nullptr: launch_argmin (unproven = 0).
+hipError_t launch_argmin_proving(const double *ll, int64_t n, int64_t flat_begin, double *partial_val, int64_t *partial_idx,
+                                 ArgminResult *result, ArgminResult *host_mirror, unsigned *queue_count,
+                                 const int64_t *queue_index, hipStream_t stream);
 
 // The same reduction and, beside it, the selection scan of covest/grid.py:65-70 started from `start`: the strict
 // running-minimum records below it, in index order, written to `scan` (page-locked host memory).  n <= kArgminSmall.

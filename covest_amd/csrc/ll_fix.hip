@@ -27,11 +27,13 @@ namespace {
 // ones whose LAST keys underflow, which are the ones with a SMALL threshold_o -- three to six lots, most of them out
 // of the rows' reach -- and every one of the four waves repeated the point's loads, its two pows and the rows' bins:
 // C3's 2 962 queued points 46.8 us with four waves a point, 35.8 us with one, profiles/r05_c3_kstat_fix_one_wave_a_point.txt.)
-// Launched after every K-basic / K-factored launch, before anything reads the values; with an empty queue it costs
-// a launch and one load.  The queued points of a wide grid come in clusters (whole (c, e) rows of it) and the work
-// of one grows with its threshold_o, which is why they are compacted into a queue and spread over the chip instead
+// Launched after every K-basic / K-factored launch, before anything reads the values -- a grid handle's plain evaluation
+// puts it off until somebody does (abi_grid.cpp grid_complete: the arg-min needs no more than the bound that a queued
+// point's value only falls here); with an empty queue it costs a launch and one load.  The queued points of a wide
+// grid come in clusters (whole (c, e) rows of it) and the work of one grows with its threshold_o, which is why they are compacted into a queue and spread over the chip instead
 // of being patched by whichever thread meets them.  The queue's counter is reset by whoever runs next on the
-// stream: the arg-min pass (grids) or the host (point lists).
+// stream: the arg-min pass (grids; it leaves the queue's length in the word behind the counter, which is the `count` of
+// a pass that was put off) or the host (point lists).
 // (Measured and not kept, round 5: the kernel held to 96 registers for five waves a SIMD -- it takes 155, three waves --
 // spills 27 of them and is slower, 42.9 against 35.8 us on C3's 2 962 queued points (threshold_o 11 .. 87, 27 rows
 // each); to 128 for four waves, 36.4.  The launch is one trip of every wave: by the counters a point is 2 750 vector

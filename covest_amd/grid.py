@@ -20,6 +20,7 @@ strict <, first index wins ties, NaN never wins.
 import ctypes
 import itertools
 import math
+import os
 import random
 
 import numpy as np
@@ -195,6 +196,8 @@ class DenseGrid:
         _capi.check(L.covest_grid_create(model.handle, len(self.axes), ptrs.ctypes.data, lens.ctypes.data, self.flat_range[0],
                                          self.flat_range[1], ctypes.byref(h)), "covest_grid_create")
         self._handle = h
+        if os.environ.get("COVEST_GRID_FIX", "") == "eager":  # the strict pass inside every evaluation, as it was: for A/B runs
+            self.fix_eager(True)
         if hasattr(model, "_register_grid"):
             model._register_grid(self)
 
@@ -301,6 +304,24 @@ class DenseGrid:
         out = np.empty(len(self), dtype=np.float64)
         _capi.check(_capi.lib().covest_grid_ll_host(self._handle, out.ctypes.data_as(_DP)),
                     "covest_grid_ll_host")
+        return out
+
+    def complete(self):
+        """Launch what the last evaluate() still owes (covest_grid_complete): a plain evaluate() puts the strict
+        re-evaluation of the handed-back points off until something reads the values -- loglikelihoods(), axis_minima(),
+        launch_record(), ll_device_ptr and argmin_pair_tensor() do this themselves, argmin() where it has to."""
+        _capi.check(_capi.lib().covest_grid_complete(self._handle), "covest_grid_complete")
+
+    def fix_eager(self, eager=True):
+        """The strict re-evaluation inside every evaluate() of this handle (covest_grid_fix_eager); the environment's
+        COVEST_GRID_FIX=eager asks that of every DenseGrid."""
+        _capi.check(_capi.lib().covest_grid_fix_eager(self._handle, 1 if eager else 0), "covest_grid_fix_eager")
+
+    def provisional_loglikelihoods(self):
+        """A diagnostic for the tests: the values while the strict re-evaluation is owed (an error if it is not)."""
+        out = np.empty(len(self), dtype=np.float64)
+        _capi.check(_capi.lib().covest_grid_ll_provisional_host(self._handle, out.ctypes.data_as(_DP)),
+                    "covest_grid_ll_provisional_host")
         return out
 
     @property

@@ -211,6 +211,22 @@ int64_t covest_grid_size(const covest_grid *g); /* flat_end - flat_begin */
  * Replaces the Pool.map + scan of covest/grid.py:63-70. */
 int covest_grid_eval(covest_grid *g, int32_t kernel, void *stream);
 
+/* THE STRICT RE-EVALUATION IS PUT OFF.  The recurrence kernels hand a few points back for a strict, term-by-term pass that
+ * corrects their values (at most downwards: it adds non-positive terms).  A plain covest_grid_eval launches the
+ * likelihood kernel and an arg-min that PROVES its winner against the handed-back points' provisional values, and
+ * leaves the pass out; whatever exposes the values or describes the launches -- covest_grid_ll_host,
+ * covest_grid_ll_device, covest_grid_axis_min, covest_grid_launch_record, covest_grid_argmin_pair_device -- runs it first
+ * (and the arg-min again), so that they see exactly what an evaluation with the pass inside leaves, bit for bit.
+ * covest_grid_argmin runs it only where the winner could not be proven.  covest_grid_eval_scan keeps the pass inside.
+ * covest_grid_complete does it by hand: the pass and the arg-min on the evaluation's stream, asynchronously; nothing
+ * if nothing is owed.  covest_grid_fix_eager(g, 1) keeps the pass inside every evaluation of the handle from then on
+ * (0: puts it off again); covest_grid_argmin_pair_device switches a handle to that by itself.
+ * covest_grid_ll_provisional_host, a diagnostic for the tests: the values as they are while the pass is owed;
+ * COVEST_E_INVALID if none is. */
+int covest_grid_complete(covest_grid *g);
+int covest_grid_fix_eager(covest_grid *g, int32_t eager);
+int covest_grid_ll_provisional_host(covest_grid *g, double *out_ll);
+
 /* Wait for the last covest_grid_eval and return the reduction.  Selection is the
  * scan of covest/grid.py:65-70 with maximize=False starting from +inf: strict <,
  * lowest GLOBAL flat index wins ties, NaN never wins; argmin -1 if nothing is

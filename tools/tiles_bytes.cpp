@@ -51,7 +51,11 @@ void *pinned_block_take() { return calloc(1, kPinnedBlockBytes); }
 void pinned_block_give(void *) {}
 int64_t launch_record_text(const LaunchRecord &, char *, int64_t) { return 0; }
 LaunchRecordScope::LaunchRecordScope(LaunchRecord &) : prev(nullptr) {}
+LaunchRecordScope::LaunchRecordScope(LaunchRecord &, bool) : prev(nullptr) {}
 LaunchRecordScope::~LaunchRecordScope() {}
+hipError_t launch_ll_unfixed(const covest_model *, int, const PointSource &, int64_t, double *, const SubList &, hipStream_t, const char **, const covest_grid *) { return hipSuccess; }
+hipError_t launch_ll_fix_list(const DevModel &, const TileView &, const PointSource &, double *, const SubList &, hipStream_t, int64_t) { return hipSuccess; }
+hipError_t launch_argmin_proving(const double *, int64_t, int64_t, double *, int64_t *, ArgminResult *, ArgminResult *, unsigned *, const int64_t *, hipStream_t) { return hipSuccess; }
 hipError_t launch_argmin(const double *, int64_t, int64_t, double *, int64_t *, ArgminResult *, ArgminResult *, unsigned *, hipStream_t) { return hipSuccess; }
 hipError_t launch_argmin_scan(const double *, int64_t, int64_t, double, ArgminResult *, ArgminResult *, ScanRecords *, unsigned *, hipStream_t) { return hipSuccess; }
 bool axis_min_plan(const int64_t *, int, uint32_t, int64_t, int64_t, AxisMinPlan *) { return false; }
