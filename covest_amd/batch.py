@@ -72,14 +72,17 @@ class HistogramBatch:
         n_keys = len(model.hist)
         h = _counts_array(counts, n_keys)
         t = _tails_array(tails, h.shape[0])
-        self.model = model
-        self._n = int(h.shape[0])
-        self._n_keys = n_keys
-        self._handle = None
+        self._fields(model, h.shape[0], n_keys)
         handle = ctypes.c_void_p()
         _capi.check(_capi.lib().covest_batch_create(model.handle, self._n, h.ctypes.data, t.ctypes.data,
                                                     ctypes.byref(handle)), "covest_batch_create")
         self._adopt(handle)
+
+    def _fields(self, model, n_hist, n_keys):
+        self.model = model
+        self._n = int(n_hist)
+        self._n_keys = n_keys
+        self._handle = None
 
     def _adopt(self, handle):
         self._handle = handle
@@ -101,10 +104,7 @@ class HistogramBatch:
         if replicates > MAX_HISTOGRAMS:
             raise ValueError("more than %d histograms" % MAX_HISTOGRAMS)
         self = cls.__new__(cls)
-        self.model = model
-        self._n = int(replicates)
-        self._n_keys = n_keys
-        self._handle = None
+        self._fields(model, replicates, n_keys)
         par = np.asarray(estimate, dtype=np.float64)
         handle = ctypes.c_void_p()
         _capi.check(_capi.lib().covest_batch_draw(model.handle, par.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
@@ -124,6 +124,14 @@ class HistogramBatch:
     def _points(self, points):
         return np.ascontiguousarray(points, dtype=np.float64).reshape(-1, self.model.param_count)
 
+    def _requests(self, index, points):
+        """A pairs call's points and its histogram numbers, one per point."""
+        pts = self._points(points)
+        idx = _index_array(index, self._n)
+        if len(idx) != len(pts):
+            raise ValueError("one histogram index per point")
+        return pts, idx
+
     def counts(self):
         """(counts (B, n_keys), tails (B,)) as the device holds them."""
         h = np.empty((self._n, self._n_keys), dtype=np.float64)
@@ -141,10 +149,7 @@ class HistogramBatch:
 
     def loglikelihood_pairs(self, index, points):
         """(n,): the log-likelihood of histogram index[i] at points[i]."""
-        pts = self._points(points)
-        idx = _index_array(index, self._n)
-        if len(idx) != len(pts):
-            raise ValueError("one histogram index per point")
+        pts, idx = self._requests(index, points)
         out = np.empty(len(pts), dtype=np.float64)
         _capi.check(_capi.lib().covest_batch_eval_pairs(self._open(), len(pts), idx.ctypes.data, pts.ctypes.data,
                                                         out.ctypes.data), "covest_batch_eval_pairs")
@@ -166,10 +171,7 @@ class HistogramBatch:
         """(ll (n,), grad (n, P)): histogram index[i] at points[i], value and analytic gradient from one table as in
         loglikelihood_gradient_cross (the value is the derivative kernel's: loglikelihood_pairs' to 1e-11 relative, not
         to the bit).  A request's result does not depend on what else is in the call."""
-        pts = self._points(points)
-        idx = _index_array(index, self._n)
-        if len(idx) != len(pts):
-            raise ValueError("one histogram index per point")
+        pts, idx = self._requests(index, points)
         out = np.empty((len(pts), self.model.param_count + 1), dtype=np.float64)
         _capi.check(_capi.lib().covest_batch_eval_pairs_grad(self._open(), len(pts), idx.ctypes.data, pts.ctypes.data,
                                                              out.ctypes.data), "covest_batch_eval_pairs_grad")

@@ -335,18 +335,6 @@ static int reserve_point_queue(covest_model *m, int64_t n)
     return COVEST_OK;
 }
 
-// threshold_o of every point of a list (repeats model; the basic model has none: empty)
-static std::vector<int32_t> point_thresholds(const covest_model *m, int64_t n, const double *params)
-{
-    std::vector<int32_t> t;
-    if (m->n_par == 5) {
-        t.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i)
-            t[(size_t)i] = threshold_for_point(m, params + i * 5);
-    }
-    return t;
-}
-
 // A point list where the kernels read it and where they leave its result: stage_points.
 struct StagedPoints {
     PointSource src{};
@@ -751,12 +739,7 @@ int covest_probabilities(covest_model *m, const double *params, int32_t clamp, d
         HIP_TRY(hipMemcpy(m->ws_t.ptr, &t, sizeof(int32_t), hipMemcpyHostToDevice));
         src.t_list = m->ws_t.as<int32_t>();
     }
-    if (!m->all_bins_ready) { // the view over EVERY key is only needed here: uploaded on first use
-        rc = upload_bins(m->bins_all, m->all_bins, m->host_all_key, m->host_all_lgam, m->host_all_cnt);
-        if (rc != COVEST_OK)
-            return rc;
-        m->all_bins_ready = true;
-    }
+    COVEST_TRY(ensure_all_bins(m));
     DevModel full = m->dm;
     full.bins = m->all_bins;
     if (!clamp)

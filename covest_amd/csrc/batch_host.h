@@ -46,6 +46,12 @@ inline const char *batch_check_points(int64_t n, int64_t n_hist, const void *par
     return nullptr;
 }
 
+// ... with two result arrays (the arg-min's value and index; the score table's rows and tail coefficients)
+inline const char *batch_check_points(int64_t n, int64_t n_hist, const void *params, const void *out_a, const void *out_b)
+{
+    return batch_check_points(n, n_hist, params, out_a && out_b ? out_a : nullptr);
+}
+
 // ... and with the histogram numbers of a pairs call: each in 0 .. n_hist - 1
 inline const char *batch_check_index(int64_t n, const int64_t *index, int64_t n_hist)
 {
@@ -57,19 +63,20 @@ inline const char *batch_check_index(int64_t n, const int64_t *index, int64_t n_
     return nullptr;
 }
 
-// Points of one table chunk: as many rows of n_keys doubles as the budget holds, one at least.
-inline int64_t batch_points_per_chunk(int64_t n_keys, int64_t budget_bytes)
+// A pairs call: its list (the buffers whenever n > 0: a request names its histogram), then its histogram numbers
+inline const char *batch_check_pairs(int64_t n, int64_t n_hist, const int64_t *index, const void *params, const void *out)
 {
-    const int64_t row = (n_keys > 0 ? n_keys : 1) * (int64_t)sizeof(double);
-    const int64_t per = budget_bytes / row;
-    return per > 0 ? per : 1;
+    if (const char *bad = batch_check_points(n, 1, params, out))
+        return bad;
+    return batch_check_index(n, index, n_hist);
 }
 
-// ... of a table with `rows_per_point` rows a point (the gradient's table: the value row and one score row a parameter)
-inline int64_t batch_grad_points_per_chunk(int64_t n_keys, int64_t rows_per_point, int64_t budget_bytes)
+// Points of one table chunk: as many as the budget holds at `rows_per_point` rows of n_keys doubles each (1: the value
+// table; P + 1: the gradient's, the value row and one score row a parameter), one at least.
+inline int64_t batch_points_per_chunk(int64_t n_keys, int64_t rows_per_point, int64_t budget_bytes)
 {
-    const int64_t rows = rows_per_point > 0 ? rows_per_point : 1;
-    const int64_t per = batch_points_per_chunk(n_keys, budget_bytes) / rows;
+    const int64_t point = (n_keys > 0 ? n_keys : 1) * (rows_per_point > 0 ? rows_per_point : 1) * (int64_t)sizeof(double);
+    const int64_t per = budget_bytes / point;
     return per > 0 ? per : 1;
 }
 

@@ -46,4 +46,13 @@ struct PointSource {
     const int32_t *t_table;   // threshold_o over the (q1, q2, q) sub-grid
 };
 
+// a point list (list mode, P parameters a point) from its point `first` on
+inline PointSource points_from(const PointSource &src, int64_t first, int P)
+{
+    PointSource part = src;
+    part.params = src.params + first * P;
+    part.t_list = src.t_list ? src.t_list + first : nullptr;
+    return part;
+}
+
 } // namespace covest

@@ -388,6 +388,8 @@ void threshold_table(const covest_model *m, const double *a1, int64_t n1, const 
                      int64_t n3, int32_t *out); // threshold_o over the product of three (q1, q2, q) axes, last fastest
 double clamp_one(const DevModel &dm, int d, double v);
 int threshold_for_point(const covest_model *m, const double *par);
+std::vector<int32_t> point_thresholds(const covest_model *m, int64_t n, const double *params); // of a list; basic: empty
+int ensure_all_bins(covest_model *m); // m->all_bins on the device, uploaded on first use
 void lgamma_ensure(int64_t j_max);
 double lgamma_at(int64_t j); // (after lgamma_ensure(j) or larger)
 double lgamma_of_factorial(int64_t j);

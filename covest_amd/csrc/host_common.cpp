@@ -254,6 +254,30 @@ int threshold_for_point(const covest_model *m, const double *par)
     return threshold_o_host(clamp_one(m->dm, 2, par[2]), clamp_one(m->dm, 3, par[3]),
                             clamp_one(m->dm, 4, par[4]), m->threshold, m->has_threshold, m->hist_max);
 }
+
+// threshold_o of every point of a list (repeats model; the basic model has none: empty)
+std::vector<int32_t> point_thresholds(const covest_model *m, int64_t n, const double *params)
+{
+    std::vector<int32_t> t;
+    if (m->n_par == 5) {
+        t.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i)
+            t[(size_t)i] = threshold_for_point(m, params + i * 5);
+    }
+    return t;
+}
+
+// The view over EVERY key is only needed by covest_probabilities and by a batch's table: uploaded on first use.  With the
+// model locked and its device current.
+int ensure_all_bins(covest_model *m)
+{
+    if (m->all_bins_ready)
+        return COVEST_OK;
+    COVEST_TRY(upload_bins(m->bins_all, m->all_bins, m->host_all_key, m->host_all_lgam, m->host_all_cnt));
+    m->all_bins_ready = true;
+    return COVEST_OK;
+}
+
 // device < 0 = the calling thread's current device (include/covest_amd.h); checked against the device count.
 int resolve_device(int device, const char *who, int *out)
 {

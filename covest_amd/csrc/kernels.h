@@ -368,20 +368,18 @@ hipError_t launch_batch_cross(const double *H, const double *tails, int64_t n_hi
 // (h_bj != 0), out[b * ld + i] = -inf unless it is NaN already.
 hipError_t launch_batch_fix_dead(const double *H, int64_t n_hist, const double *table, int64_t n_keys,
                                  const int32_t *dead_list, int64_t n_dead, double *out, int64_t ld, hipStream_t stream);
-// out[i] = sum_j H[index[i]][j] table[i][j] + tails[index[i]] tl[i], the dead-key rule applied inline; a wave a request.
-hipError_t launch_batch_pairs(const double *H, const double *tails, const int64_t *index, const double *table,
-                              const double *tl, int64_t n, int64_t n_keys, double *out, hipStream_t stream);
+// out[i * R + q] = sum_j H[index[i]][j] rows[i * R + q][j] + tails[index[i]] tc[i * R + q], one wave a request: the R dot
+// products in one sweep over the keys; the dead-key rule inline (value -inf), and where the value is not finite the
+// R - 1 derivative entries NaN.  R is 1 (the value form: rows and tc are launch_batch_table's table and tl) or, for the
+// gradient's table below, 3 or 6.
+hipError_t launch_batch_pairs(const double *H, const double *tails, const int64_t *index, const double *rows,
+                              const double *tc, int64_t n, int64_t n_keys, int rows_per_point, double *out,
+                              hipStream_t stream);
 // ---- the gradient of a batch: `rows` is launch_ll_deriv_table's, R = P + 1 rows a point ----
 // tc[i * R + q] from the finishing pass's out_ll[i] (q = 0) and out_grad[i][q - 1]: the array launch_batch_cross takes
 // for tl when the table has R n rows.
 hipError_t launch_batch_tail_pack(const double *fin_ll, const double *fin_grad, int64_t n, int rows_per_point, double *tc,
                                   hipStream_t stream);
-// out[i * R + q] = sum_j H[index[i]][j] rows[i * R + q][j] + tails[index[i]] tc[i * R + q], one wave a request: the R dot
-// products in one sweep over the keys; the dead-key rule inline (value -inf), and where the value is not finite the
-// R - 1 derivative entries NaN.  R is 3 or 6.
-hipError_t launch_batch_pairs_grad(const double *H, const double *tails, const int64_t *index, const double *rows,
-                                   const double *tc, int64_t n, int64_t n_keys, int rows_per_point, double *out,
-                                   hipStream_t stream);
 // out is n_hist x (n * R) with row length ld (launch_batch_cross over R n rows, then launch_batch_fix_dead with the dead
 // points' VALUE rows listed): where out[b * ld + i * R] is not finite, the R - 1 entries behind it become NaN.
 hipError_t launch_batch_grad_specials(int64_t n_hist, int64_t n, int rows_per_point, double *out, int64_t ld,

@@ -24,10 +24,10 @@
 //                         contraction adds nothing for it) and the point is listed; one wave per (histogram, listed
 //                         point) sets -inf where the histogram counts such a key.  A key with h_bj = 0 contributes
 //                         nothing (covest/models.py:105-107, `if h`).
-//   batch_pairs_kernel    histogram index[i] at point i, one wave a request, the dead-key rule inline.
-//   batch_pairs_grad_kernel, batch_tail_pack_kernel, batch_grad_specials_kernel  the gradient of a batch (DESIGN.md
-//                         section 6u): the same contraction over the derivative kernel's score table, R = P + 1 rows a
-//                         point; the pairs form takes a request's R dot products in one sweep.
+//   batch_pairs_kernel<R> histogram index[i] at point i, one wave a request, the dead-key rule inline; R rows a point,
+//                         a request's R dot products in one sweep (R = 1: the value form).
+//   batch_tail_pack_kernel, batch_grad_specials_kernel  the gradient of a batch: the same
+//                         contraction over the derivative kernel's score table, R = P + 1 rows a point.
 //   batch_argmin_kernel   per histogram the first index of the strictly smallest -LL (covest/grid.py:65-70), carried
 //                         across table chunks on the device.
 //   batch_from_draw_kernel  int64 rows of draw_hist.hip to double counts and tails.
@@ -166,38 +166,13 @@ __global__ __launch_bounds__(256) void batch_fix_dead_kernel(const double *__res
     }
 }
 
-__global__ __launch_bounds__(256) void batch_pairs_kernel(const double *__restrict__ H, const double *__restrict__ tails,
-                                                          const int64_t *__restrict__ index, const double *__restrict__ L,
-                                                          const double *__restrict__ tl, const int64_t n, const int64_t nk,
-                                                          double *__restrict__ out, const int64_t w0)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t i = w0 + (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x / kWave);
-    if (i >= n)
-        return; // wave-uniform
-    const int64_t b = index[i];
-    const double *hrow = H + b * nk, *lrow = L + i * nk;
-    double acc = 0.0;
-    bool hit = false;
-    for (int64_t j = lane; j < nk; j += kWave) {
-        const double h = hrow[j], l = lrow[j];
-        acc += h * l;
-        hit = hit || (h != 0.0 && is_dead_entry(l));
-    }
-    double v = wave_sum(acc) + tails[b] * tl[i];
-    if (__any(hit) && v == v)
-        v = -INFINITY;
-    if (lane == 0)
-        out[i] = v;
-}
-
-// a wave a request: histogram index[i] against the R rows of point i (value, then the scores), one sweep over the keys
+// a wave a request: histogram index[i] against the R rows of point i (value, then the scores), one sweep over the keys.
+// R = 1 is the value form: the one row a point of launch_batch_table's table, and tl.
 template <int R>
-__global__ __launch_bounds__(256) void batch_pairs_grad_kernel(const double *__restrict__ H, const double *__restrict__ tails,
-                                                               const int64_t *__restrict__ index,
-                                                               const double *__restrict__ rows, const double *__restrict__ tc,
-                                                               const int64_t n, const int64_t nk, double *__restrict__ out,
-                                                               const int64_t w0)
+__global__ __launch_bounds__(256) void batch_pairs_kernel(const double *__restrict__ H, const double *__restrict__ tails,
+                                                          const int64_t *__restrict__ index, const double *__restrict__ rows,
+                                                          const double *__restrict__ tc, const int64_t n, const int64_t nk,
+                                                          double *__restrict__ out, const int64_t w0)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t i = w0 + (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x / kWave);
@@ -311,29 +286,38 @@ __global__ __launch_bounds__(256) void batch_from_draw_kernel(const int64_t *__r
 
 } // namespace
 
-hipError_t launch_batch_table(const DevModel &m, const PointSource &src, int64_t n, double *table, double *tl, int32_t *dead,
-                              bool keep_p, hipStream_t stream)
+namespace {
+
+// `n` items, one wave each, in launches of at most kWavesPerBlock * kMaxBlocks waves: launch(grid, block, first item)
+template <class Launch>
+hipError_t launch_waves(int64_t n, Launch launch)
 {
     if (n <= 0)
         return hipSuccess;
-    const int P = m.kind == 0 ? 2 : 5;
     const int64_t per_launch = kWavesPerBlock * kMaxBlocks;
     for (int64_t k = 0; k < batch_launch_parts(n, per_launch); ++k) {
         int64_t first, cnt;
         batch_launch_part(n, per_launch, k, &first, &cnt);
-        const dim3 grid((unsigned)((cnt + kWavesPerBlock - 1) / kWavesPerBlock)), block(kWavesPerBlock * kWave);
-        PointSource part = src;
-        part.params = src.params + first * P;
-        part.t_list = src.t_list ? src.t_list + first : nullptr;
-        double *rows = table + first * m.bins.n;
-        if (m.kind == 0)
-            hipLaunchKernelGGL((batch_table_kernel<2>), grid, block, 0, stream, m, part, cnt, rows, tl + first, dead + first,
-                               keep_p ? 1 : 0);
-        else
-            hipLaunchKernelGGL((batch_table_kernel<5>), grid, block, 0, stream, m, part, cnt, rows, tl + first, dead + first,
-                               keep_p ? 1 : 0);
+        launch(dim3((unsigned)((cnt + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kWavesPerBlock * kWave), first);
     }
     return hipGetLastError();
+}
+
+// the grid of an elementwise kernel over `total` items: workgroups of 256 threads, each in a grid-stride loop
+dim3 elementwise_grid(int64_t total) { return dim3((unsigned)std::min<int64_t>((total + 255) / 256, (int64_t)1 << 16)); }
+
+} // namespace
+
+hipError_t launch_batch_table(const DevModel &m, const PointSource &src, int64_t n, double *table, double *tl, int32_t *dead,
+                              bool keep_p, hipStream_t stream)
+{
+    const int P = m.kind == 0 ? 2 : 5;
+    return launch_waves(n, [&](dim3 grid, dim3 block, int64_t first) {
+        // a part is its own list; n - first bounds it (a part before the last has a wave for each of its points)
+        const auto kernel = m.kind == 0 ? batch_table_kernel<2> : batch_table_kernel<5>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, m, points_from(src, first, P), n - first, table + first * m.bins.n,
+                           tl + first, dead + first, keep_p ? 1 : 0);
+    });
 }
 
 hipError_t launch_batch_cross(const double *H, const double *tails, int64_t n_hist, const double *table, const double *tl,
@@ -361,32 +345,25 @@ hipError_t launch_batch_cross(const double *H, const double *tails, int64_t n_hi
 hipError_t launch_batch_fix_dead(const double *H, int64_t n_hist, const double *table, int64_t n_keys,
                                  const int32_t *dead_list, int64_t n_dead, double *out, int64_t ld, hipStream_t stream)
 {
-    const int64_t waves = n_hist * n_dead;
-    if (waves <= 0)
-        return hipSuccess;
-    const int64_t per_launch = kWavesPerBlock * kMaxBlocks;
-    for (int64_t k = 0; k < batch_launch_parts(waves, per_launch); ++k) {
-        int64_t w0, cnt;
-        batch_launch_part(waves, per_launch, k, &w0, &cnt);
-        hipLaunchKernelGGL(batch_fix_dead_kernel, dim3((unsigned)((cnt + kWavesPerBlock - 1) / kWavesPerBlock)),
-                           dim3(kWavesPerBlock * kWave), 0, stream, H, n_hist, table, n_keys, dead_list, n_dead, out, ld, w0);
-    }
-    return hipGetLastError();
+    return launch_waves(n_hist * n_dead, [&](dim3 grid, dim3 block, int64_t w0) {
+        hipLaunchKernelGGL(batch_fix_dead_kernel, grid, block, 0, stream, H, n_hist, table, n_keys, dead_list, n_dead, out, ld, w0);
+    });
 }
 
-hipError_t launch_batch_pairs(const double *H, const double *tails, const int64_t *index, const double *table,
-                              const double *tl, int64_t n, int64_t n_keys, double *out, hipStream_t stream)
+hipError_t launch_batch_pairs(const double *H, const double *tails, const int64_t *index, const double *rows,
+                              const double *tc, int64_t n, int64_t n_keys, int rows_per_point, double *out, hipStream_t stream)
 {
     if (n <= 0)
         return hipSuccess;
-    const int64_t per_launch = kWavesPerBlock * kMaxBlocks;
-    for (int64_t k = 0; k < batch_launch_parts(n, per_launch); ++k) {
-        int64_t w0, cnt;
-        batch_launch_part(n, per_launch, k, &w0, &cnt);
-        hipLaunchKernelGGL(batch_pairs_kernel, dim3((unsigned)((cnt + kWavesPerBlock - 1) / kWavesPerBlock)),
-                           dim3(kWavesPerBlock * kWave), 0, stream, H, tails, index, table, tl, n, n_keys, out, w0);
-    }
-    return hipGetLastError();
+    const auto kernel = rows_per_point == 1   ? batch_pairs_kernel<1>
+                        : rows_per_point == 3 ? batch_pairs_kernel<3>
+                        : rows_per_point == 6 ? batch_pairs_kernel<6>
+                                              : nullptr;
+    if (!kernel)
+        return hipErrorInvalidValue;
+    return launch_waves(n, [&](dim3 grid, dim3 block, int64_t w0) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, H, tails, index, rows, tc, n, n_keys, out, w0);
+    });
 }
 
 hipError_t launch_batch_tail_pack(const double *fin_ll, const double *fin_grad, int64_t n, int rows_per_point, double *tc,
@@ -395,30 +372,8 @@ hipError_t launch_batch_tail_pack(const double *fin_ll, const double *fin_grad, 
     const int64_t total = n * rows_per_point;
     if (total <= 0)
         return hipSuccess;
-    const int64_t blocks = std::min<int64_t>((total + 255) / 256, (int64_t)1 << 16);
-    hipLaunchKernelGGL(batch_tail_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, fin_ll, fin_grad, n,
+    hipLaunchKernelGGL(batch_tail_pack_kernel, elementwise_grid(total), dim3(256), 0, stream, fin_ll, fin_grad, n,
                        rows_per_point, tc);
-    return hipGetLastError();
-}
-
-hipError_t launch_batch_pairs_grad(const double *H, const double *tails, const int64_t *index, const double *rows,
-                                   const double *tc, int64_t n, int64_t n_keys, int rows_per_point, double *out,
-                                   hipStream_t stream)
-{
-    if (n <= 0)
-        return hipSuccess;
-    if (rows_per_point != 3 && rows_per_point != 6)
-        return hipErrorInvalidValue;
-    const int64_t per_launch = kWavesPerBlock * kMaxBlocks;
-    for (int64_t k = 0; k < batch_launch_parts(n, per_launch); ++k) {
-        int64_t w0, cnt;
-        batch_launch_part(n, per_launch, k, &w0, &cnt);
-        const dim3 grid((unsigned)((cnt + kWavesPerBlock - 1) / kWavesPerBlock)), block(kWavesPerBlock * kWave);
-        if (rows_per_point == 3)
-            hipLaunchKernelGGL((batch_pairs_grad_kernel<3>), grid, block, 0, stream, H, tails, index, rows, tc, n, n_keys, out, w0);
-        else
-            hipLaunchKernelGGL((batch_pairs_grad_kernel<6>), grid, block, 0, stream, H, tails, index, rows, tc, n, n_keys, out, w0);
-    }
     return hipGetLastError();
 }
 
@@ -428,9 +383,8 @@ hipError_t launch_batch_grad_specials(int64_t n_hist, int64_t n, int rows_per_po
     const int64_t total = n_hist * n;
     if (total <= 0)
         return hipSuccess;
-    const int64_t blocks = std::min<int64_t>((total + 255) / 256, (int64_t)1 << 16);
-    hipLaunchKernelGGL(batch_grad_specials_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, n_hist, n, rows_per_point, out,
-                       ld);
+    hipLaunchKernelGGL(batch_grad_specials_kernel, elementwise_grid(total), dim3(256), 0, stream, n_hist, n, rows_per_point,
+                       out, ld);
     return hipGetLastError();
 }
 
@@ -446,16 +400,11 @@ hipError_t launch_batch_argmin_init(int64_t n_hist, double *run_val, int64_t *ru
 hipError_t launch_batch_argmin(const double *ll, int64_t ld, int64_t n_hist, int64_t n, int64_t first, double *run_val,
                                int64_t *run_idx, hipStream_t stream)
 {
-    if (n_hist <= 0 || n <= 0)
+    if (n <= 0)
         return hipSuccess;
-    const int64_t per_launch = kWavesPerBlock * kMaxBlocks;
-    for (int64_t k = 0; k < batch_launch_parts(n_hist, per_launch); ++k) {
-        int64_t w0, cnt;
-        batch_launch_part(n_hist, per_launch, k, &w0, &cnt);
-        hipLaunchKernelGGL(batch_argmin_kernel, dim3((unsigned)((cnt + kWavesPerBlock - 1) / kWavesPerBlock)),
-                           dim3(kWavesPerBlock * kWave), 0, stream, ll, ld, n_hist, n, first, run_val, run_idx, w0);
-    }
-    return hipGetLastError();
+    return launch_waves(n_hist, [&](dim3 grid, dim3 block, int64_t w0) {
+        hipLaunchKernelGGL(batch_argmin_kernel, grid, block, 0, stream, ll, ld, n_hist, n, first, run_val, run_idx, w0);
+    });
 }
 
 hipError_t launch_batch_from_draw(const int64_t *draw, int64_t n_hist, int64_t n_keys, bool has_tail, double *H,
@@ -464,8 +413,7 @@ hipError_t launch_batch_from_draw(const int64_t *draw, int64_t n_hist, int64_t n
     const int64_t total = n_hist * (n_keys + (has_tail ? 1 : 0));
     if (total <= 0)
         return hipSuccess;
-    const int64_t blocks = std::min<int64_t>((total + 255) / 256, (int64_t)1 << 16);
-    hipLaunchKernelGGL(batch_from_draw_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, draw, n_hist, n_keys,
+    hipLaunchKernelGGL(batch_from_draw_kernel, elementwise_grid(total), dim3(256), 0, stream, draw, n_hist, n_keys,
                        has_tail ? 1 : 0, H, tails);
     return hipGetLastError();
 }

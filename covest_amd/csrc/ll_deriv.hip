@@ -590,10 +590,7 @@ hipError_t deriv_launches(const DevModel &m, int order, const PointSource &src, 
                                : (order == 1 ? launch_part<5, 1> : order == 2 ? launch_part<5, 2> : launch_part<5, kDerivOpg>);
     for (int64_t first = 0; first < n; first += kDerivPointsPerLaunch) {
         const int64_t cnt = n - first < kDerivPointsPerLaunch ? n - first : kDerivPointsPerLaunch;
-        PointSource part = src;
-        part.params = src.params + first * P;
-        part.t_list = src.t_list ? src.t_list + first : nullptr;
-        launch(m, part, n_seg, cnt, partial, out_ll + first, out_grad + first * P,
+        launch(m, points_from(src, first, P), n_seg, cnt, partial, out_ll + first, out_grad + first * P,
                order != 1 ? out_hess + first * P * P : nullptr, rows ? rows + first * (P + 1) * m.bins.n : nullptr,
                rows ? dead + first : nullptr, stream);
         if (!rows) // (the table-writing walk is the batch's: not a variant of the launch record)

@@ -1,5 +1,5 @@
 // batch_grad_host_check.cpp -- the chunk arithmetic of a batch's gradient table (covest_amd/csrc/batch_host.h:
-// batch_grad_points_per_chunk, with batch_chunk_count and batch_chunk) in a program of its own, for
+// batch_points_per_chunk, with batch_chunk_count and batch_chunk) in a program of its own, for
 // tests/test_batch_grad_cpu.py to build with the host compiler under -fsanitize=address,undefined and run.  No device.
 #include <cstdio>
 #include <vector>
@@ -43,12 +43,12 @@ static void check_list(int64_t n, int64_t per, int64_t rows, int64_t n_keys, int
 int main()
 {
     const int64_t budget = kBatchHostTableBytes, cells = budget / 8;
-    CHECK(batch_grad_points_per_chunk(256, 3, budget) == 43690); // 2^28 / (3 * 256 * 8)
-    CHECK(batch_grad_points_per_chunk(256, 6, budget) == 21845);
-    CHECK(batch_grad_points_per_chunk(256, 1, budget) == batch_points_per_chunk(256, budget));
+    CHECK(batch_points_per_chunk(256, 3, budget) == 43690); // 2^28 / (3 * 256 * 8)
+    CHECK(batch_points_per_chunk(256, 6, budget) == 21845);
+    CHECK(batch_points_per_chunk(256, 1, budget) == 131072); // one row a point: the value table's chunk
     for (const int64_t rows : {(int64_t)3, (int64_t)6}) {
         for (const int64_t n_keys : {(int64_t)1, (int64_t)63, (int64_t)256, (int64_t)257, (int64_t)100000}) {
-            const int64_t per = batch_grad_points_per_chunk(n_keys, rows, budget);
+            const int64_t per = batch_points_per_chunk(n_keys, rows, budget);
             CHECK(per >= 1);
             CHECK(per * rows * n_keys <= cells);             // a chunk fits the budget ...
             CHECK((per + 1) * rows * n_keys > cells);        // ... and one point more would not
@@ -63,13 +63,13 @@ int main()
         }
         // a row larger than the budget: one point a chunk
         const int64_t huge = cells + 1;
-        CHECK(batch_grad_points_per_chunk(huge, rows, budget) == 1);
-        CHECK(batch_grad_points_per_chunk(cells / rows + 1, rows, budget) == 1);
+        CHECK(batch_points_per_chunk(huge, rows, budget) == 1);
+        CHECK(batch_points_per_chunk(cells / rows + 1, rows, budget) == 1);
         check_list(3, 1, rows, huge, cells, 3);
         // a small budget, so that the large counts are walked too
         const int64_t small = 4096 * 8;
         for (const int64_t n_keys : {(int64_t)1, (int64_t)5, (int64_t)4096, (int64_t)5000}) {
-            const int64_t per = batch_grad_points_per_chunk(n_keys, rows, small);
+            const int64_t per = batch_points_per_chunk(n_keys, rows, small);
             CHECK(per == (small / (rows * n_keys * 8) > 0 ? small / (rows * n_keys * 8) : 1));
             check_list(0, per, rows, n_keys, 4096, 0);
             check_list(per, per, rows, n_keys, 4096, 1);
@@ -77,9 +77,9 @@ int main()
         }
     }
     // degenerate arguments stay defined: at least one point, whatever is asked
-    CHECK(batch_grad_points_per_chunk(0, 3, budget) == batch_points_per_chunk(0, budget) / 3);
-    CHECK(batch_grad_points_per_chunk(256, 0, budget) == batch_points_per_chunk(256, budget));
-    CHECK(batch_grad_points_per_chunk(256, 3, 0) == 1);
+    CHECK(batch_points_per_chunk(0, 3, budget) == batch_points_per_chunk(0, 1, budget) / 3);
+    CHECK(batch_points_per_chunk(256, 0, budget) == batch_points_per_chunk(256, 1, budget));
+    CHECK(batch_points_per_chunk(256, 3, 0) == 1);
     if (failures) {
         std::printf("batch_grad_host_check: %d failures\n", failures);
         return 1;

@@ -88,14 +88,37 @@ int main()
         CHECK(batch_check_index(1, idx.data(), 0) != nullptr);
         const int64_t neg = -1;
         CHECK(batch_check_index(1, &neg, 5) != nullptr);
+        // the arg-min's two results and the score table's: both, whenever there is anything to do
+        int64_t arg[1];
+        CHECK(batch_check_points(1, 1, par, out, arg) == nullptr);
+        CHECK(batch_check_points(0, 1, nullptr, nullptr, nullptr) == nullptr);
+        CHECK(batch_check_points(5, 0, nullptr, nullptr, nullptr) == nullptr); // (an empty batch has no minimum to write)
+        CHECK(batch_check_points(-1, 1, par, out, arg) != nullptr);
+        CHECK(batch_check_points(-1, 0, par, out, arg) != nullptr);
+        CHECK(batch_check_points(1, 1, nullptr, out, arg) != nullptr);
+        CHECK(batch_check_points(1, 1, par, nullptr, arg) != nullptr);
+        CHECK(batch_check_points(1, 1, par, out, nullptr) != nullptr);
+        // a pairs call: the sign of n before anything is read, the buffers whatever the batch holds, then the index
+        double four[4];
+        const std::vector<double> pts(8, 1.0);
+        CHECK(batch_check_pairs(4, 5, idx.data(), pts.data(), four) == nullptr);
+        CHECK(batch_check_pairs(0, 5, nullptr, nullptr, nullptr) == nullptr);
+        CHECK(batch_check_pairs(0, 0, nullptr, nullptr, nullptr) == nullptr);
+        CHECK(batch_check_pairs(-1, 5, nullptr, pts.data(), four) != nullptr); // (a null index of -1 entries is not read)
+        CHECK(batch_check_pairs(4, 5, idx.data(), nullptr, four) != nullptr);
+        CHECK(batch_check_pairs(4, 5, idx.data(), pts.data(), nullptr) != nullptr);
+        CHECK(batch_check_pairs(4, 0, idx.data(), nullptr, four) != nullptr); // an empty batch: still a null buffer
+        CHECK(batch_check_pairs(4, 5, nullptr, pts.data(), four) != nullptr);
+        CHECK(batch_check_pairs(4, 4, idx.data(), pts.data(), four) != nullptr);
+        CHECK(batch_check_pairs(1, 0, idx.data(), pts.data(), four) != nullptr);
     }
     // ---- the chunking of a point list against the table budget: 0, 1, one chunk exactly, one chunk plus one
     {
-        CHECK(batch_points_per_chunk(256, 256 * 8 * 10) == 10);
-        CHECK(batch_points_per_chunk(256, 256 * 8 * 10 + 7) == 10);
-        CHECK(batch_points_per_chunk(256, 100) == 1); // a row beyond the budget: one point at a time
-        CHECK(batch_points_per_chunk(1, kBatchHostTableBytes) == kBatchHostTableBytes / 8);
-        CHECK(batch_points_per_chunk(256, kBatchHostTableBytes) == 131072);
+        CHECK(batch_points_per_chunk(256, 1, 256 * 8 * 10) == 10);
+        CHECK(batch_points_per_chunk(256, 1, 256 * 8 * 10 + 7) == 10);
+        CHECK(batch_points_per_chunk(256, 1, 100) == 1); // a row beyond the budget: one point at a time
+        CHECK(batch_points_per_chunk(1, 1, kBatchHostTableBytes) == kBatchHostTableBytes / 8);
+        CHECK(batch_points_per_chunk(256, 1, kBatchHostTableBytes) == 131072);
         for (const int64_t per : {(int64_t)1, (int64_t)10, (int64_t)131072}) {
             CHECK(batch_chunk_count(0, per) == 0);
             CHECK(batch_chunk_count(1, per) == 1);

@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 NAMES = list(S.SHAPES)
 TOL_KERNELS = 1e-11  # between the derivative kernel's value and K-direct's (tests/test_gpu_deriv_shapes.py)
-CHUNK_POINTS_256 = (1 << 28) // (3 * 256 * 8)  # batch_host.h batch_grad_points_per_chunk: basic model, 256 keys
+CHUNK_POINTS_256 = (1 << 28) // (3 * 256 * 8)  # batch_host.h batch_points_per_chunk at 3 rows a point: basic model, 256 keys
 
 
 @functools.lru_cache(maxsize=None)
