@@ -10,7 +10,7 @@ from .hist_steps import (load_histogram, save_histogram, process_histogram, samp
                          compute_coverage_apx)
 from .report import print_output  # noqa: F401,E402
 from .profile import profile_negll, likelihood_interval, coverage_interval  # noqa: F401,E402
-from .information import observed_information, sandwich_covariance, wald_intervals, genome_size_se  # noqa: F401,E402
+from .information import observed_information, observed_information_batch, sandwich_covariance, wald_intervals, genome_size_se  # noqa: F401,E402
 from . import bootstrap  # noqa: F401,E402
 from .bootstrap import parametric_bootstrap, draw_histograms, draw_thresholds, model_cells  # noqa: F401,E402
 from . import batch  # noqa: F401,E402

@@ -44,6 +44,7 @@ EXPORTS = (
     "covest_batch_create", "covest_batch_draw", "covest_batch_counts", "covest_batch_eval_cross", "covest_batch_eval_pairs",
     "covest_batch_argmin_cross", "covest_batch_info", "covest_batch_destroy",
     "covest_batch_eval_cross_grad", "covest_batch_eval_pairs_grad", "covest_batch_score_table",
+    "covest_batch_eval_cross_hess", "covest_batch_eval_pairs_hess", "covest_batch_score_table2",
 )
 
 
@@ -266,6 +267,12 @@ def lib():
     L.covest_batch_eval_pairs_grad.argtypes = [vp, i64, vp, vp, vp]
     L.covest_batch_score_table.restype = ctypes.c_int
     L.covest_batch_score_table.argtypes = [vp, i64, vp, vp, vp]
+    L.covest_batch_eval_cross_hess.restype = ctypes.c_int
+    L.covest_batch_eval_cross_hess.argtypes = [vp, i64, vp, vp]
+    L.covest_batch_eval_pairs_hess.restype = ctypes.c_int
+    L.covest_batch_eval_pairs_hess.argtypes = [vp, i64, vp, vp, vp]
+    L.covest_batch_score_table2.restype = ctypes.c_int
+    L.covest_batch_score_table2.argtypes = [vp, i64, vp, vp, vp]
     L.covest_batch_info.restype = ctypes.c_int
     L.covest_batch_info.argtypes = [vp, i64p]
     L.covest_batch_destroy.restype = None

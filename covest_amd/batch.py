@@ -9,11 +9,17 @@ include/covest_amd.h).
     ll, grad = batch.loglikelihood_gradient_cross(points) # (B, n), (B, n, P): value and analytic gradient
     ll, grad = batch.loglikelihood_gradient_pairs(index, points)   # (n,), (n, P)
     log_p, score, tail = batch.score_table(points)        # the table behind the two: (n, n_keys), (n, P, n_keys), (n, P + 1)
+    ll, grad, hess = batch.loglikelihood_hessian_cross(points)     # (B, n), (B, n, P), (B, n, P, P): with the Hessian of LL
+    ll, grad, hess = batch.loglikelihood_hessian_pairs(index, points)   # (n,), (n, P), (n, P, P)
+    log_p, score, curv, tail = batch.score_table(points, order=2)  # ... and its table: curv (n, P (P + 1) / 2, n_keys)
 
 For a fixed key set p_j(theta) does not depend on the counts, so B histograms at n points cost n evaluations of p and
 one B x n_keys x n contraction instead of B n evaluations.  The per-key score d_k p_j / p_j does not depend on them
 either, so the gradient costs n walks of the derivative kernel and a contraction against P + 1 rows a point (DESIGN.md
-section 6u).  What a batch is not: its histograms share the model's keys, k, r, comb, bounds and threshold -- only the
+section 6u).  Nor does the curvature c_kl(j) = d_k d_l p_j / p_j - (d_k p_j / p_j)(d_l p_j / p_j) of log p_j: the Hessians
+of B histograms at n points cost n walks of the derivative kernel at order 2 and a contraction against
+R2 = 1 + P + P (P + 1) / 2 rows a point (section 6x) -- the observed information of every bootstrap replicate at its own
+refit in one call (information.observed_information_batch).  What a batch is not: its histograms share the model's keys, k, r, comb, bounds and threshold -- only the
 counts and the tail differ.  There is no CPU path: without the library or a HIP device the constructor raises
 CovestHipError.
 """
@@ -62,6 +68,18 @@ def _index_array(index, n_hist):
     if idx.size and (idx.min() < 0 or idx.max() >= n_hist):
         raise ValueError("a histogram index is outside 0 .. %d" % (n_hist - 1))
     return idx
+
+
+def pair_index(P, k, l):
+    """Where the packed upper triangle (k <= l, row by row) holds entry (k, l): csrc/ll_deriv.hip pair_index."""
+    return k * P - k * (k - 1) // 2 + (l - k)
+
+
+def _unpack_hessian(packed, P):
+    """(..., P (P + 1) / 2) -> (..., P, P), mirrored on the host: bit-symmetric.  One gather: entry (k, l) and entry
+    (l, k) read the same packed number."""
+    at = np.array([[pair_index(P, min(k, l), max(k, l)) for l in range(P)] for k in range(P)])
+    return np.ascontiguousarray(packed[..., at])
 
 
 class HistogramBatch:
@@ -177,19 +195,52 @@ class HistogramBatch:
                                                              out.ctypes.data), "covest_batch_eval_pairs_grad")
         return np.ascontiguousarray(out[:, 0]), np.ascontiguousarray(out[:, 1:])
 
-    def score_table(self, points):
+    def loglikelihood_hessian_cross(self, points):
+        """(ll (B, n), grad (B, n, P), hess (B, n, P, P)): every histogram's log-likelihood, analytic gradient and
+        closed-form Hessian -- of LL, not of -LL -- at every point, at the point after fit_to_bounds (a row and a column
+        whose parameter the clamp moved are 0; where the value is not finite every other entry is NaN).  All three come
+        from ONE table, the derivative kernel's at order 2; the device returns the upper triangle
+        and the matrix is mirrored here, so it is symmetric to the bit."""
+        pts = self._points(points)
+        P = self.model.param_count
+        out = np.empty((self._n, len(pts), 1 + P + P * (P + 1) // 2), dtype=np.float64)
+        _capi.check(_capi.lib().covest_batch_eval_cross_hess(self._open(), len(pts), pts.ctypes.data, out.ctypes.data),
+                    "covest_batch_eval_cross_hess")
+        return np.ascontiguousarray(out[:, :, 0]), np.ascontiguousarray(out[:, :, 1:1 + P]), _unpack_hessian(out[:, :, 1 + P:], P)
+
+    def loglikelihood_hessian_pairs(self, index, points):
+        """(ll (n,), grad (n, P), hess (n, P, P)): histogram index[i] at points[i], as loglikelihood_hessian_cross.  A
+        request's result does not depend on what else is in the call."""
+        pts, idx = self._requests(index, points)
+        P = self.model.param_count
+        out = np.empty((len(pts), 1 + P + P * (P + 1) // 2), dtype=np.float64)
+        _capi.check(_capi.lib().covest_batch_eval_pairs_hess(self._open(), len(pts), idx.ctypes.data, pts.ctypes.data,
+                                                             out.ctypes.data), "covest_batch_eval_pairs_hess")
+        return np.ascontiguousarray(out[:, 0]), np.ascontiguousarray(out[:, 1:1 + P]), _unpack_hessian(out[:, 1 + P:], P)
+
+    def score_table(self, points, order=1):
         """(log_p (n, n_keys), score (n, P, n_keys), tail (n, P + 1)): the table the gradient methods contract with, as
         the device holds it.  log_p is +0.0 where p_ij <= 0 and nowhere else (p = 1 is -0.0; NaN stays NaN);
         score[i, k, j] = d_k p_ij / p_ij, +0.0 at such a key and throughout where the clamp moved parameter k;
         tail[i] = [log(1 - sp_i), -S_k / (1 - sp_i) ...], all 0 where sp_i is not < 1.  It does not depend on the
-        histograms."""
+        histograms.
+
+        order=2: (log_p, score, curv (n, P (P + 1) / 2, n_keys), tail (n, R2)), the Hessian methods' table --
+        curv[i, pair_index(P, k, l), j] = d_k d_l p_ij / p_ij - score_k score_l for k <= l, +0.0 at a dead key and
+        throughout where the clamp moved k or l; tail[i] continues with -(S_kl / (1 - sp_i) + S_k S_l / (1 - sp_i)^2)."""
+        if order not in (1, 2):
+            raise ValueError("score_table: order must be 1 or 2")
         pts = self._points(points)
-        R = self.model.param_count + 1
+        P = self.model.param_count
+        R = P + 1 if order == 1 else 1 + P + P * (P + 1) // 2
         rows = np.empty((len(pts), R, self._n_keys), dtype=np.float64)
         tail = np.empty((len(pts), R), dtype=np.float64)
-        _capi.check(_capi.lib().covest_batch_score_table(self._open(), len(pts), pts.ctypes.data, rows.ctypes.data,
-                                                         tail.ctypes.data), "covest_batch_score_table")
-        return np.ascontiguousarray(rows[:, 0, :]), np.ascontiguousarray(rows[:, 1:, :]), tail
+        name = "covest_batch_score_table" if order == 1 else "covest_batch_score_table2"
+        _capi.check(getattr(_capi.lib(), name)(self._open(), len(pts), pts.ctypes.data, rows.ctypes.data, tail.ctypes.data), name)
+        if order == 1:
+            return np.ascontiguousarray(rows[:, 0, :]), np.ascontiguousarray(rows[:, 1:, :]), tail
+        return (np.ascontiguousarray(rows[:, 0, :]), np.ascontiguousarray(rows[:, 1:1 + P, :]),
+                np.ascontiguousarray(rows[:, 1 + P:, :]), tail)
 
     def argmin_cross(self, points):
         """(min_negll (B,), arg (B,)): per histogram the smallest -LL over the points and the first index that attains

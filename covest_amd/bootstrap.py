@@ -13,6 +13,13 @@ What it is not: a replicate is n independent draws from the model's cell probabi
 assumption the Wald errors make.  It measures bias and non-normality of the estimator UNDER THE MODEL, not the
 dependence between overlapping k-mers; its standard errors are as small as the model's own.
 
+studentized=True adds the bootstrap-t interval: every replicate's observed information at its own refit comes from ONE
+batch call (information.observed_information_batch), t_b = (theta_b - theta^) / se_b is formed per
+parameter, and the interval is [theta^ - q_hi se, theta^ - q_lo se] with q the quantiles of t and se the original's own
+standard error.  It is second-order accurate where the percentile interval is first-order: it corrects the estimator's
+skew and bias UNDER THE MODEL.  The caveat above holds for it unchanged -- it does not correct the dependence between
+overlapping k-mers, and it is as narrow as the model's own errors.
+
 The generator is a device kernel (draw_hist.hip; the definition of a draw is in include/covest_amd.h): every count is
 a stated function of (weights, seed, replicate, draw index), so a run is reproducible, a run of replicates equals the
 same rows of a larger run, and n draws are the first n of any longer row.  There is no CPU path: without the library
@@ -214,8 +221,44 @@ def summarize(estimates, success, estimate, names, fix=None, level=0.95):
     return out
 
 
+def t_intervals(estimates, success, replicate_se, estimate, standard_errors, names, level=0.95):
+    """The bootstrap-t arithmetic on arrays: (intervals, used).  Per parameter d the replicates that succeeded and have a
+    standard error (finite, > 0) give t_b = (estimates[b, d] - estimate[d]) / replicate_se[b, d]; used[name] counts them;
+    intervals[name] = [estimate[d] - q_hi se, estimate[d] - q_lo se] with q_lo, q_hi the (1 -+ level) / 2 quantiles of t
+    (numpy's linear interpolation) and se = standard_errors[name], the original's -- None where that is None or fewer
+    than two replicates qualify."""
+    if not (0.0 < level < 1.0):
+        raise ValueError("level must be in (0, 1)")
+    est = np.asarray(estimates, dtype=np.float64).reshape(-1, len(names))
+    rse = np.asarray(replicate_se, dtype=np.float64).reshape(-1, len(names))
+    ok = np.asarray(success, dtype=bool).reshape(-1)
+    intervals, used = {}, {}
+    for d, name in enumerate(names):
+        with np.errstate(invalid="ignore"):
+            take = ok & np.isfinite(rse[:, d]) & (rse[:, d] > 0.0) & np.isfinite(est[:, d])
+        used[name] = int(take.sum())
+        se = standard_errors.get(name)
+        if se is None or used[name] < 2:
+            intervals[name] = None
+            continue
+        t = (est[take, d] - float(estimate[d])) / rse[take, d]
+        q_lo, q_hi = _percentiles(t, level)
+        intervals[name] = [float(estimate[d] - q_hi * se), float(estimate[d] - q_lo * se)]
+    return intervals, used
+
+
+def _replicate_standard_errors(infos, names):
+    """B x P from observed_information_batch's dicts, NaN where a replicate has no standard error for the parameter."""
+    out = np.full((len(infos), len(names)), np.nan)
+    for b, info in enumerate(infos):
+        for d, name in enumerate(names):
+            if info['standard_errors'][name] is not None:
+                out[b, d] = info['standard_errors'][name]
+    return out
+
+
 def parametric_bootstrap(model, estimate, replicates=100, seed=0, fix=None, level=0.95, hist_orig=None, sample_factor=1,
-                         refit="sequential", **estimator_options):
+                         refit="sequential", studentized=False, **estimator_options):
     """`replicates` histograms of round(sum(counts) + tail) draws from `model` at `estimate` (model_cells), each
     refitted by CoverageEstimator(model_b, fix=fix, **estimator_options) started at `estimate`, one after the other.
 
@@ -234,6 +277,14 @@ def parametric_bootstrap(model, estimate, replicates=100, seed=0, fix=None, leve
     `level` per parameter name over the successful refits (None for a fixed parameter), failed; and, with `hist_orig`,
     genome_size {mean, standard_error, interval}: a replicate's genome size is sum i * h_i of hist_orig -- held
     fixed: the number of k-mer occurrences is a property of the read set -- over correct_c(c_b * sample_factor).
+
+    studentized=True, on every `refit` route: the replicates' observed information at their own refits from one batch
+    call (information.observed_information_batch; the lock-step routes keep their batch for it, the sequential route
+    builds HistogramBatch(model, counts, tails) from the rows it drew), and three more keys: replicate_standard_errors
+    (B x P, NaN where a replicate has none: a fixed parameter, one on its bound, an information that is not positive
+    definite), studentized_used (per name the replicates behind t) and t_intervals (t_intervals above, with
+    information.observed_information(model, estimate, fix)'s standard errors of the original); with `hist_orig`
+    genome_size['t_interval'], the coverage interval's endpoints through the monotone map c -> genome size.
     See the module's docstring for what these numbers do and do not say."""
     replicates, seed = int(replicates), int(seed)
     estimate = [float(v) for v in estimate]
@@ -251,24 +302,43 @@ def parametric_bootstrap(model, estimate, replicates=100, seed=0, fix=None, leve
     success = np.zeros(replicates, dtype=bool)
     loglik = np.full(replicates, np.nan)
     at_bound = np.zeros((replicates, len(names)), dtype=bool)
-    if refit != "sequential":
-        estimates, success, loglik = _refit_lockstep(model, estimate, replicates, seed, n_draws, fix, estimator_options,
-                                                     analytic=refit == "lockstep-gradient")
-        for b in range(replicates):
-            at_bound[b] = _on_bound(estimates[b], model.bounds)
-    else:
-        keys, weights, has_tail = model_cells(model, estimate)
-        counts = draw_histograms(weights, n_draws, replicates, seed=seed, device=model.device)
-        n_keys = len(keys)
-        for b in range(replicates):
-            tail_b = int(counts[b, n_keys]) if has_tail else 0
-            x, ok, ll = _refit(model, keys, counts[b, :n_keys], tail_b, estimate, fix, estimator_options)
-            estimates[b], success[b], loglik[b] = x, ok, ll
-            at_bound[b] = _on_bound(x, model.bounds)
+    batch = None  # (studentized) the replicates' histograms, for their observed information
+    try:
+        if refit != "sequential":
+            if studentized:
+                from .batch import HistogramBatch
+                batch = HistogramBatch.draw(model, estimate, replicates, seed=seed, n_draws=n_draws)
+            estimates, success, loglik = _refit_lockstep(model, estimate, replicates, seed, n_draws, fix, estimator_options,
+                                                         analytic=refit == "lockstep-gradient", batch=batch)
+            for b in range(replicates):
+                at_bound[b] = _on_bound(estimates[b], model.bounds)
+        else:
+            keys, weights, has_tail = model_cells(model, estimate)
+            counts = draw_histograms(weights, n_draws, replicates, seed=seed, device=model.device)
+            n_keys = len(keys)
+            for b in range(replicates):
+                tail_b = int(counts[b, n_keys]) if has_tail else 0
+                x, ok, ll = _refit(model, keys, counts[b, :n_keys], tail_b, estimate, fix, estimator_options)
+                estimates[b], success[b], loglik[b] = x, ok, ll
+                at_bound[b] = _on_bound(x, model.bounds)
+            if studentized:
+                from .batch import HistogramBatch
+                batch = HistogramBatch(model, counts[:, :n_keys].astype(np.float64),
+                                       counts[:, n_keys].astype(np.float64) if has_tail else None)
+        if studentized:
+            from .information import observed_information, observed_information_batch
+            replicate_se = _replicate_standard_errors(observed_information_batch(batch, estimates, fix), names)
+            original = observed_information(model, estimate, fix)
+    finally:
+        if batch is not None:
+            batch.close()
     out = {'replicates': replicates, 'seed': seed, 'n_draws': n_draws, 'level': float(level), 'params': names,
            'estimate': estimate, 'estimates': estimates, 'success': success, 'loglikelihood': loglik, 'at_bound': at_bound,
            'refit': refit}
     out.update(summarize(estimates, success, estimate, names, fix=fix, level=level))
+    if studentized:
+        intervals, used = t_intervals(estimates, success, replicate_se, estimate, original['standard_errors'], names, level)
+        out.update(replicate_standard_errors=replicate_se, studentized_used=used, t_intervals=intervals)
     if hist_orig is not None:
         occurrences = sum(i * h for i, h in hist_orig.items())
         good = estimates[success, 0]
@@ -277,4 +347,9 @@ def parametric_bootstrap(model, estimate, replicates=100, seed=0, fix=None, leve
         out['genome_size'] = {'mean': float(sizes.mean()) if len(sizes) else None,
                               'standard_error': float(sizes.std(ddof=1)) if len(sizes) > 1 else None,
                               'interval': [float(lo), float(hi)] if len(sizes) else None}
+        if studentized:  # (the genome size falls as the coverage rises: the endpoints change places)
+            c_int = out['t_intervals'][names[0]]
+            ends = None if c_int is None else [model.correct_c(c * sample_factor) for c in c_int]
+            out['genome_size']['t_interval'] = (sorted(float(occurrences / v) for v in ends)
+                                                if ends is not None and all(v > 0 for v in ends) else None)
     return out

@@ -1,10 +1,11 @@
 // abi_batch.cpp -- covest_batch_* of the C ABI over ll_batch.hip: a batch of histograms on one model's key set, scored
-// in one pass (DESIGN.md sections 6r, 6u and, for the staging of this file, 6w).  The argument rules, the chunking of a
+// in one pass (DESIGN.md sections 6r, 6u, 6x and, for the staging of this file, 6w).  The argument rules, the chunking of a
 // point list against the table budget and the cut of launches are batch_host.h's (plain C++, checked without a device).
 // A batch borrows its model; every call takes the model's lock and works on the model's device.
 //
 // An evaluation is open_call (the rules, the lock, fresh counters), then walk_chunks: the point list goes up once, and
-// per chunk table_chunk builds the table of R rows a point (R = 1: log p; R = P + 1: with the scores), a STAGE contracts
+// per chunk table_chunk builds the table of R rows a point (R = 1: log p; R = P + 1: with the scores; R = 1 + P +
+// P (P + 1) / 2: with the curvature rows behind them), a STAGE contracts
 // it with the histograms into b->out (cross_stage, pairs_stage; the score table has none) and the entry point's own
 // few lines deliver the chunk.
 #include "host.h"
@@ -32,8 +33,9 @@ struct covest_batch {
     DevBuf out;              // a chunk's values: [n_hist][points of the chunk][R] (cross), [points][R] (pairs)
     DevBuf index, dead_list; // a pairs call's histogram numbers; the value rows of the chunk's points with dead keys
     DevBuf run_val, run_idx; // the running arg-min of covest_batch_argmin_cross
-    DevBuf partial, fin;     // the gradient's table: the derivative kernel's segment sums; its finishing pass's value
-                             // [points] and gradient [points][P] (the tail coefficients before they are packed into tl)
+    DevBuf partial, fin;     // the gradient's and the Hessian's table: the derivative kernel's segment sums; its finishing
+                             // pass's value [points], gradient [points][P] and (order 2) Hessian [points][P][P] (the tail
+                             // coefficients before they are packed into tl)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // ev[0] .. ev[1]: a chunk's table; ev[2] .. ev[3]: its stage
     int64_t info[kInfoFields] = {};
     ~covest_batch()
@@ -88,9 +90,8 @@ int upload_points(covest_batch *b, int64_t n, const double *params, PointSource 
     return COVEST_OK;
 }
 
-// Rows a point of the table: 1 for the values, P + 1 for the gradient (the value row, then a score
-// row a parameter, from the derivative kernel's walk).
-int rows_per_point(const covest_batch *b, bool grad) { return grad ? b->model->n_par + 1 : 1; }
+// Rows a point of the table for derivatives up to `order` (0, 1, 2): batch_host.h's
+int rows_per_point(const covest_batch *b, int order) { return batch_rows_per_point(b->model->n_par, order); }
 
 // room for a chunk of nc_max points at R rows each
 int reserve_chunk(covest_batch *b, int64_t nc_max, int R)
@@ -101,9 +102,10 @@ int reserve_chunk(covest_batch *b, int64_t nc_max, int R)
     HIP_TRY(b->table.reserve((size_t)nc_max * (size_t)R * (size_t)b->n_keys * sizeof(double)));
     HIP_TRY(b->tl.reserve((size_t)nc_max * (size_t)R * sizeof(double)));
     HIP_TRY(b->dead.reserve((size_t)nc_max * sizeof(int32_t)));
-    if (R > 1) {
-        HIP_TRY(b->partial.reserve(ll_deriv_partial_bytes(table_model(b), 1, nc_max)));
-        HIP_TRY(b->fin.reserve((size_t)nc_max * (size_t)R * sizeof(double)));
+    if (R > 1) { // the derivative kernel's buffers, by DerivLayout<P, order>; fin: value, gradient and (order 2) P x P
+        const int P = b->model->n_par, order = batch_table_order(P, R);
+        HIP_TRY(b->partial.reserve(ll_deriv_partial_bytes(table_model(b), order, nc_max)));
+        HIP_TRY(b->fin.reserve((size_t)nc_max * (size_t)(1 + P + (order == 2 ? P * P : 0)) * sizeof(double)));
     }
     return COVEST_OK;
 }
@@ -119,10 +121,11 @@ int table_chunk(covest_batch *b, const PointSource &src, int64_t first, int64_t 
         HIP_TRY(launch_batch_table(table_model(b), part, nc, b->table.as<double>(), b->tl.as<double>(),
                                    b->dead.as<int32_t>(), false, nullptr));
     } else {
-        double *fin_ll = b->fin.as<double>(), *fin_grad = fin_ll + nc;
-        HIP_TRY(launch_ll_deriv_table(table_model(b), part, nc, b->partial.as<double>(), b->table.as<double>(),
-                                      b->dead.as<int32_t>(), fin_ll, fin_grad, nullptr));
-        HIP_TRY(launch_batch_tail_pack(fin_ll, fin_grad, nc, R, b->tl.as<double>(), nullptr));
+        const int P = b->model->n_par, order = batch_table_order(P, R);
+        double *fin_ll = b->fin.as<double>(), *fin_grad = fin_ll + nc, *fin_hess = order == 2 ? fin_grad + nc * P : nullptr;
+        HIP_TRY(launch_ll_deriv_table(table_model(b), order, part, nc, b->partial.as<double>(), b->table.as<double>(),
+                                      b->dead.as<int32_t>(), fin_ll, fin_grad, fin_hess, nullptr));
+        HIP_TRY(launch_batch_tail_pack(fin_ll, fin_grad, fin_hess, nc, P, R, b->tl.as<double>(), nullptr));
     }
     HIP_TRY(hipEventRecord(b->ev[1], nullptr));
     std::vector<int32_t> dead((size_t)nc), list;
@@ -184,7 +187,7 @@ int walk_chunks(covest_batch *b, int64_t n, const double *params, int R, int64_t
 }
 
 // The cross stage: every histogram against the chunk's nc R table rows, b->out[h][i R + q] with row length nc R; -inf
-// where a histogram counts a dead key of a point; behind a gradient's value that is not finite, NaN derivatives.
+// where a histogram counts a dead key of a point; behind a value that is not finite, NaN derivatives.
 int cross_stage(covest_batch *b, int64_t nc, int R, int64_t n_dead)
 {
     const int64_t ld = nc * R; // the contraction sees R nc rows of the table and as many tail coefficients
@@ -234,14 +237,14 @@ int open_call(const char *who, covest_batch *b, Rule rule, std::optional<BatchCa
     return call.emplace(b).status;
 }
 
-// covest_batch_eval_cross and _cross_grad: out[h][i][R] of the whole list, chunk by chunk
-int eval_cross(const char *who, covest_batch *b, int64_t n, const double *params, bool grad, double *out)
+// covest_batch_eval_cross, _cross_grad and _cross_hess (order 0, 1, 2): out[h][i][R] of the whole list, chunk by chunk
+int eval_cross(const char *who, covest_batch *b, int64_t n, const double *params, int order, double *out)
 {
     std::optional<BatchCall> call;
     COVEST_TRY(open_call(who, b, [&] { return batch_check_points(n, b->n_hist, params, out); }, call));
     if (n == 0 || b->n_hist == 0)
         return COVEST_OK;
-    const int R = rows_per_point(b, grad);
+    const int R = rows_per_point(b, order);
     return walk_chunks(
         b, n, params, R, b->n_hist, [&](int64_t, int64_t nc, int64_t n_dead) { return cross_stage(b, nc, R, n_dead); },
         [&](int64_t first, int64_t nc) -> int {
@@ -252,8 +255,8 @@ int eval_cross(const char *who, covest_batch *b, int64_t n, const double *params
         });
 }
 
-// covest_batch_eval_pairs and _pairs_grad: out[i][R]
-int eval_pairs(const char *who, covest_batch *b, int64_t n, const int64_t *hist_index, const double *params, bool grad,
+// covest_batch_eval_pairs, _pairs_grad and _pairs_hess (order 0, 1, 2): out[i][R]
+int eval_pairs(const char *who, covest_batch *b, int64_t n, const int64_t *hist_index, const double *params, int order,
                double *out)
 {
     std::optional<BatchCall> call;
@@ -263,13 +266,31 @@ int eval_pairs(const char *who, covest_batch *b, int64_t n, const int64_t *hist_
     HIP_TRY(b->index.reserve((size_t)n * sizeof(int64_t)));
     COVEST_TRY(stage_upload(b->index.ptr, hist_index, (size_t)n * sizeof(int64_t),
                             (std::string(who) + ": upload of the index").c_str()));
-    const int R = rows_per_point(b, grad);
+    const int R = rows_per_point(b, order);
     return walk_chunks(
         b, n, params, R, 1, [&](int64_t first, int64_t nc, int64_t) { return pairs_stage(b, first, nc, R); },
         [&](int64_t first, int64_t nc) -> int {
             HIP_TRY(hipMemcpy(out + first * R, b->out.ptr, (size_t)nc * (size_t)R * sizeof(double), hipMemcpyDeviceToHost));
             return COVEST_OK;
         });
+}
+
+// covest_batch_score_table and _score_table2 (order 1, 2): the stage-less walk, the chunk's table and tail coefficients
+// handed back as they are
+int score_table(const char *who, covest_batch *b, int64_t n, const double *params, int order, double *out_rows,
+                double *out_tail)
+{
+    std::optional<BatchCall> call; // (the table does not depend on the histograms: the rule of a batch of one)
+    COVEST_TRY(open_call(who, b, [&] { return batch_check_points(n, 1, params, out_rows, out_tail); }, call));
+    if (n == 0)
+        return COVEST_OK;
+    const int R = rows_per_point(b, order);
+    return walk_chunks(b, n, params, R, 0, nullptr, [&](int64_t first, int64_t nc) -> int {
+        HIP_TRY(hipMemcpy(out_rows + first * R * b->n_keys, b->table.ptr,
+                          (size_t)nc * (size_t)R * (size_t)b->n_keys * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_tail + first * R, b->tl.ptr, (size_t)nc * (size_t)R * sizeof(double), hipMemcpyDeviceToHost));
+        return COVEST_OK;
+    });
 }
 
 int new_batch(covest_model *m, int64_t n_hist, covest_batch **out)
@@ -395,22 +416,32 @@ int covest_batch_counts(covest_batch *b, double *out_counts, double *out_tails)
 
 int covest_batch_eval_cross(covest_batch *b, int64_t n, const double *params, double *out_ll)
 {
-    return eval_cross("covest_batch_eval_cross", b, n, params, false, out_ll);
+    return eval_cross("covest_batch_eval_cross", b, n, params, 0, out_ll);
 }
 
 int covest_batch_eval_cross_grad(covest_batch *b, int64_t n, const double *params, double *out)
 {
-    return eval_cross("covest_batch_eval_cross_grad", b, n, params, true, out);
+    return eval_cross("covest_batch_eval_cross_grad", b, n, params, 1, out);
+}
+
+int covest_batch_eval_cross_hess(covest_batch *b, int64_t n, const double *params, double *out)
+{
+    return eval_cross("covest_batch_eval_cross_hess", b, n, params, 2, out);
 }
 
 int covest_batch_eval_pairs(covest_batch *b, int64_t n, const int64_t *hist_index, const double *params, double *out_ll)
 {
-    return eval_pairs("covest_batch_eval_pairs", b, n, hist_index, params, false, out_ll);
+    return eval_pairs("covest_batch_eval_pairs", b, n, hist_index, params, 0, out_ll);
 }
 
 int covest_batch_eval_pairs_grad(covest_batch *b, int64_t n, const int64_t *hist_index, const double *params, double *out)
 {
-    return eval_pairs("covest_batch_eval_pairs_grad", b, n, hist_index, params, true, out);
+    return eval_pairs("covest_batch_eval_pairs_grad", b, n, hist_index, params, 1, out);
+}
+
+int covest_batch_eval_pairs_hess(covest_batch *b, int64_t n, const int64_t *hist_index, const double *params, double *out)
+{
+    return eval_pairs("covest_batch_eval_pairs_hess", b, n, hist_index, params, 2, out);
 }
 
 int covest_batch_argmin_cross(covest_batch *b, int64_t n, const double *params, double *out_min_negll, int64_t *out_arg)
@@ -437,18 +468,12 @@ int covest_batch_argmin_cross(covest_batch *b, int64_t n, const double *params, 
 
 int covest_batch_score_table(covest_batch *b, int64_t n, const double *params, double *out_rows, double *out_tail)
 {
-    std::optional<BatchCall> call; // (the table does not depend on the histograms: the rule of a batch of one)
-    COVEST_TRY(open_call("covest_batch_score_table", b, [&] { return batch_check_points(n, 1, params, out_rows, out_tail); },
-                         call));
-    if (n == 0)
-        return COVEST_OK;
-    const int R = rows_per_point(b, true);
-    return walk_chunks(b, n, params, R, 0, nullptr, [&](int64_t first, int64_t nc) -> int {
-        HIP_TRY(hipMemcpy(out_rows + first * R * b->n_keys, b->table.ptr,
-                          (size_t)nc * (size_t)R * (size_t)b->n_keys * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_tail + first * R, b->tl.ptr, (size_t)nc * (size_t)R * sizeof(double), hipMemcpyDeviceToHost));
-        return COVEST_OK;
-    });
+    return score_table("covest_batch_score_table", b, n, params, 1, out_rows, out_tail);
+}
+
+int covest_batch_score_table2(covest_batch *b, int64_t n, const double *params, double *out_rows, double *out_tail)
+{
+    return score_table("covest_batch_score_table2", b, n, params, 2, out_rows, out_tail);
 }
 
 int covest_batch_info(covest_batch *b, int64_t *out)

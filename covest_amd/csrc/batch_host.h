@@ -71,8 +71,19 @@ inline const char *batch_check_pairs(int64_t n, int64_t n_hist, const int64_t *i
     return batch_check_index(n, index, n_hist);
 }
 
+// Rows a point of the table of a model with n_par parameters, by the order of the derivatives asked for: 1 for the values
+// (order 0), P + 1 with the gradient (the value row, then a score row a parameter), and
+// 1 + P + P (P + 1) / 2 with the Hessian (behind those a curvature row a pair k <= l; section 6x): 6 and 21.
+inline int batch_rows_per_point(int n_par, int order)
+{
+    return order <= 0 ? 1 : order == 1 ? n_par + 1 : 1 + n_par + n_par * (n_par + 1) / 2;
+}
+
+// ... and the order a table of `rows` rows a point was built for
+inline int batch_table_order(int n_par, int rows) { return rows <= 1 ? 0 : rows == n_par + 1 ? 1 : 2; }
+
 // Points of one table chunk: as many as the budget holds at `rows_per_point` rows of n_keys doubles each (1: the value
-// table; P + 1: the gradient's, the value row and one score row a parameter), one at least.
+// table; P + 1: the gradient's; 1 + P + P (P + 1) / 2: the Hessian's), one at least.
 inline int64_t batch_points_per_chunk(int64_t n_keys, int64_t rows_per_point, int64_t budget_bytes)
 {
     const int64_t point = (n_keys > 0 ? n_keys : 1) * (rows_per_point > 0 ? rows_per_point : 1) * (int64_t)sizeof(double);

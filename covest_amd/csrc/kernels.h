@@ -169,15 +169,20 @@ size_t ll_deriv_partial_bytes(const DevModel &m, int order, int64_t n);
 hipError_t launch_ll_deriv(const DevModel &m, int order, const PointSource &src, int64_t n, double *partial, double *out_ll,
                            double *out_grad, double *out_hess, hipStream_t stream);
 
-// K-grad's walk (order 1) with its per-key quantities stored on the way: `m` is the batch's table
+// K-grad's walk (order 1) or K-hess's (order 2) with its per-key quantities stored on the way (DESIGN.md sections 6u, 6x): `m` is the batch's table
 // model (the all-keys view, a zero count array, tail 1).  rows: per point P + 1 rows of n_keys doubles, point-major -- row
 // (P + 1) i is log p_ij in launch_batch_table's conventions (+0.0 dead and nothing else, p = 1 as -0.0, NaN stays), rows
 // (P + 1) i + 1 + k the scores d_k p_ij / p_ij, +0.0 at a dead key and throughout where the clamp moved parameter k;
 // dead[i] the keys with p_ij <= 0.  With zero counts and tail 1 the finishing pass leaves the tail coefficients:
 // out_ll[i] = log(1 - sp_i), out_grad[i][k] = -S_k / (1 - sp_i), all 0 where sp_i is not < 1, 0 for a moved parameter.
-// partial: ll_deriv_partial_bytes(m, 1, n) bytes.  The launch cut is launch_ll_deriv's.
-hipError_t launch_ll_deriv_table(const DevModel &m, const PointSource &src, int64_t n, double *partial, double *rows,
-                                 int32_t *dead, double *out_ll, double *out_grad, hipStream_t stream);
+// Order 2: R2 = 1 + P + P (P + 1) / 2 rows a point -- behind the P + 1 above, at row R2 i + 1 + P + pair(k, l), k <= l row by
+// row, c_kl(j) = d_k d_l p_ij / p_ij - (d_k p_ij / p_ij)(d_l p_ij / p_ij), +0.0 at a dead key and throughout where the clamp
+// moved k or l -- and out_hess[i][P][P] the tail's second-order coefficients
+// -(S_kl / (1 - sp_i) + S_k S_l / (1 - sp_i)^2), S_kl = sum_j d_k d_l p_ij, with the same zeros (not read at order 1).
+// partial: ll_deriv_partial_bytes(m, order, n) bytes.  The launch cut is launch_ll_deriv's; not entered in the launch
+// record.
+hipError_t launch_ll_deriv_table(const DevModel &m, int order, const PointSource &src, int64_t n, double *partial, double *rows,
+                                 int32_t *dead, double *out_ll, double *out_grad, double *out_hess, hipStream_t stream);
 
 // ---- K-tp (tp_eval.hip): the truncated-Poisson pmf itself, c_src/covest_poissonmodule.c:7-35 ----
 // Modes of the pairs kernel (include/covest_amd.h COVEST_TP_*): the finite value the formula defines (0 below the
@@ -371,15 +376,18 @@ hipError_t launch_batch_fix_dead(const double *H, int64_t n_hist, const double *
 // out[i * R + q] = sum_j H[index[i]][j] rows[i * R + q][j] + tails[index[i]] tc[i * R + q], one wave a request: the R dot
 // products in one sweep over the keys; the dead-key rule inline (value -inf), and where the value is not finite the
 // R - 1 derivative entries NaN.  R is 1 (the value form: rows and tc are launch_batch_table's table and tl) or, for the
-// gradient's table below, 3 or 6.
+// gradient's and the Hessian's tables below, 3 or 6, or 21 (the repeat model's second-order table; the basic model's has
+// 6).
 hipError_t launch_batch_pairs(const double *H, const double *tails, const int64_t *index, const double *rows,
                               const double *tc, int64_t n, int64_t n_keys, int rows_per_point, double *out,
                               hipStream_t stream);
-// ---- the gradient of a batch: `rows` is launch_ll_deriv_table's, R = P + 1 rows a point ----
-// tc[i * R + q] from the finishing pass's out_ll[i] (q = 0) and out_grad[i][q - 1]: the array launch_batch_cross takes
-// for tl when the table has R n rows.
-hipError_t launch_batch_tail_pack(const double *fin_ll, const double *fin_grad, int64_t n, int rows_per_point, double *tc,
-                                  hipStream_t stream);
+// ---- the gradient and the Hessian of a batch (DESIGN.md sections 6u, 6x): `rows` is launch_ll_deriv_table's, R = P + 1
+// or 1 + P + P (P + 1) / 2 rows a point ----
+// tc[i * R + q] from the finishing pass's out_ll[i] (q = 0), out_grad[i][q - 1] (q <= P) and, where R > P + 1, the upper
+// triangle of out_hess[i][P][P], k <= l row by row (fin_hess is not read otherwise): the array launch_batch_cross takes for
+// tl when the table has R n rows.
+hipError_t launch_batch_tail_pack(const double *fin_ll, const double *fin_grad, const double *fin_hess, int64_t n, int n_par,
+                                  int rows_per_point, double *tc, hipStream_t stream);
 // out is n_hist x (n * R) with row length ld (launch_batch_cross over R n rows, then launch_batch_fix_dead with the dead
 // points' VALUE rows listed): where out[b * ld + i * R] is not finite, the R - 1 entries behind it become NaN.
 hipError_t launch_batch_grad_specials(int64_t n_hist, int64_t n, int rows_per_point, double *out, int64_t ld,

@@ -26,8 +26,9 @@
 //                         nothing (covest/models.py:105-107, `if h`).
 //   batch_pairs_kernel<R> histogram index[i] at point i, one wave a request, the dead-key rule inline; R rows a point,
 //                         a request's R dot products in one sweep (R = 1: the value form).
-//   batch_tail_pack_kernel, batch_grad_specials_kernel  the gradient of a batch: the same
-//                         contraction over the derivative kernel's score table, R = P + 1 rows a point.
+//   batch_tail_pack_kernel, batch_grad_specials_kernel  the gradient and the Hessian of a batch (DESIGN.md sections 6u,
+//                         6x): the same contraction over the derivative kernel's table, R = P + 1 rows a point for the
+//                         gradient, R2 = 1 + P + P (P + 1) / 2 (6 and 21) with the curvature rows c_kl behind them.
 //   batch_argmin_kernel   per histogram the first index of the strictly smallest -LL (covest/grid.py:65-70), carried
 //                         across table chunks on the device.
 //   batch_from_draw_kernel  int64 rows of draw_hist.hip to double counts and tails.
@@ -208,15 +209,27 @@ __global__ __launch_bounds__(256) void batch_pairs_kernel(const double *__restri
     }
 }
 
+// (R > P + 1: behind the value and the P first-order coefficients the upper triangle of the finishing pass's P x P, k <= l
+// row by row)
 __global__ __launch_bounds__(256) void batch_tail_pack_kernel(const double *__restrict__ fin_ll,
-                                                              const double *__restrict__ fin_grad, const int64_t n,
+                                                              const double *__restrict__ fin_grad,
+                                                              const double *__restrict__ fin_hess, const int64_t n, const int P,
                                                               const int R, double *__restrict__ tc)
 {
     const int64_t total = n * R;
     for (int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; at < total; at += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = at / R;
         const int q = (int)(at - i * R);
-        tc[at] = q == 0 ? fin_ll[i] : fin_grad[i * (R - 1) + (q - 1)];
+        if (q <= P) {
+            tc[at] = q == 0 ? fin_ll[i] : fin_grad[i * P + (q - 1)];
+        } else {
+            int k = 0, first = 1 + P; // row k of the triangle begins at entry `first` and holds P - k pairs
+            while (q >= first + (P - k)) {
+                first += P - k;
+                ++k;
+            }
+            tc[at] = fin_hess[(i * P + k) * P + k + (q - first)];
+        }
     }
 }
 
@@ -358,7 +371,8 @@ hipError_t launch_batch_pairs(const double *H, const double *tails, const int64_
     const auto kernel = rows_per_point == 1   ? batch_pairs_kernel<1>
                         : rows_per_point == 3 ? batch_pairs_kernel<3>
                         : rows_per_point == 6 ? batch_pairs_kernel<6>
-                                              : nullptr;
+                        : rows_per_point == 21 ? batch_pairs_kernel<21>
+                                               : nullptr;
     if (!kernel)
         return hipErrorInvalidValue;
     return launch_waves(n, [&](dim3 grid, dim3 block, int64_t w0) {
@@ -366,14 +380,14 @@ hipError_t launch_batch_pairs(const double *H, const double *tails, const int64_
     });
 }
 
-hipError_t launch_batch_tail_pack(const double *fin_ll, const double *fin_grad, int64_t n, int rows_per_point, double *tc,
-                                  hipStream_t stream)
+hipError_t launch_batch_tail_pack(const double *fin_ll, const double *fin_grad, const double *fin_hess, int64_t n, int n_par,
+                                  int rows_per_point, double *tc, hipStream_t stream)
 {
     const int64_t total = n * rows_per_point;
     if (total <= 0)
         return hipSuccess;
-    hipLaunchKernelGGL(batch_tail_pack_kernel, elementwise_grid(total), dim3(256), 0, stream, fin_ll, fin_grad, n,
-                       rows_per_point, tc);
+    hipLaunchKernelGGL(batch_tail_pack_kernel, elementwise_grid(total), dim3(256), 0, stream, fin_ll, fin_grad, fin_hess, n,
+                       n_par, rows_per_point, tc);
     return hipGetLastError();
 }
 

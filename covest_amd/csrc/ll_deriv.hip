@@ -75,17 +75,19 @@ __device__ __forceinline__ void hess_coef(double a, double da, double dap, doubl
     al = d2a - l1 * cross - a * l1 * d2x + a * xx * (l1 * l1 - l2);
 }
 
-// TABLE (order 1 only) is the same walk with its per-key quantities stored on the way, before the
-// counts enter: Extra is then (double *rows, int32_t *dead) -- into row (P + 1) pt of `rows` (n_bins doubles a row) goes
-// log p_j, behind it the P rows d_k p_j / p_j, and dead[pt] (zeroed by the launcher) counts the keys with p_j <= 0.  It
-// is launched on the batch's all-keys view with zero counts and tail 1, so that the segment sums are those of the pure
-// tail term and ll_deriv_finish_kernel<P, 1> returns the tail coefficients.  The stores sit in the key epilogue behind
-// `if constexpr`; without TABLE the pack is empty and the six instantiations compile to the instructions they had.
+// TABLE (orders 1 and 2; DESIGN.md sections 6u, 6x) is the same walk with its per-key quantities stored on the way, before
+// the counts enter: Extra is then (double *rows, int32_t *dead) -- into row RT pt of `rows` (n_bins doubles a row; RT = P + 1
+// at order 1, 1 + P + P (P + 1) / 2 at order 2) goes log p_j, behind it the P rows d_k p_j / p_j, at order 2 behind those
+// the rows c_kl(j) = d_k d_l p_j / p_j - (d_k p_j / p_j)(d_l p_j / p_j), k <= l row by row, and dead[pt] (zeroed by the
+// launcher) counts the keys with p_j <= 0.  It is launched on the batch's all-keys view with zero counts and tail 1, so that
+// the segment sums are those of the pure tail term and ll_deriv_finish_kernel<P, ORDER> returns the tail coefficients.  The
+// stores sit in the key epilogue behind `if constexpr`; without TABLE the pack is empty and the six instantiations compile
+// to the instructions they had, and the order-1 table's to those it had.
 template <int P, int ORDER, bool TABLE = false, class... Extra>
 __global__ __launch_bounds__(kDerivWaves *kWave) void ll_deriv_kernel(const DevModel m, const PointSource src,
                                                                       double *__restrict__ partial, Extra... extra)
 {
-    static_assert(!TABLE || ORDER == 1, "the score table is first order");
+    static_assert(!TABLE || ORDER == 1 || ORDER == 2, "the table is first or second order");
     static_assert(sizeof...(Extra) == (TABLE ? 2 : 0), "TABLE takes (double *rows, int32_t *dead)");
     double *rows = nullptr;
     int32_t *dead = nullptr;
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(kDerivWaves *kWave) void ll_deriv_kernel(const DevM
         double par[kMaxParams];
         int T;
         fetch_point<P>(src, pt, par, T);
-        bool moved[P]; // (TABLE) the clamp moved the parameter: its score row is 0, K-grad's rule
+        bool moved[P]; // (TABLE) the clamp moved the parameter: its score row is 0, K-grad's rule (its c_kl rows: K-hess's)
         if constexpr (TABLE) {
             double raw[P];
 #pragma unroll
@@ -353,7 +355,7 @@ __global__ __launch_bounds__(kDerivWaves *kWave) void ll_deriv_kernel(const DevM
             if constexpr (TABLE) {
                 // the batch table's conventions (ll_batch.hip): +0.0 is a dead key's and nothing else's, p = 1 is -0.0,
                 // NaN stays NaN; a dead key's scores are +0.0, so that a histogram that does not count it adds 0
-                double *row = rows + (int64_t)pt * (P + 1) * n_bins + idx;
+                double *row = rows + (int64_t)pt * (P + 1 + NP) * n_bins + idx; // (P + 1 + NP rows a point)
                 const bool is_dead = p <= 0.0;
                 double l = 0.0;
                 if (!is_dead) {
@@ -365,6 +367,19 @@ __global__ __launch_bounds__(kDerivWaves *kWave) void ll_deriv_kernel(const DevM
 #pragma unroll
                 for (int d = 0; d < P; ++d)
                     row[(int64_t)(1 + d) * n_bins] = (is_dead || moved[d]) ? 0.0 : p1[d] / p;
+                if constexpr (ORDER == 2) {
+                    double r1[P]; // d_k p / p, as the sums below form it
+#pragma unroll
+                    for (int d = 0; d < P; ++d)
+                        r1[d] = p1[d] / p;
+#pragma unroll
+                    for (int k = 0; k < P; ++k)
+#pragma unroll
+                        for (int l = k; l < P; ++l) {
+                            const int q = pair_index(P, k, l);
+                            row[(int64_t)(1 + P + q) * n_bins] = (is_dead || moved[k] || moved[l]) ? 0.0 : p2[q] / p - r1[k] * r1[l];
+                        }
+                }
                 if (is_dead)
                     atomicAdd(dead + pt, 1);
             }
@@ -538,8 +553,8 @@ void launch_part(const DevModel &m, const PointSource &part, int n_seg, int64_t 
                  double *out_grad, double *out_hess, double *rows, int32_t *dead, hipStream_t stream)
 {
     if (rows) {
-        if constexpr (ORDER == 1)
-            hipLaunchKernelGGL((ll_deriv_kernel<P, 1, true, double *, int32_t *>), dim3((unsigned)n_seg, (unsigned)cnt), dim3(kDerivWaves * kWave), 0,
+        if constexpr (ORDER == 1 || ORDER == 2)
+            hipLaunchKernelGGL((ll_deriv_kernel<P, ORDER, true, double *, int32_t *>), dim3((unsigned)n_seg, (unsigned)cnt), dim3(kDerivWaves * kWave), 0,
                                stream, m, part, partial, rows, dead);
     } else {
         hipLaunchKernelGGL((ll_deriv_kernel<P, ORDER>), dim3((unsigned)n_seg, (unsigned)cnt), dim3(kDerivWaves * kWave), 0,
@@ -576,22 +591,23 @@ size_t ll_deriv_partial_bytes(const DevModel &m, int order, int64_t n)
 
 namespace {
 
-// the launches of a point list, cut at kDerivPointsPerLaunch points; rows != nullptr: the table-writing walk (order 1)
+// the launches of a point list, cut at kDerivPointsPerLaunch points; rows != nullptr: the table-writing walk (order 1 or 2)
 hipError_t deriv_launches(const DevModel &m, int order, const PointSource &src, int64_t n, double *partial, double *out_ll,
                           double *out_grad, double *out_hess, double *rows, int32_t *dead, hipStream_t stream)
 {
     if (n <= 0)
         return hipSuccess;
-    if (src.is_grid || (order != 1 && order != 2 && order != kDerivOpg) || (rows && (order != 1 || !dead)))
+    if (src.is_grid || (order != 1 && order != 2 && order != kDerivOpg) || (rows && (order == kDerivOpg || !dead)))
         return hipErrorInvalidValue;
     const int n_seg = ll_deriv_segments(m);
     const int P = m.kind == 0 ? 2 : 5;
+    const int64_t table_rows = order == 2 ? 1 + P + P * (P + 1) / 2 : P + 1; // (rows a point of the table-writing walk)
     const auto launch = P == 2 ? (order == 1 ? launch_part<2, 1> : order == 2 ? launch_part<2, 2> : launch_part<2, kDerivOpg>)
                                : (order == 1 ? launch_part<5, 1> : order == 2 ? launch_part<5, 2> : launch_part<5, kDerivOpg>);
     for (int64_t first = 0; first < n; first += kDerivPointsPerLaunch) {
         const int64_t cnt = n - first < kDerivPointsPerLaunch ? n - first : kDerivPointsPerLaunch;
         launch(m, points_from(src, first, P), n_seg, cnt, partial, out_ll + first, out_grad + first * P,
-               order != 1 ? out_hess + first * P * P : nullptr, rows ? rows + first * (P + 1) * m.bins.n : nullptr,
+               order != 1 ? out_hess + first * P * P : nullptr, rows ? rows + first * table_rows * m.bins.n : nullptr,
                rows ? dead + first : nullptr, stream);
         if (!rows) // (the table-writing walk is the batch's: not a variant of the launch record)
             record_launch(kDerivVariantNames[(P == 5 ? 3 : 0) + (order == 1 ? 0 : order == 2 ? 1 : 2)]);
@@ -608,15 +624,15 @@ hipError_t launch_ll_deriv(const DevModel &m, int order, const PointSource &src,
     return deriv_launches(m, order, src, n, partial, out_ll, out_grad, out_hess, nullptr, nullptr, stream);
 }
 
-hipError_t launch_ll_deriv_table(const DevModel &m, const PointSource &src, int64_t n, double *partial, double *rows,
-                                 int32_t *dead, double *out_ll, double *out_grad, hipStream_t stream)
+hipError_t launch_ll_deriv_table(const DevModel &m, int order, const PointSource &src, int64_t n, double *partial, double *rows,
+                                 int32_t *dead, double *out_ll, double *out_grad, double *out_hess, hipStream_t stream)
 {
     if (n <= 0)
         return hipSuccess;
     const hipError_t err = hipMemsetAsync(dead, 0, (size_t)n * sizeof(int32_t), stream);
     if (err != hipSuccess)
         return err;
-    return deriv_launches(m, 1, src, n, partial, out_ll, out_grad, nullptr, rows, dead, stream);
+    return deriv_launches(m, order, src, n, partial, out_ll, out_grad, out_hess, rows, dead, stream);
 }
 
 } // namespace covest

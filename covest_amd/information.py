@@ -1,6 +1,8 @@
 """The observed information at an estimate: the Hessian of -LL in closed form from the device
 (covest_eval_points_hess), its inverse over the identified parameters as a covariance, standard errors,
 correlations and Wald intervals -- for every parameter and the genome size, without a grid around the estimate.
+observed_information_batch does the same for every histogram of a HistogramBatch at its own point, from one call
+(covest_batch_eval_pairs_hess).
 
 What these numbers are and are not (the caveat of DESIGN.md 6d, unchanged): the model treats the k-mer counts as
 independent and |LL| is 1e7..1e8 on real histograms, so the curvature is huge and the standard errors are very small.
@@ -44,11 +46,19 @@ def observed_information(model, estimate, fix=None):
     if len(fix) != P:
         raise ValueError("observed_information: `fix` must have one entry per parameter")
     ll, grad, hess = model.loglikelihood_hessian_points([est])
+    return _information(names, est, [tuple(b) for b in model.bounds], fix, float(np.asarray(ll).reshape(-1)[0]),
+                        np.asarray(grad).reshape(-1), np.asarray(hess, dtype=np.float64).reshape(P, P))
+
+
+def _information(names, est, bounds, fix, ll, grad, hess):
+    """observed_information's dict from the value, gradient and Hessian OF LL at `est`: the free set, the Cholesky
+    inverse of its block, `reason`.  The one place these rules are written: observed_information (one model's own
+    histogram) and observed_information_batch (every histogram of a batch) both end here."""
+    P = len(names)
     H = -np.asarray(hess, dtype=np.float64).reshape(P, P)
-    bounds = [tuple(b) for b in model.bounds]
     info = {
-        'params': names, 'estimate': est, 'bounds': bounds, 'loglikelihood': float(np.asarray(ll).reshape(-1)[0]),
-        'gradient': [float(v) for v in np.asarray(grad).reshape(-1)], 'hessian': H.tolist(), 'free': [],
+        'params': names, 'estimate': est, 'bounds': bounds, 'loglikelihood': ll,
+        'gradient': [float(v) for v in grad], 'hessian': H.tolist(), 'free': [],
         'covariance': None, 'correlation': None, 'standard_errors': {n: None for n in names}, 'reason': None,
     }
     if not np.all(np.isfinite(H)):
@@ -74,6 +84,29 @@ def observed_information(model, estimate, fix=None):
     for at, d in enumerate(free):
         info['standard_errors'][names[d]] = float(se[at])
     return info
+
+
+def observed_information_batch(batch, estimates, fix=None):
+    """observed_information for every histogram of a HistogramBatch at its own point: estimates[b] is the estimate of
+    histogram b (B x P, the model's parameters).  ONE batch.loglikelihood_hessian_pairs(arange(B), estimates) call -- the
+    derivative kernel walks each point once at order 2 and the counts enter through a contraction (DESIGN.md section
+    6x) --, then per histogram the rules of observed_information: the free set, Cholesky, `reason`.  Returns the list of
+    B dicts, each as observed_information's.  The standard errors of the replicates of a parametric bootstrap
+    (bootstrap.parametric_bootstrap(studentized=True)); the module's docstring says what such errors mean."""
+    model = batch.model
+    names = list(model.params)
+    P = len(names)
+    est = np.asarray(estimates, dtype=np.float64).reshape(-1, P)
+    if len(est) != len(batch):
+        raise ValueError("observed_information_batch: one estimate per histogram of the batch")
+    fix = [None] * P if fix is None else list(fix)
+    if len(fix) != P:
+        raise ValueError("observed_information_batch: `fix` must have one entry per parameter")
+    if not len(est):
+        return []
+    ll, grad, hess = batch.loglikelihood_hessian_pairs(np.arange(len(est)), est)
+    bounds = [tuple(b) for b in model.bounds]
+    return [_information(names, [float(v) for v in est[b]], bounds, fix, float(ll[b]), grad[b], hess[b]) for b in range(len(est))]
 
 
 def sandwich_covariance(model, estimate, fix=None, info=None):

@@ -40,8 +40,9 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
     `bootstrap`: the dict covest_amd.bootstrap.parametric_bootstrap returns; the record then carries
     bootstrap_replicates, bootstrap_failed and, per free parameter, bootstrap_bias_<param>, bootstrap_se_<param> and
     bootstrap_interval_<param> (the coverage's times sample_factor, like its neighbours), and
-    bootstrap_interval_genome_size where the bootstrap was given hist_orig.  They share the model's independence
-    assumption.  Without it the record is unchanged."""
+    bootstrap_interval_genome_size where the bootstrap was given hist_orig; and, only where the bootstrap was studentized
+    (it carries 't_intervals'), bootstrap_t_interval_<param> and bootstrap_t_interval_genome_size, scaled alike
+    (DESIGN.md 6x).  They share the model's independence assumption.  Without it the record is unchanged."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -124,9 +125,14 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
             interval = bootstrap['percentile_intervals'].get(name)
             if interval is not None:
                 record['bootstrap_interval_%s' % name] = [float(v * by) for v in interval]
+            t_interval = bootstrap.get('t_intervals', {}).get(name)
+            if t_interval is not None:
+                record['bootstrap_t_interval_%s' % name] = [float(v * by) for v in t_interval]
         size = bootstrap.get('genome_size')
         if size is not None and size.get('interval') is not None:
             record['bootstrap_interval_genome_size'] = [float(v) for v in size['interval']]
+        if size is not None and size.get('t_interval') is not None:
+            record['bootstrap_t_interval_genome_size'] = [float(v) for v in size['t_interval']]
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

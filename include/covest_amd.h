@@ -559,10 +559,25 @@ int covest_draw_histograms_device(int32_t device, int64_t m, const uint64_t *d_t
  *                           (+0.0 at such a key, and throughout where the clamp moved parameter k) -- and
  *                           out_tail[n][param_count + 1]: log(1 - sp_i), then -S_k / (1 - sp_i); all 0 where sp_i is
  *                           not < 1.  It does not depend on the histograms.
+ *   covest_batch_eval_cross_hess, covest_batch_eval_pairs_hess  the same two forms with the closed-form Hessian
+ *                           (DESIGN.md section 6x): per (histogram, point) R2 = 1 + P + P (P + 1) / 2 doubles
+ *                           (P = param_count: 6 for the basic model, 21 for repeats), [0] the log-likelihood, [1 + k] its
+ *                           gradient, [1 + P + pair(k, l)] the entry d_k d_l LL -- of LL, not of -LL -- for k <= l, row by
+ *                           row (pair(k, l) = k P - k (k - 1) / 2 + l - k); a row and a column of a parameter the clamp
+ *                           moved are 0, every entry behind the value NaN where the value is not finite.  The curvature
+ *                           of log p_j does not depend on the counts either:
+ *                             d_k d_l LL_b = sum_j h_bj c_kl(j) - tail_b [sp < 1] (S_kl / (1 - sp) + S_k S_l / (1 - sp)^2),
+ *                             c_kl(j) = d_k d_l p_j / p_j - r_k(j) r_l(j),   S_kl = sum_j d_k d_l p_j,
+ *                           so the table has R2 rows a point, written by the derivative kernel's walk at order 2
+ *                           (covest_eval_points_hess's arithmetic); value and gradient are that walk's.
+ *   covest_batch_score_table2  that table: out_rows[n][R2][n_keys] -- rows 0 .. P as covest_batch_score_table's, rows
+ *                           1 + P + pair(k, l) the c_kl (+0.0 at a key with p_ij <= 0, and throughout where the clamp
+ *                           moved k or l) -- and out_tail[n][R2]: the P + 1 coefficients above, then
+ *                           -(S_kl / (1 - sp_i) + S_k S_l / (1 - sp_i)^2); all 0 where sp_i is not < 1.
  * params is [n][param_count] as for covest_eval_points.  The table of log p is built for at most 256 MiB of points at
- * a time (the gradient's table holds param_count + 1 rows a point, so a chunk has that many times fewer points); the
- * chunking changes no value.  In covest_batch_info a gradient call counts points (not rows) as tabled and its requests
- * as pairs requests; the time fields cover its kernels.
+ * a time (the gradient's table holds param_count + 1 rows a point, the Hessian's R2, so a chunk has that many times fewer
+ * points); the chunking changes no value.  In covest_batch_info a gradient or Hessian call counts points (not rows) as
+ * tabled and its requests as pairs requests; the time fields cover its kernels.
  * A batch borrows its model: destroy the batch first.  Every call takes the model's lock and runs on the model's
  * device.  COVEST_E_INVALID: a NULL argument, a negative size, a count or tail that is negative, NaN or infinite, more
  * than 2^20 histograms, an index outside 0 .. n_hist - 1, a model without keys, and for covest_batch_draw what
@@ -581,6 +596,12 @@ int covest_batch_eval_pairs_grad(covest_batch *b, int64_t n, const int64_t *hist
     /* out: n x (P+1) */
 int covest_batch_score_table(covest_batch *b, int64_t n, const double *params, double *out_rows, double *out_tail);
     /* out_rows: n x (P+1) x n_keys as the device holds them; out_tail: n x (P+1) */
+int covest_batch_eval_cross_hess(covest_batch *b, int64_t n, const double *params, double *out);
+    /* out: B x n x R2; [..][0] the log-likelihood, [..][1+k] the gradient, [..][1+P+pair(k,l)] d_k d_l LL, k <= l */
+int covest_batch_eval_pairs_hess(covest_batch *b, int64_t n, const int64_t *hist_index, const double *params, double *out);
+    /* out: n x R2 */
+int covest_batch_score_table2(covest_batch *b, int64_t n, const double *params, double *out_rows, double *out_tail);
+    /* out_rows: n x R2 x n_keys as the device holds them; out_tail: n x R2 */
 int covest_batch_info(covest_batch *b, int64_t *out);
 void covest_batch_destroy(covest_batch *b);
 
