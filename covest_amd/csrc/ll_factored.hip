@@ -53,6 +53,7 @@
 #include <mutex>
 #include <type_traits>
 
+#include "band.h"
 #include "direct_point.h" // strict_pj_wave, for finish_point
 #include "handback.h"
 #include "fastmath.h"
@@ -151,13 +152,14 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     // from here (LDS, addressed by the unit's half) instead of selecting between two register sets per row.
     __shared__ __attribute__((aligned(16))) double2 rowc[2][kTileBins];
     __shared__ __attribute__((aligned(16))) double rows[NEED_SCAL ? 2 : 1][NEED_SCAL ? kTileBins : 2];
-    // {(1-q)^16, -, (1-q)^4, (1-q)^(-4 nsh)} of every slot with shared steps (tiles.h): wave-uniform, read back as LDS broadcasts
+    // {(1-q)^16, ln(1-q), (1-q)^4, (1-q)^(-4 nsh)} of every slot with shared steps (tiles.h): wave-uniform, read back as LDS broadcasts
     __shared__ __attribute__((aligned(16))) double rho_tab[PLAIN ? NW * MU * 4 : 4];
     __shared__ double lconst_s; // the constant the rows' scales add to every point's sum (tiles.h item_lconst)
+    __shared__ double band_ln[PLAIN ? kBandClasses : 1]; // ln of the error classes' rates, for the units' bands (band.h)
     static_assert(MU == kMaxUnits, "the LDS layout counts kMaxUnits slots a wave");
     // (+ 15 bytes of alignment in front of each array at most)
-    static_assert(sizeof(log_tab) + sizeof(sub_rec) + sizeof(rowc) + sizeof(rows) + sizeof(rho_tab) + sizeof(lconst_s) + 6 * 15 <=
-                      kFactoredStaticLds, "the planners' LDS budget (tiles.h) must hold the kernel's static LDS");
+    static_assert(sizeof(log_tab) + sizeof(sub_rec) + sizeof(rowc) + sizeof(rows) + sizeof(rho_tab) + sizeof(lconst_s) +
+                          sizeof(band_ln) + 7 * 15 <= kFactoredStaticLds, "the planners' LDS budget (tiles.h) must hold the kernel's static LDS");
 
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
@@ -249,6 +251,11 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
 #pragma unroll
     for (int s = 0; s < 8; ++s)
         lam[s] = Gs[lay.rates() + 8 * my_pass + s];
+    // (the logarithms of the rates, for the units' bands below: the kernel's own logarithm, once the table is there; read
+    // behind the next barrier.  A class without a rate gets a finite number where band.h expects -inf: the class then
+    // counts for more than it is worth, never for less)
+    if (PLAIN && tid < kBandClasses)
+        band_ln[tid] = fast_log(Gs[lay.rates() + tid], log_tab);
     double n_total = -1.0;
     if (n_pass > 1) { // the mixture weights a_os are normalised over ALL classes: covest/models.py:225-233
         n_total = 0.0;
@@ -372,6 +379,48 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
         m_first |= (qslot[k] >= 0 && !cont[k]) ? 1u << k : 0u;
         m_cont |= cont[k] ? 1u << k : 0u;
         m_sh |= nsh[k] > 0 ? 1u << k : 0u;
+    }
+    // THE BANDS (band.h) of this wave's slots, lane = item of the walk (the last lane: every item from the 64th on, as
+    // one range of keys): the MFMA steps from step_hi on add less than 2^-64 of P_j for every key of the item and every
+    // column of the unit -- at a large key the low copy numbers' Poissons are all that is left of a row, and the
+    // contraction need not run on to the unit's cut-off.  Only units with kBandMinShared shared steps or more have a band
+    // (one q a tile: the weights are geometric); a byte a slot in two registers, 255: not banded.  The item's entry is
+    // read with one lane read a register and tile; nothing else is held across the walk.
+    unsigned band_w0 = ~0u, band_w1 = ~0u;
+    // Only a wave that builds nothing makes bands: it waits for the builders' first item anyway (15 k cycles on C3, by the
+    // stage stamps of the diagnostic build), while in a builder wave the same few thousand cycles stand in front of
+    // every wave's first barrier -- and in the late key tiles, where a band is narrow, the builders are not the waves
+    // the barrier waits for.
+    bool wave_bands = false; // (wave-uniform) a unit of this wave's is long enough for a band
+#pragma unroll
+    for (int k = 0; k < MU; ++k)
+        wave_bands = wave_bands || (PLAIN && !wave_builds && nsh[k] >= kBandMinShared);
+    if (PLAIN && wave_bands) {
+        // (the kernel's own logarithm, 2e-16 absolute, and the hardware's reciprocal with one Newton step: band.h, roundings)
+        struct {
+            const double *tab;
+            __device__ double ln(double x) const { return fast_log(x, tab); }
+            __device__ double rcp(double x) const
+            {
+                const double r = __builtin_amdgcn_rcp(x);
+                return fma(fma(-x, r, 1.0), r, r);
+            }
+        } const mth = {log_tab};
+        const int it = min(lane, t_end - 1);
+        const double key_first = tv.rec[TAIL ? tv.item_first[it] : it].k0;
+        const double key_last = (lane < kWave - 1 ? key_first : tv.rec[n_tiles - 1].k0) + (double)(kTileBins - 1);
+        const BandTile bt = band_tile(band_ln, m.ln_comb, key_first, key_last);
+#pragma unroll
+        for (int k = 0; k < MU; ++k) {
+            if (nsh[k] < kBandMinShared) // wave-uniform
+                continue;
+            const Band b = band_of_unit(mth, lam[0], rho_tab[4 * (wave * MU + k) + 1], 4 + 4 * nsh[k], nsh[k] + len[k], bt);
+            const unsigned hi = (unsigned)min(b.step_hi, 255);
+            if (k < 4)
+                band_w0 = (band_w0 & ~(255u << (8 * k))) | (hi << (8 * k));
+            else
+                band_w1 = (band_w1 & ~(255u << (8 * (k - 4)))) | (hi << (8 * (k - 4)));
+        }
     }
     // b_o of every slot's first (wfirst) and second (wrun, then advanced by (1-q)^4 per step) MFMA step:
     // an L2-resident host table.  The loads for tile t+1 are issued between tile t's MFMAs and its
@@ -755,6 +804,15 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
 #pragma unroll
             for (int k = 0; k < MU; ++k)
                 a0[k] = cur[a_off0[k]]; // (an idle slot reads a valid address and uses nothing)
+            // this item's bands (above): the slots' step_hi, a byte each.  (S x b, the last position of a grid with a
+            // tail, is a sum over every key: the full range)
+            unsigned bw0 = ~0u, bw1 = ~0u;
+            if (PLAIN && !sp_item) {
+                const int bl = min(__builtin_amdgcn_readfirstlane(t), kWave - 1);
+                bw0 = (unsigned)__builtin_amdgcn_readlane((int)band_w0, bl);
+                bw1 = (unsigned)__builtin_amdgcn_readlane((int)band_w1, bl);
+            }
+            auto band_hi = [&](int k) -> int { return (int)(((k < 4 ? bw0 >> (8 * k) : bw1 >> (8 * (k - 4)))) & 255u); };
             if (diag) { // (diagnostic builds: until the first fragments and the weights are there)
                 double sink = 0.0;
 #pragma unroll
@@ -783,6 +841,8 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                 // lanes and fetched back with v_readlane, a VECTOR instruction, every tile)
                 int nsh_k = nsh[k];
                 asm volatile("" : "+s"(nsh_k));
+                if (PLAIN) // the shared steps above the band are left out: the weights are relative to the FIRST shared step
+                    nsh_k = min(nsh_k, band_hi(k) - 1);
                 const int n4 = nsh_k >> 2, rem = nsh_k & 3;
                 // the top `rem` steps (m = n4) are the heads of chains 0 .. rem - 1
                 const double *top = g1 + 4 * (1 + 4 * n4);
@@ -835,28 +895,34 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
             if (!COVEST_SKIP_PHASE(plan, 2)) {
                 int a_off[MU]; // this lane's A fragments counted from the first step after the shared ones (per tile: 6 adds
                                // instead of 6 registers held through the other phases)
+                // lenb: of the steps after the shared ones a slot runs those below its band's edge -- none where the band ends
+                // at or below its last shared step.  (The loops stay correct with such entries among the sorted lengths, as
+                // with a dead unit's 0: slot k gets max(lenb[k..5]) steps, the suffix maximum, which is at most len[k]; a
+                // step beyond the band is only unnecessary.)
+                int lenb[MU];
 #pragma unroll
                 for (int k = 0; k < MU; ++k)
                 {
                     int nsh_k = nsh[k];
                     asm volatile("" : "+s"(nsh_k));
                     a_off[k] = a_off0[k] + 4 * nsh_k;
+                    lenb[k] = PLAIN ? min(len[k], max(band_hi(k) - nsh_k, 1)) : len[k];
                 }
                 // (measured and not kept, round 4: one address register a slot with the buffer's base folded in and two
                 // steps a trip, the second fragment an immediate offset away -- the compiler moves the induction to the
                 // scalar unit, six s_add a trip: 0.867-0.871 against 0.855-0.858 ms)
                 int i = 1;
-                for (; i < len[5]; ++i)
+                for (; i < lenb[5]; ++i)
                     contract_step<6, MU>(i, cur, a_off, cut, r4, wrun, acc);
-                for (; i < len[4]; ++i)
+                for (; i < lenb[4]; ++i)
                     contract_step<5, MU>(i, cur, a_off, cut, r4, wrun, acc);
-                for (; i < len[3]; ++i)
+                for (; i < lenb[3]; ++i)
                     contract_step<4, MU>(i, cur, a_off, cut, r4, wrun, acc);
-                for (; i < len[2]; ++i)
+                for (; i < lenb[2]; ++i)
                     contract_step<3, MU>(i, cur, a_off, cut, r4, wrun, acc);
-                for (; i < len[1]; ++i)
+                for (; i < lenb[1]; ++i)
                     contract_step<2, MU>(i, cur, a_off, cut, r4, wrun, acc);
-                for (; i < len[0]; ++i)
+                for (; i < lenb[0]; ++i)
                     contract_step<1, MU>(i, cur, a_off, cut, r4, wrun, acc);
             }
             // pieces of one unit: add the accumulators into the unit's first slot.  A BRANCH per slot (the empty asm

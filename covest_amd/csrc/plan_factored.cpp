@@ -473,6 +473,7 @@ void slot_weights(size_t at, const PartSpec &ps, const PartColumns &pc, const Un
             // makes from the weight it holds anyway -- b_o of the first step AFTER them -- times (1-q)^(-4 nsh)
             // (<= 1e10: the cut-off is where b_o reaches 1e-8)
             unit_rho[4 * at] = pw_16;
+            unit_rho[4 * at + 1] = std::log(base); // ln(1-q): the unit's band is made from it (band.h)
             unit_rho[4 * at + 2] = pw_4;
             unit_rho[4 * at + 3] = pw_inv;
             // the first step after the shared ones: o = 5 + 4 nsh .. 8 + 4 nsh

@@ -140,7 +140,9 @@ inline __host__ __device__ TileView tile_view_from(int32_t nt, int32_t ni, const
 // on their number (no per-slot branches inside it).
 constexpr int kMaxUnits = 6;       // accumulator slots per wave
 constexpr int kHalfUnits = 3;      // (kept for the 256-thread capacity rule: 4 waves x 6 slots)
-constexpr int kBuildCost = 18;     // phase A of one wave and key tile, in MFMA-step equivalents (tuned on C3; 36 before round 3 took the scales and the scalar-load stalls out of phase A)
+constexpr int kBuildCost = 27;     // phase A of one wave and key tile, in MFMA-step equivalents (tuned on C3; 36 before round 3 took the scales and the scalar-load
+                                   //   stalls out of phase A, 18 until the waves that build nothing cut their units to the band, band.h: what moves to them
+                                   //   is cut too -- swept again, profiles/band_charge_sweep.txt: 0.625 ms at 18, 0.613 at 22 and 24, 0.600 at 27, 0.606 at 30)
 constexpr int kBuildCostLowKeys = 24; // ... of a histogram whose tiles are (nearly) all at low keys, where every error class is
                                    //   live in every tile -- what the reference's trimming leaves (380 keys of H10k_rep): swept on it in
                                    //   round 5, 0.4015 against 0.4103 ms at 18 (profiles/r05_factored_builder_charge_sweep.txt); C3 itself,
@@ -183,7 +185,7 @@ struct FactoredPlan {
     const int32_t *unit_nsh;       // SHARED steps of the slot's unit (0: none), see below
     const int32_t *unit_pair;      // first slot of a half-0 unit: wave * kMaxUnits + slot (inside the workgroup) of the first
                                    //   slot of the same q-tile's half-1 unit (-1: none); the kernel's last step adds the two
-    const double *unit_rho;        // [slots][4] units with unit_nsh > 0: {(1-q)^16, unused, (1-q)^4, (1-q)^(-4 nsh)} of the unit's q-tile
+    const double *unit_rho;        // [slots][4] units with unit_nsh > 0: {(1-q)^16, ln(1-q), (1-q)^4, (1-q)^(-4 nsh)} of the unit's q-tile
     const double *piece_w;         // [slots][64 lanes][2] b_o at the piece's first step (masked by the column's
                                    //   cut-off) and at its second (o = 1 + 4 step + lane/16, column lane%16), libm
                                    //   pow on the host; units with unit_nsh > 0: second = the first step AFTER the
