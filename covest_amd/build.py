@@ -6,6 +6,7 @@ the built .so is git-ignored but travels to the GPU box with the repo snapshot.
     python -m covest_amd.build [--force]
 """
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -15,19 +16,22 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libcovest_amd.so")
 # (source, extra flags, object name).  K-factored is compiled once per template variant, each into a translation unit
-# of its own (csrc/ll_factored.hip, COVEST_FACTORED_VARIANT): the HIP runtime loads a translation unit's code object
-# when one of its kernels is first launched, so a process only pays for the variants it uses.
+# of its own (csrc/ll_factored.hip, COVEST_FACTORED_VARIANT = the row of csrc/factored_launch.h's table): the HIP runtime
+# loads a translation unit's code object when one of its kernels is first launched, so a process only pays for the
+# variants it uses.  The finishing kernels and the dispatcher: csrc/ll_factored_launch.hip.
 SOURCES = [("host_common.cpp", (), "host_common"), ("tiles_host.cpp", (), "tiles_host"), ("plan_factored.cpp", (), "plan_factored"),
            ("abi_model.cpp", (), "abi_model"), ("abi_grid.cpp", (), "abi_grid"), ("kmer_host.cpp", (), "kmer_host"),
            ("thin_host.cpp", (), "thin_host"), ("abi_tp.cpp", (), "abi_tp"), ("reads_io.cpp", (), "reads_io"), ("ll_direct.hip", (), "ll_direct"),
-           ("ll_basic.hip", (), "ll_basic"), ("ll_factored.hip", (), "ll_factored"), ("argmin.hip", (), "argmin"), ("ll_fix.hip", (), "ll_fix"), ("axis_min.hip", (), "axis_min"), ("ll_deriv.hip", (), "ll_deriv"),
+           ("ll_basic.hip", (), "ll_basic"), ("ll_factored_launch.hip", (), "ll_factored_launch"), ("argmin.hip", (), "argmin"), ("ll_fix.hip", (), "ll_fix"), ("axis_min.hip", (), "axis_min"), ("ll_deriv.hip", (), "ll_deriv"),
            ("kmer_count.hip", (), "kmer_count"), ("kmer_wide.hip", (), "kmer_wide"), ("kmer_bulk.hip", (), "kmer_bulk"), ("thin_hist.hip", (), "thin_hist"),
            ("tp_eval.hip", (), "tp_eval"), ("abi_sim.cpp", (), "abi_sim"), ("sim_reads.hip", (), "sim_reads"),
            ("abi_sample.cpp", (), "abi_sample"), ("sample_reads.hip", (), "sample_reads"),
            ("abi_repeat.cpp", (), "abi_repeat"), ("sim_repeats.hip", (), "sim_repeats"),
            ("abi_draw.cpp", (), "abi_draw"), ("draw_hist.hip", (), "draw_hist"),
            ("abi_batch.cpp", (), "abi_batch"), ("ll_batch.hip", (), "ll_batch")]
-SOURCES += [("ll_factored.hip", ("-DCOVEST_FACTORED_VARIANT=%d" % v,), "ll_factored_v%d" % v) for v in range(10)]
+# (the rows of the table, from the one place that counts them)
+FACTORED_VARIANTS = int(re.search(r"kFactoredVariants = (\d+)", open(os.path.join(CSRC, "kernels.h")).read()).group(1))
+SOURCES += [("ll_factored.hip", ("-DCOVEST_FACTORED_VARIANT=%d" % v,), "ll_factored_v%d" % v) for v in range(FACTORED_VARIANTS)]
 SOURCES += [("ll_basic.hip", ("-DCOVEST_BASIC_VARIANT=%d" % v,), "ll_basic_v%d" % v) for v in range(8)]
 MAX_PARALLEL = 8
 ARCH = "gfx950"

@@ -120,4 +120,21 @@ COVEST_HD inline Band band_of_unit(const Math &mth, double rate0, double ln_1mq,
     return Band{0, step_hi};
 }
 
+// The upper edges (step_hi) of a wave's six slots as the kernel keeps them: a byte a slot in two registers, 255: not
+// banded (the full range; an edge of 255 steps or more is as good as none: a unit has 128 steps at most).  In the
+// kernel lane t holds the bytes of item t of the walk: set per lane in the prologue, one lane read a register and item.
+struct BandBytes {
+    static constexpr int kSlots = 6, kNone = 255;
+    unsigned w0 = ~0u, w1 = ~0u; // slots 0 .. 3, slots 4 and 5
+    COVEST_HD void set(int k, int step_hi)
+    {
+        const unsigned hi = (unsigned)(step_hi < kNone ? step_hi : kNone);
+        if (k < 4)
+            w0 = (w0 & ~(255u << (8 * k))) | (hi << (8 * k));
+        else
+            w1 = (w1 & ~(255u << (8 * (k - 4)))) | (hi << (8 * (k - 4)));
+    }
+    COVEST_HD int get(int k) const { return (int)(((k < 4 ? w0 >> (8 * k) : w1 >> (8 * (k - 4)))) & 255u); }
+};
+
 } // namespace covest

@@ -1,6 +1,7 @@
 // host_common.cpp -- error state, device selection, the ln j! table and threshold_o (host arithmetic: libm,
 // as CPython) of libcovest_amd.so.  Compiled with hipcc, links only the HIP runtime.  There is no CPU compute path in
 // this library: every likelihood value comes out of a gfx950 kernel.
+#include "factored_launch.h" // K-factored's variants, for covest_compiled_variants
 #include "host.h"
 
 using namespace covest;
@@ -411,7 +412,8 @@ int64_t covest_compiled_variants(char *buf, int64_t cap)
             t += '\n';
         }
     };
-    add(kFactoredVariantNames, kFactoredVariants);
+    for (const FactoredVariant &v : kFactoredVariantTable)
+        add(&v.name, 1);
     add(kFactoredFinishNames, 2);
     add(kBasicVariantNames, kBasicVariants);
     add(kFixVariantNames, kFixVariants);

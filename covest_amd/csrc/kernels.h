@@ -16,7 +16,8 @@ namespace covest {
 // Host bookkeeping only.  A launcher notes the instantiation it picked and how many launches it took into the record
 // of the evaluation in progress on the calling thread (LaunchRecordScope; none: nothing is noted).  Nothing is read from
 // the device and nothing waits for it.  The names come from the tables beside the instantiation lists (kVariantNames of
-// ll_factored.hip, ll_basic.hip, ll_fix.hip, argmin.hip and ll_deriv.hip); covest_compiled_variants lists those tables.
+// ll_basic.hip, ll_fix.hip, argmin.hip and ll_deriv.hip; K-factored's: the table of factored_launch.h); covest_compiled_variants
+// lists those tables.
 struct LaunchRecord {
     struct Entry {
         const char *name;
@@ -42,8 +43,8 @@ struct LaunchRecordScope { // notes go to `r` (cleared; append: kept and added t
 };
 // The instantiations linked in, by family; a launcher records kXxxVariantNames[its index].
 constexpr int kFactoredVariants = 10, kBasicVariants = 8, kFixVariants = 6, kArgminVariants = 3, kDerivVariants = 7;
-extern const char *const kFactoredVariantNames[kFactoredVariants]; // ll_factored.hip
-extern const char *const kFactoredFinishNames[2];                   // ll_factored.hip: ll_finish_dense, ll_finish_partials
+// (K-factored's names: factored_launch.h kFactoredVariantTable, kFactoredVariants rows -- covest_amd/build.py reads the figure above)
+extern const char *const kFactoredFinishNames[2];                   // ll_factored_launch.hip: ll_finish_dense, ll_finish_partials
 extern const char *const kBasicVariantNames[kBasicVariants];       // ll_basic.hip
 extern const char *const kFixVariantNames[kFixVariants];           // ll_fix.hip
 extern const char *const kArgminVariantNames[kArgminVariants];     // argmin.hip

@@ -47,16 +47,30 @@
 //
 // Reference restated: covest/models.py:100-107 (LL), :211-242 (p_j), over
 // covest/grid.py:59-64 (the grid map).
+//
+// This file is the kernel and its launcher, compiled once per variant (-DCOVEST_FACTORED_VARIANT=v, the row of
+// factored_launch.h's table); the finishing kernels and the dispatcher are ll_factored_launch.hip.  The stages that
+// stand on their own are in headers (which, and why the others are still written out in the kernel):
+//   factored_build.h     phase A: the walk of a tile, the tile's entry and dispatch, an item
+//   factored_contract.h  phase B: an MFMA step, the shared steps' sum, the pieces' adding, an item's bands (band.h BandBytes)
+//   factored_log.h       phase C: the chunks' shares of p_j on their way to HBM
+//   factored_epilogue.h  the result entries' unit-table words
+//   factored_diag.h      the stamps of the diagnostic build (empty otherwise)
+//   factored_state.h     the layout made afresh, the rows' scale
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <mutex>
-#include <type_traits>
 
 #include "band.h"
-#include "direct_point.h" // strict_pj_wave, for finish_point
-#include "handback.h"
+#include "factored_build.h"
+#include "factored_contract.h"
+#include "factored_diag.h"
+#include "factored_epilogue.h"
+#include "factored_launch.h"
+#include "factored_log.h"
 #include "fastmath.h"
+#include "handback.h"
 #include "kernels.h"
 #include "point_fetch.h"
 #include "streams.h"
@@ -66,38 +80,7 @@ namespace covest {
 
 namespace {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-// The chunks' shares of p_j (list modes 2 and 3, tiles.h) travel through HBM TIMES 2^128: p_j <= 2.5, so nothing
-// overflows, and a p_j below half a grid step -- which the reference's roundings may still keep alive, handback.h
-// kZeroSteps -- does not flush to 0 on the way: finish_point decides on the exact value.
-constexpr double kShareScale = 0x1p128;
-
-
-// One MFMA step of the first N accumulator slots of a wave (they are sorted by length, so the active
-// slots are always a prefix): all A fragments first -- N independent LDS reads in flight -- then per
-// slot the weight b_o (advanced by (1-q)^4, cut off at o >= T: models.py:198-206,239) and the MFMA.
-// Straight-line code: no per-slot branch separates the reads from their MFMAs.
-// (Measured and not kept, round 3: the fragments of step i + 1 read during step i -- 0.896 against 0.864 ms: the
-// registers of the second set are spilled elsewhere.)
-template <int N, int MU>
-__device__ __forceinline__ void contract_step(int i, const double *cur, const int (&a_off)[MU], const int (&cut)[MU],
-                                              const double (&r4)[MU], double (&wrun)[MU], d4 (&acc)[MU])
-{
-    double a[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        a[k] = cur[a_off[k] + 4 * i];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const double w = (i < cut[k]) ? wrun[k] : 0.0; // this lane's o has reached T: models.py:239
-        wrun[k] *= r4[k];
-        acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[k], w, acc[k], 0, 0, 0);
-    }
-}
-
-// PLAIN: the shape every dense grid of the reference's own set-up has -- list_mode 0, at most 8 error classes (one
-// lane per copy number) -- compiled on its own so that the other modes' code costs it no registers.
+// (PLAIN, LDC: factored_launch.h, the table of variants.)
 //
 // Round 3: the rows of a plain item stay UNSCALED in LDS and in the accumulators -- G' = the sum of the streams'
 // scaled terms (streams.h), P'_j = p_j / scal_j -- because the per-key scale is the same for every copy number and
@@ -107,10 +90,6 @@ __device__ __forceinline__ void contract_step(int i, const double *cur, const in
 // right before their use: an exposed scalar-load latency every two keys); the 2^-SC disappears into the exponent
 // arithmetic of the log (fastmath.h fast_log_bits_n).  Only where p_j itself is needed -- sp_j with a tail, the
 // chunks' shares of p_j in list modes 2 and 3 -- a row is multiplied by its scale, read from LDS.
-// LDC: the row stride of G as a COMPILE-TIME constant (0: plan.ld) -- kLdWide = 290, the stride of every plain grid whose
-// largest threshold_o - 1 lies in 257 .. 288 (C3: 284): the 32 stores of a tile's walk and the fragments' offsets become
-// immediates (round 4).
-[[maybe_unused]] constexpr int kLdWide = 290;
 template <int NT, int HU, bool TAIL, bool PLAIN, int LDC = 0>
 __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const int32_t n_tiles, const int32_t n_items,
                                                          const double *__restrict__ tile_dbl,
@@ -119,10 +98,6 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                                                          double *__restrict__ out_ll, const SubList sub_list)
 {
     const TileView tv = tile_view_from(n_tiles, n_items, tile_dbl, tile_int);
-#ifdef COVEST_DIAG // (COVEST_FACTORED_DIAG=4: where a workgroup's time OUTSIDE the walk goes -- stamps at the stages' ends)
-    const long long dgx_0 = (long long)clock64();
-    long long dgx_1 = 0, dgx_2 = 0, dgx_3 = 0, dgx_4 = 0;
-#endif
     constexpr int NW = NT / kWave;
     constexpr int MU = 2 * HU; // accumulator slots per wave (6: the specialised step loops below assume it)
     static_assert(MU == 6, "contract loops are written for 6 slots");
@@ -164,6 +139,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+    Stamps stamps(plan, NW, wave); // (diagnostic builds only: factored_diag.h)
     const double p_clamp = plan.p_clamp; // handback.h
     const double zero_frac = kZeroSteps * (kGridStep / p_clamp); // handback.h kZeroSteps, in units of p_clamp
     const int list_mode = PLAIN ? 0 : plan.list_mode;
@@ -234,9 +210,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
             lconst_s = PLAIN ? lc - kLogRawBias<kScaleBits> * tv.suf_h[0] : lc;
     }
     __syncthreads();
-#ifdef COVEST_DIAG
-    dgx_1 = (long long)clock64(); // the table, the point, the classes' rates, the items' constants; the first barrier
-#endif
+    stamps.stage(Stamps::kFetched);
 
     // ---- phase-A state: lane = (pass, copy number): column pass * pass_stride + (o - o_base - 1) of G ----
     // With more than 8 error classes a copy number's classes are dealt to n_pass lanes, 8 each, whose columns the
@@ -289,9 +263,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
             st.an.set(s, 0.0, -INFINITY);
         }
     }
-#ifdef COVEST_DIAG
-    dgx_2 = (long long)clock64(); // the streams' constants (builder waves)
-#endif
+    stamps.stage(Stamps::kStreams);
     const bool lane_in_row = tid < LD - 2; // columns of G that exist (waves past them build nothing)
     if (tid < FactoredLds::kSlack)
         Gs[lay.slack() + tid] = 0.0; // the slack behind the buffers
@@ -386,7 +358,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     // contraction need not run on to the unit's cut-off.  Only units with kBandMinShared shared steps or more have a band
     // (one q a tile: the weights are geometric); a byte a slot in two registers, 255: not banded.  The item's entry is
     // read with one lane read a register and tile; nothing else is held across the walk.
-    unsigned band_w0 = ~0u, band_w1 = ~0u;
+    BandBytes bands; // (band.h)
     // Only a wave that builds nothing makes bands: it waits for the builders' first item anyway (15 k cycles on C3, by the
     // stage stamps of the diagnostic build), while in a builder wave the same few thousand cycles stand in front of
     // every wave's first barrier -- and in the late key tiles, where a band is narrow, the builders are not the waves
@@ -415,11 +387,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
             if (nsh[k] < kBandMinShared) // wave-uniform
                 continue;
             const Band b = band_of_unit(mth, lam[0], rho_tab[4 * (wave * MU + k) + 1], 4 + 4 * nsh[k], nsh[k] + len[k], bt);
-            const unsigned hi = (unsigned)min(b.step_hi, 255);
-            if (k < 4)
-                band_w0 = (band_w0 & ~(255u << (8 * k))) | (hi << (8 * k));
-            else
-                band_w1 = (band_w1 & ~(255u << (8 * (k - 4)))) | (hi << (8 * (k - 4)));
+            bands.set(k, b.step_hi);
         }
     }
     // b_o of every slot's first (wfirst) and second (wrun, then advanced by (1-q)^4 per step) MFMA step:
@@ -441,278 +409,16 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     // a finite number: the columns concerned are found from the weights themselves -- AFTER the walk (round 4: found
     // here and kept, the six masks held twelve scalar registers through the whole kernel, which spills them).
 
-    // ================= phase A: G'[key][o] of key tile t into `dst` =================
-    // in-kernel stamps (diagnostic builds only): cycles per wave in build / contract / log / barrier
-    long long dg_a = 0, dg_b = 0, dg_b0 = 0, dg_c = 0, dg_w = 0, dg_t0 = 0, dg_zero = 0, dg_enter = 0, dg_first = 0;
-#ifdef COVEST_DIAG
-    const bool diag = plan.diag != nullptr;
-#else
-    constexpr bool diag = false; // (the stamps exist in diagnostic builds only: tiles.h)
-#endif
-    // the 32 keys of a full tile with the streams 0 .. N-1 (the others are zero in every lane of the wave).  One
-    // region under the row mask, straight-line inside: the sums go to LDS as they stand (no scale, see above)
-    // SPO: returns sum_b u_b 2^SC of this lane's copy number over the tile's 32 keys (u_b: the true terms' sum at key
-    // b, streams.h) WITHOUT the keys' 32 scales: with  W_b = (u_0 + .. + u_b) / scal_b,  scal_(b-1) / scal_b = k0 + b
-    // (tiles.h) gives
-    //     W_b = W_(b-1) (k0 + b) + g_b,          g_b = the streams' sum at key b, what goes to LDS anyway,
-    // a fused multiply-add and an add a key on a counter that holds the key as a double (exact: keys <= 16384), and the
-    // tile's sum is W_31 scal_31 = W_31 renorm 2^-SC.  W stays inside the range the streams' own terms are scaled for
-    // (partial sums <= 2.5: at most 2.5 x 2^540 x 1e140).  No scalar is fetched in the walk (the tile's 32 scales
-    // through scalar registers cost the TAIL variants 45 more spilled scalars and an exposed scalar-cache latency a
-    // half).  Tiles with a FILLER key (a gap of the histogram: its scale is 0, it must add nothing) and short tiles
-    // take the key-by-key path of build_tile with the scales.
-    auto walk_tile = [&](auto n_tag, double *colp, double renorm, double k0) __attribute__((always_inline)) -> double {
-        constexpr int N = decltype(n_tag)::value;
-        if (!lane_in_row)
-            return 0.0; // (lanes past the row hold no copy number: nothing of theirs is ever read)
-        // squared rates (the streams advance two keys per step, streams.h step2): N multiplies per tile
-        // rather than 16 registers held through phases B and C -- the empty asm keeps the compiler from
-        // hoisting them back out of the tile loop (it would spill them)
-        double xx[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            double xs = st.x[s];
-            if (s < N) {
-                asm volatile("" : "+v"(xs));
-                xx[s] = xs * xs;
-            } else {
-                xx[s] = 0.0;
-            }
-        }
-        double *row = colp; // (walked row by row: one vector add a store, no scalar multiply by the row's number)
-        double tsum = 0.0;
-        if (SPO) {
-            double kk = k0; // the key of row b
-#pragma unroll
-            for (int b = 0; b < kTileBins; b += 2) {
-                double g1, g2;
-                st.template step2n<N>(xx, g1, g2);
-                row[0] = g1;
-                row[LD] = g2;
-                row += 2 * LD;
-                tsum = fma(tsum, kk, g1);
-                kk += 1.0;
-                tsum = fma(tsum, kk, g2);
-                kk += 1.0;
-            }
-            tsum *= renorm;
-        } else {
-#pragma unroll
-            for (int b = 0; b < kTileBins; b += 2) {
-                double g1, g2;
-                st.template step2n<N>(xx, g1, g2);
-                row[0] = g1;
-                row[LD] = g2;
-                row += 2 * LD;
-            }
-        }
-        st.template leave_tile_n<N>(renorm);
-        return tsum;
-    };
-    auto build_tile = [&](int t, bool seg_start, double *dst) __attribute__((always_inline)) -> double {
-        if (COVEST_SKIP_PHASE(plan, 1))
-            return 0.0;
-        const TileRec rc = tv.rec[t]; // (the tile's constants: one scalar load of one cache line, tiles.h)
-        const double k0 = rc.k0;
-        const int nb = rc.nb;
-        // n_live: streams above it are zero in every lane of this wave (streams.h) -- most of them, for most tiles.
-        // (Measured and not kept, round 5: the entry compiled for one and for two classes as well and picked by `gone` --
-        // C3 0.671 against 0.661 ms, the trimmed histogram with a tail 0.395 against 0.396:
-        // profiles/r05_c3_ab_entry_by_live_classes_not_kept.txt.  The gone classes' tests are scalar and cost little;
-        // three copies of the entry cost the instruction cache more.)
-        const int n_live = st.enter_tile(k0 - 1.0, k0 + (double)(nb - 1), rc.lgam_prev, rc.lgam_last,
-                                         rc.run_start != 0 || seg_start); // (a key segment starts like a run: every stream anchored)
-        if (diag) { // (diagnostic builds: entering the tile apart from walking it)
-            const long long now__ = (long long)clock64();
-            dg_enter += now__ - dg_t0;
-            dg_t0 = now__;
-        }
-        double *colp = dst + (lane_in_row ? tid : 0);
-        const double *scal = tv.scal + (int64_t)t * kTileBins;
-        if (nb == kTileBins && !(SPO && rc.has_filler != 0)) { // the common case: straight-line code
-            if (n_live > 4)
-                return walk_tile(std::integral_constant<int, 8>{}, colp, rc.renorm, k0);
-            if (n_live > 2)
-                return walk_tile(std::integral_constant<int, 4>{}, colp, rc.renorm, k0);
-            if (n_live == 2)
-                return walk_tile(std::integral_constant<int, 2>{}, colp, rc.renorm, k0);
-            if (n_live == 1)
-                return walk_tile(std::integral_constant<int, 1>{}, colp, rc.renorm, k0);
-            if (lane_in_row) { // nothing is on: G = 0 for this wave's copy numbers
-                if (diag)
-                    dg_zero += 1;
-#pragma unroll
-                for (int b = 0; b < kTileBins; ++b)
-                    colp[b * LD] = 0.0;
-            }
-            return 0.0;
-        }
-        double tsum = 0.0;
-        for (int b = 0; b < kTileBins; ++b) { // (rows past the tile's keys: 0 -- they carry no count and no scale)
-            const double g = b < nb ? st.step() : 0.0;
-            if (SPO && b < nb)
-                tsum = fma(g, scal[b], tsum);
-            if (lane_in_row)
-                colp[b * LD] = g;
-        }
-        st.leave_tile(rc.renorm);
-        return tsum * 0x1p476; // (tv.scal carries 2^(kBasicShift - SC); S[o] is kept times 2^SC: exact)
-    };
-    // The same walk over a tile WITHOUT counts (tail != 0 only): sum_j G[o][j] over its keys stays in a register
-    // -- 32 terms of one sign added plainly, the compensated accumulator of phase C gets their contraction --
-    // and is returned instead of 32 stores.  These rows ARE scaled (a sum over keys needs every key's own scale).
-    auto sum_tile = [&](auto n_tag, const double *scal_ptr, double scal_or_k0, double renorm) __attribute__((always_inline)) -> double {
-        constexpr int N = decltype(n_tag)::value; // the live streams, as in walk_tile
-        double xx[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            double xs = st.x[s];
-            if (s < N) {
-                asm volatile("" : "+v"(xs));
-                xx[s] = xs * xs;
-            } else {
-                xx[s] = 0.0;
-            }
-        }
-        double gsum = 0.0;
-        if (SPO) { // (the W recurrence of walk_tile: no scales; `scal` is the tile's first key here, as a double)
-            double kk = scal_or_k0;
-#pragma unroll
-            for (int b = 0; b < kTileBins; b += 2) {
-                double g1, g2;
-                st.template step2n<N>(xx, g1, g2);
-                gsum = fma(gsum, kk, g1);
-                kk += 1.0;
-                gsum = fma(gsum, kk, g2);
-                kk += 1.0;
-            }
-            st.template leave_tile_n<N>(renorm);
-            return gsum * renorm;
-        }
-        const double *scal = SPO ? nullptr : scal_ptr;
-        // two halves of 16 keys, each half's scales fetched into scalar registers up front (one s_load_dwordx16 pair,
-        // as K-basic does): fetched pair by pair right before their use, every second key waited for the scalar cache
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            double sc[16];
-#pragma unroll
-            for (int b = 0; b < 16; ++b)
-                sc[b] = scal[16 * half + b];
-            asm volatile("" ::: "memory"); // (keeps the loads above the half's arithmetic)
-#pragma unroll
-            for (int b = 0; b < 16; b += 2) {
-                double g1, g2;
-                st.template step2n<N>(xx, g1, g2);
-                gsum = fma(g1, sc[b], gsum);
-                gsum = fma(g2, sc[b + 1], gsum);
-            }
-        }
-        st.template leave_tile_n<N>(renorm);
-        return gsum * (1.0 / kBasicScale); // (tv.scal carries 2^kBasicShift, tiles.h)
-    };
-    auto build_tile_sum = [&](int t, bool seg_start) __attribute__((always_inline)) -> double {
-        const TileRec rc = tv.rec[t];
-        const double k0 = rc.k0;
-        const int nb = rc.nb;
-        // (SPO: the tile only enters S[o] -- streams.h enter_sum_tile: a stream is on where it matters to a sum)
-        const int n_live = SPO ? st.enter_sum_tile(k0 - 1.0, k0 + (double)(nb - 1), rc.lgam_prev, rc.lgam_last,
-                                                   rc.run_start != 0 || seg_start)
-                               : st.enter_tile(k0 - 1.0, k0 + (double)(nb - 1), rc.lgam_prev, rc.lgam_last,
-                                               rc.run_start != 0 || seg_start);
-        const double *scal = tv.scal + (int64_t)t * kTileBins;
-        if (nb == kTileBins && !(SPO && rc.has_filler != 0)) { // (the count-less tiles of a histogram's tail are full ones: the live streams only)
-            if (n_live > 2)
-                return sum_tile(std::integral_constant<int, 8>{}, scal, k0, rc.renorm);
-            if (n_live == 2)
-                return sum_tile(std::integral_constant<int, 2>{}, scal, k0, rc.renorm);
-            if (n_live == 1)
-                return sum_tile(std::integral_constant<int, 1>{}, scal, k0, rc.renorm);
-            return 0.0; // nothing is on
-        }
-        double gsum = 0.0;
-        for (int b = 0; b < nb; ++b)
-            gsum = fma(st.step(), scal[b], gsum);
-        st.leave_tile(rc.renorm);
-        return SPO ? gsum * 0x1p476 : gsum * (1.0 / kBasicScale); // (SPO: S[o] is kept times 2^SC)
-    };
-    // One item into `dst`: a plain tile, or (TAIL) the per-tile sums of up to 32 count-less tiles as its rows.
+    // ================= phase A (factored_build.h): G'[key][o] of an item into a buffer =================
     bool resync = false; // (SPO, wave-uniform) tiles were skipped: the next one walked anchors every stream afresh
-    auto build_item = [&](int it, bool seg_start, double *dst) __attribute__((always_inline)) {
-        const int first = TAIL ? __builtin_amdgcn_readfirstlane(tv.item_first[it]) : it;
-        if (TAIL && tv.item_sum[it] != 0) {
-            if (COVEST_SKIP_PHASE(plan, 1))
-                return;
-            const int n = __builtin_amdgcn_readfirstlane(tv.item_ntiles[it]);
-            if (SPO) { // the tiles without a count only enter S[o]: nothing is stored, nothing contracted
-                // The whole item -- up to 32 tiles, 1024 keys -- at a glance first: a stream's log-term is concave in the
-                // key, so where the item does not hold its mode its largest value over the item is at an end.  If that is
-                // below what a sum can hold (streams.h kSumWindowLn) for every stream of every lane of this wave, nothing
-                // of the item reaches S[o]: it is skipped for the price of two multiply-adds a stream, where entering
-                // each of its tiles in turn costs a thousand cycles a tile -- the long count-less stretch of a 10 000-key
-                // histogram is mostly such items (a wave's copy numbers have their mass within a few hundred keys).
-                // The streams are anchored afresh at the next tile that is walked (resync), as at the start of a run.
-                if (!seg_start) {
-                    const int tl = first + n - 1;
-                    const TileRec ra = tv.rec[first], rb = tv.rec[tl];
-                    const double ka = ra.k0 - 1.0, kb = rb.k0 + (double)(rb.nb - 1);
-                    const double lga = ra.lgam_prev, lgb = rb.lgam_last;
-                    bool matters = false;
-#pragma unroll
-                    for (int s = 0; s < 8; ++s) {
-                        if ((st.gone >> s) & 1u)
-                            continue; // (wave-uniform)
-                        const double lx = st.an.lx(s), c = st.an.c(s);
-                        const double top = fmax(fma(ka, lx, c - lga), fma(kb, lx, c - lgb));
-                        matters = matters || !(top < StreamSet<8>::kSumWindowLn) || (st.x[s] >= ka - 1.0 && st.x[s] <= kb + 1.0);
-                    }
-                    if (!__any(matters)) { // wave-uniform
-#pragma unroll
-                        for (int s = 0; s < 8; ++s)
-                            st.v[s] = 0.0;
-                        resync = true;
-                        return;
-                    }
-                }
-                for (int r = 0; r < n; ++r) {
-                    // (every stream of this wave's copy numbers has GONE -- off in all lanes, outside the window, past its
-                    // mode, streams.h: exact zeros from here on.  The far end of a long histogram: a wave of small copy
-                    // numbers is done with H10k_rep's 10 000 keys after the first two thousand)
-                    if (st.gone == 0xFFu && !(seg_start && r == 0))
-                        break;
-                    so.add(build_tile_sum(first + r, (seg_start && r == 0) || resync));
-                    resync = false;
-                }
-                return;
-            }
-            double *colp = dst + (lane_in_row ? tid : 0);
-            for (int r = 0; r < n; ++r) {
-                const double gsum = build_tile_sum(first + r, seg_start && r == 0);
-                if (lane_in_row)
-                    colp[r * LD] = gsum;
-            }
-            for (int r = n; r < kTileBins; ++r)
-                if (lane_in_row)
-                    colp[r * LD] = 0.0;
-        } else {
-            const double tsum = build_tile(first, seg_start || (SPO && resync), dst);
-            resync = false;
-            if (SPO)
-                so.add(tsum);
-        }
+    // (A local lambda forwards to the stage, here and below, and the stages take the kernel's variables one by one, where
+    // they are declared: called directly, or with the state gathered into a struct, the compiler numbers the streams'
+    // registers otherwise and fuses other products of a key's sum -- DESIGN.md 6z.)
+    auto build = [&](int it, bool seg_start, double *dst) __attribute__((always_inline)) {
+        build_item<TAIL, SPO>(tv, plan, st, so, resync, tid, LD, lane_in_row, stamps, it, seg_start, dst);
     };
-
-    // in-kernel stamps (diagnostic builds only): cycles per wave in build / contract / log / barrier
-#define STAMP(acc)                                    \
-    if (diag) {                                       \
-        const long long now__ = (long long)clock64(); \
-        acc += now__ - dg_t0;                         \
-        dg_t0 = now__;                                \
-    }
-    if (diag)
-        dg_t0 = (long long)clock64();
-#ifdef COVEST_DIAG
-    dgx_3 = (long long)clock64(); // the units' tables and first weights
-#endif
+    stamps.walk_begins();
+    stamps.stage(Stamps::kUnits);
 
     // With two buffers the builders fill item t+1 while every wave contracts item t: one barrier per item, and the
     // host's unit assignment charges the builders for phase A.  ONE loop for both set-ups (and ONE copy of phase A in
@@ -773,56 +479,34 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
             if (wave_builds) {
                 if (last_first && pb == t_begin + 1)
                     st.gone = 0u;
-                build_item(tile_at(pb), pb == t_begin || (last_first && (pb == t_begin + 1 || pb == last_item + 1)),
-                           Gs + lay.buf(pb));
+                build(tile_at(pb), pb == t_begin || (last_first && (pb == t_begin + 1 || pb == last_item + 1)), Gs + lay.buf(pb));
             }
         }
-        STAMP(dg_a)
+        stamps.lap(Stamps::kBuild);
         if (!dbuf)
             __syncthreads();
         const bool sp_item = SPO && p == t_end; // (wave-uniform) the last position: S x b
         if (p >= t_begin && !(SPO && !sp_item && tv.item_sum[tile_at(p)] != 0)) { // (SPO: a sum item was phase A only)
             const int t = tile_at(p); // the tile this interval contracts and logs
             const double *cur = Gs + lay.buf(p);
-            // ================= phase B: P' = G' x b on the matrix pipe =================
+            // ================= phase B (its steps: factored_contract.h): P' = G' x b on the matrix pipe =================
             d4 acc[MU];
             const d4 zero4 = (d4){0.0, 0.0, 0.0, 0.0};
             // Every slot's accumulator starts from its first MFMA (C = 0 costs nothing; zeroing 8 registers per slot
             // does); the step-0 fragments of all slots are read first, in flight together.
-            // A unit with shared steps (tiles.h) sums them on the vector unit:
-            //     sum_{i = 1 .. nsh} G'[key][1 + 4 i + kq] r^(i - 1),   r = (1-q)^4 (wave-uniform: the tile has one q)
-            // for this lane's key and o mod 4 -- weights RELATIVE TO THE FIRST shared step, so they only fall (the
-            // unscaled rows reach 1e297; with weights relative to the step AFTER the shared ones, up to 1e10, the sum
-            // could leave the range) -- as four Horner chains in r^4 (chain c: the steps i = 1 + c + 4 m) walked from
-            // the last step down, eight loads in flight per trip.  (Measured and not kept, round 3: the loads issued
-            // three groups ahead of their FMAs through a ring of four register sets, 0.934 against 0.872 ms -- the
-            // registers it takes are spilled elsewhere; and one fused pass over all the wave's units with one chain
-            // each, 1.08 ms.)  ONE MFMA brings the sum in: the four lanes of a key add up inside it,
-            // every column gets its own b_o of that first shared step, made from the weight the slot holds (b_o of
-            // the first step after them) times r^-nsh.
+            // A unit with shared steps (tiles.h) sums them on the vector unit (factored_contract.h shared_steps_sum) and
+            // ONE MFMA brings the sum in: the four lanes of a key add up inside it, every column gets its own b_o of
+            // that first shared step, made from the weight the slot holds (b_o of the first step after them) times r^-nsh.
             double a0[MU];
 #pragma unroll
             for (int k = 0; k < MU; ++k)
                 a0[k] = cur[a_off0[k]]; // (an idle slot reads a valid address and uses nothing)
             // this item's bands (above): the slots' step_hi, a byte each.  (S x b, the last position of a grid with a
             // tail, is a sum over every key: the full range)
-            unsigned bw0 = ~0u, bw1 = ~0u;
-            if (PLAIN && !sp_item) {
-                const int bl = min(__builtin_amdgcn_readfirstlane(t), kWave - 1);
-                bw0 = (unsigned)__builtin_amdgcn_readlane((int)band_w0, bl);
-                bw1 = (unsigned)__builtin_amdgcn_readlane((int)band_w1, bl);
-            }
-            auto band_hi = [&](int k) -> int { return (int)(((k < 4 ? bw0 >> (8 * k) : bw1 >> (8 * (k - 4)))) & 255u); };
-            if (diag) { // (diagnostic builds: until the first fragments and the weights are there)
-                double sink = 0.0;
-#pragma unroll
-                for (int k = 0; k < MU; ++k)
-                    sink += a0[k] + wfirst[k];
-                asm volatile("" ::"v"(sink));
-                const long long now__ = (long long)clock64();
-                dg_first += now__ - dg_t0;
-                dg_t0 = now__;
-            }
+            BandBytes item_bands;
+            if (PLAIN && !sp_item)
+                item_bands = bands_of_item(bands, t);
+            stamps.first_fragments(a0, wfirst);
 #pragma unroll
             for (int k = 0; k < MU; ++k) {
                 // (a dead unit, off_slots: its len[k] is 0 by now and its bit of m_sh cleared -- it takes the branch below
@@ -842,55 +526,13 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                 int nsh_k = nsh[k];
                 asm volatile("" : "+s"(nsh_k));
                 if (PLAIN) // the shared steps above the band are left out: the weights are relative to the FIRST shared step
-                    nsh_k = min(nsh_k, band_hi(k) - 1);
-                const int n4 = nsh_k >> 2, rem = nsh_k & 3;
-                // the top `rem` steps (m = n4) are the heads of chains 0 .. rem - 1
-                const double *top = g1 + 4 * (1 + 4 * n4);
-                // the heads WITHOUT branches: a head that does not exist is read from the zeroed slack behind the buffers
-                // (one select on the address), so that the three loads, the slot's constants above and the first trip's
-                // eight are in flight together -- one LDS round trip at the top of a slot instead of three or four
-                // (the layout made afresh from the plan: `lay`'s n_buf, held from the top of the kernel, cost the walk spilled scalars)
-                const double *zp = Gs + FactoredLds{NT, plan.n_buf, LD, SPO}.slack();
-                double h0 = *(rem > 0 ? top : zp), h1 = *(rem > 1 ? top + 4 : zp), h2 = *(rem > 2 ? top + 8 : zp), h3 = 0.0;
-                {
-                    // The trips' reads are written out as ds_read_b64: left alone the compiler pairs them into
-                    // ds_read2_b64, which the LDS serves at half the rate and with banks counted mod 32 -- rows 8 apart
-                    // collide there (the row stride is 4 dwords mod 64: conflict-free for ds_read_b64 only).  The
-                    // compiler does not count reads it cannot see: the wait is part of the statement.
-                    unsigned qa = (unsigned)(uintptr_t)(top - 32); // LDS byte address of the trip's lowest step
-                    int gq = n4;
-                    for (; gq >= 2; gq -= 2, qa -= 256) { // eight loads in flight per trip
-                        double b0, b1, b2, b3, c0, c1, c2, c3;
-                        asm volatile("ds_read_b64 %0, %8 offset:128\n\tds_read_b64 %1, %8 offset:160\n\t"
-                                     "ds_read_b64 %2, %8 offset:192\n\tds_read_b64 %3, %8 offset:224\n\t"
-                                     "ds_read_b64 %4, %8\n\tds_read_b64 %5, %8 offset:32\n\t"
-                                     "ds_read_b64 %6, %8 offset:64\n\tds_read_b64 %7, %8 offset:96\n\t"
-                                     "s_waitcnt lgkmcnt(0)"
-                                     : "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3), "=&v"(c0), "=&v"(c1), "=&v"(c2), "=&v"(c3)
-                                     : "v"(qa));
-                        h0 = fma_vvv(fma(h0, rr16, b0), rr16, c0); // (three-address: no copy back into the chain's register)
-                        h1 = fma_vvv(fma(h1, rr16, b1), rr16, c1);
-                        h2 = fma_vvv(fma(h2, rr16, b2), rr16, c2);
-                        h3 = fma_vvv(fma(h3, rr16, b3), rr16, c3);
-                    }
-                    if (gq > 0) {
-                        double b0, b1, b2, b3;
-                        asm volatile("ds_read_b64 %0, %4 offset:128\n\tds_read_b64 %1, %4 offset:160\n\t"
-                                     "ds_read_b64 %2, %4 offset:192\n\tds_read_b64 %3, %4 offset:224\n\t"
-                                     "s_waitcnt lgkmcnt(0)"
-                                     : "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3)
-                                     : "v"(qa));
-                        h0 = fma_vvv(h0, rr16, b0);
-                        h1 = fma_vvv(h1, rr16, b1);
-                        h2 = fma_vvv(h2, rr16, b2);
-                        h3 = fma_vvv(h3, rr16, b3);
-                    }
-                }
-                const double hs = fma(fma(fma(h3, rr4, h2), rr4, h1), rr4, h0);
+                    nsh_k = min(nsh_k, item_bands.get(k) - 1);
+                // (the slack: a head that does not exist is read from there; the layout made afresh from the plan, factored_state.h)
+                const double hs = shared_steps_sum(g1, nsh_k, Gs + fresh_lds<NT, SPO>(plan, LD).slack(), rr16, rr4);
                 acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(hs, wrun[k] * rho_n, zero4, 0, 0, 0);
                 acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[k], wfirst[k], acc[k], 0, 0, 0);
             }
-            STAMP(dg_b0)
+            stamps.lap(Stamps::kShared);
             // the remaining steps, specialised on the number of slots still running (len is sorted)
             if (!COVEST_SKIP_PHASE(plan, 2)) {
                 int a_off[MU]; // this lane's A fragments counted from the first step after the shared ones (per tile: 6 adds
@@ -906,7 +548,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                     int nsh_k = nsh[k];
                     asm volatile("" : "+s"(nsh_k));
                     a_off[k] = a_off0[k] + 4 * nsh_k;
-                    lenb[k] = PLAIN ? min(len[k], max(band_hi(k) - nsh_k, 1)) : len[k];
+                    lenb[k] = PLAIN ? min(len[k], max(item_bands.get(k) - nsh_k, 1)) : len[k];
                 }
                 // (measured and not kept, round 4: one address register a slot with the buffer's base folded in and two
                 // steps a trip, the second fragment an immediate offset away -- the compiler moves the induction to the
@@ -925,41 +567,26 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                 for (; i < lenb[0]; ++i)
                     contract_step<1, MU>(i, cur, a_off, cut, r4, wrun, acc);
             }
-            // pieces of one unit: add the accumulators into the unit's first slot.  A BRANCH per slot (the empty asm
-            // keeps the compiler from turning it into four adds and eight selects for every slot, taken or not)
-#pragma unroll
-            for (int k = MU - 1; k >= 1; --k)
-                if ((m_cont >> k) & 1u) { // wave-uniform
-                    asm volatile("" ::: "memory");
-                    acc[k - 1] += acc[k];
-                }
-            STAMP(dg_b)
+            add_pieces<MU>(m_cont, acc);
+            stamps.lap(Stamps::kContract);
             // ================= phase C: h_j * log p_j from the accumulators =================
             const bool item_is_sum = TAIL && !SPO && tv.item_sum[t] != 0; // wave-uniform
             // f64 C/D layout: register r of a lane is row (lane>>4) + 4r, column lane&15.
 #pragma unroll
             for (int k = 0; k < MU; ++k) {
                 if (list_mode == 2) { // a chunk of a point's copy numbers: hand p_j's share on (column 0 only)
-                    if (qslot[k] >= 0 && !cont[k] && col == 0) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            plan.partial[(ce * tv.n_items + t) * kTileBins + 16 * uhalf[k] + kq + 4 * r] = // (x 2^128: kShareScale)
-                                acc[k][r] * (rows[NEED_SCAL ? (p & 1) : 0][NEED_SCAL ? 16 * uhalf[k] + kq + 4 * r : 0] * kShareScale);
-                    }
+                    if (qslot[k] >= 0 && !cont[k] && col == 0)
+                        store_shares<NEED_SCAL>(plan.partial + (ce * tv.n_items + t) * kTileBins + 16 * uhalf[k] + kq, false, acc[k],
+                                                row_scale<NEED_SCAL>(rows, p, 16 * uhalf[k] + kq));
                     continue;
                 }
                 if (list_mode == 3) { // a chunk of the copy numbers of a dense grid's LONG weight vectors: every
                                            // column's share of p_j goes to (the first chunk) or is added to the block's
-                                           // buffer in HBM; ll_finish_dense takes the logs.  Each element has one owner.
-                    if (qslot[k] >= 0 && !cont[k]) {
-                        double *row = plan.partial + (((ce - plan.ce_first) * plan.n_cols_partial + qslot[k]) * tv.n_items + t) * kTileBins +
-                                      16 * uhalf[k] + kq;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const double share = acc[k][r] * (rows[NEED_SCAL ? (p & 1) : 0][NEED_SCAL ? 16 * uhalf[k] + kq + 4 * r : 0] * kShareScale);
-                            row[4 * r] = plan.o_base == 0 ? share : row[4 * r] + share;
-                        }
-                    }
+                                           // buffer in HBM; ll_finish_dense takes the logs.
+                    if (qslot[k] >= 0 && !cont[k])
+                        store_shares<NEED_SCAL>(plan.partial + (((ce - plan.ce_first) * plan.n_cols_partial + qslot[k]) * tv.n_items + t) * kTileBins +
+                                                    16 * uhalf[k] + kq,
+                                                plan.o_base != 0, acc[k], row_scale<NEED_SCAL>(rows, p, 16 * uhalf[k] + kq));
                     continue;
                 }
                 if (SPO && sp_item) {
@@ -996,7 +623,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                         c4[r] = hc.y;
                     }
                     if (TAIL && !SPO) { // sp_j needs p_j itself (filler and padding keys: scale 0), before the clamp
-                        const double *sr = &rows[NEED_SCAL ? (p & 1) : 0][NEED_SCAL ? 16 * uhalf[k] + kq : 0];
+                        const double *sr = row_scale<NEED_SCAL>(rows, p, 16 * uhalf[k] + kq);
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
                             spacc[k].add(acc[k][r] * sr[NEED_SCAL ? 4 * r : 0]);
@@ -1076,37 +703,12 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
                     }
                 }
             }
-            STAMP(dg_c)
+            stamps.lap(Stamps::kLog);
         }
         __syncthreads(); // the tile just contracted may be overwritten, the one just built may be read
-#ifdef COVEST_DIAG
-        if (diag && (plan.skip_phases & 0x10000)) { // (COVEST_FACTORED_DIAG=2) the wait at the barrier by eighths of the walk
-            const long long now__ = (long long)clock64();
-            if (lane == 0) {
-                const int grp = (plan.skip_phases & 0x20000) ? min(7, p - t_begin + 1) // (=3: the first seven intervals one by one)
-                                                              : min(7, (p - t_begin + 1) * 8 / (t_end - t_begin + 1));
-                plan.diag[((int64_t)(blockIdx.x * gridDim.y + blockIdx.y) * NW + wave) * 8 + grp] += now__ - dg_t0;
-            }
-        }
-#endif
-        STAMP(dg_w)
+        stamps.barrier_passed(p, t_begin, t_end, lane);
     }
-
-#ifdef COVEST_DIAG
-    dgx_4 = (long long)clock64(); // the walk
-#endif
-    if (diag && lane == 0 && !(plan.skip_phases & 0x50000)) {
-        long long *d = plan.diag + ((int64_t)(blockIdx.x * gridDim.y + blockIdx.y) * NW + wave) * 8;
-        d[0] = dg_a;
-        d[1] = dg_b;
-        d[2] = dg_c;
-        d[3] = dg_w;
-        d[4] = dg_b0;
-        d[5] = dg_zero; // key tiles whose G columns of this (builder) wave were all zero
-        d[6] = dg_enter; // of phase A: StreamSet::enter_tile
-        d[7] = dg_first; // of phase B: waiting for the first A fragments (LDS) and the tile's weights (HBM / L2)
-    }
-#undef STAMP
+    stamps.dump_laps(lane);
     if (list_mode >= 2)
         return; // (wave-uniform for the whole workgroup) the chunks are combined by ll_finish_partials / _dense
     // ---- per-q results: sum the 4 row groups of the accumulator layout, then the two
@@ -1127,10 +729,11 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
         for (int u = 0; u < kEntries; ++u) {
             const int e = min(tid + u * NT, NE - 1);
             const int at = wave_block(e / (MU * 16)) * MU + (e / 16) % MU;
-            en_qt[u] = plan.unit_tile[at];
-            en_half[u] = plan.unit_half[at];
-            en_cont[u] = plan.unit_cont[at];
-            en_pair[u] = plan.unit_pair[at];
+            const ResultEntry en = fetch_entry(plan, at);
+            en_qt[u] = en.qt;
+            en_half[u] = en.half;
+            en_cont[u] = en.cont;
+            en_pair[u] = en.pair;
         }
 #pragma unroll
         for (int u = 0; u < kEntries; ++u)
@@ -1143,7 +746,7 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     int ld_end = LD;
     if (SPO && LDC == 0)
         asm volatile("" : "+s"(ld_end));
-    const FactoredLds lay_end{NT, plan.n_buf, ld_end, SPO};
+    const FactoredLds lay_end = fresh_lds<NT, SPO>(plan, ld_end);
     double *part_ll = Gs + lay_end.part_ll();
     double *part_hi = Gs + lay_end.part_hi(t_end);
     double *part_lo = Gs + lay_end.part_lo(t_end);
@@ -1247,158 +850,22 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     } else {
         for (int e = tid; e < NE; e += NT) {
             const int at = wave_block(e / (MU * 16)) * MU + (e / 16) % MU;
-            // (the entry's four words fetched together: behind `||` each waited for the one before)
-            const int qt = plan.unit_tile[at], e_half = plan.unit_half[at], e_cont = plan.unit_cont[at];
-            finish_entry(e, qt, e_half, e_cont, plan.unit_pair[at], 0);
+            const ResultEntry en = fetch_entry(plan, at);
+            finish_entry(e, en.qt, en.half, en.cont, en.pair, 0);
         }
     }
-#ifdef COVEST_DIAG
-    if (plan.diag && (plan.skip_phases & 0x40000) && lane == 0) {
-        long long *d = plan.diag + ((int64_t)(blockIdx.x * gridDim.y + blockIdx.y) * NW + wave) * 8;
-        const long long end = (long long)clock64();
-        d[0] = dgx_1 - dgx_0;
-        d[1] = dgx_2 - dgx_1;
-        d[2] = dgx_3 - dgx_2;
-        d[3] = dgx_4 - dgx_3;
-        d[4] = end - dgx_4;
-        d[5] = end - dgx_0;
-        d[6] = dgx_0; // (absolute: a workgroup's start against the others')
-        d[7] = end;
-    }
-#endif
+    stamps.dump_stages(lane);
 }
-
-#ifndef COVEST_FACTORED_VARIANT // (the finishing kernels live in the common translation unit only)
-// One wave finishes ONE point whose p_j lie in HBM, summed over chunks of copy numbers (tiles.h list modes 2, 3):
-// LL = sum_j h_j log p_j + tail log(1 - sp), covest/models.py:100-107.  read_pj(row): the p_j of row `row` of the
-// items (tiles.h: a key, or the sum over a count-less tile), TIMES kShareScale.  A subnormal p_j at a key with h_j != 0
-// -- down to kZeroSteps of a grid step, below which it is 0 in the reference whatever the roundings (handback.h) -- is
-// replaced on the spot by its strict evaluation (direct_point.h: the whole wave, K-direct's arithmetic).  par: the
-// point's parameters, clamped; every lane returns the value.
-template <class ReadPj>
-__device__ __forceinline__ double finish_point(const DevModel &m, const TileView &tv, const double *par, int T,
-                                               ReadPj read_pj)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t n_rows = (int64_t)tv.n_items * kTileBins;
-    double ll = 0.0;
-    bool dead = false, poisoned = false;
-    CompSum sp = {0.0, 0.0};
-    for (int64_t base = 0; base < n_rows; base += kWave) { // wave-uniform trip count
-        const int64_t row = base + lane;
-        const bool valid = row < n_rows;
-        const double pj_scaled = valid ? read_pj(row) : 0.0;
-        double pj = pj_scaled * (1.0 / kShareScale); // (one rounding, onto the doubles' grid)
-        const double h = valid ? tv.item_cnt[row] : 0.0;
-        uint64_t sub = __ballot(h != 0.0 && pj_scaled > zero_steps_scaled(kShareScale) &&
-                                pj < 2.2250738585072014e-308); // a subnormal p_j, or one the product above flushed
-        while (sub) { // wave-uniform, rare
-            const int who = __builtin_ctzll(sub);
-            sub &= sub - 1;
-            const int64_t r = base + who;
-            const int item = (int)(r / kTileBins);
-            const int bin = tv.row_bin[(int64_t)tv.item_first[item] * kTileBins + (r - (int64_t)item * kTileBins)];
-            const double strict = strict_pj_wave<5>(m, par, T, m.bins.key[bin], -m.bins.lgam[bin]);
-            if (lane == who)
-                pj = strict;
-        }
-        if (m.tail != 0.0)
-            sp.add(pj);
-        if (h != 0.0) {
-            dead |= pj <= 0.0; // utils.safe_log
-            poisoned |= pj != pj; // a NaN parameter: NaN, as in the reference (math.log(nan))
-            ll = fma(h, log(pj > 0.0 ? pj : 1.0), ll);
-        }
-    }
-    ll = wave_sum(ll);
-    double tail_term = 0.0;
-    if (m.tail != 0.0) {
-        double s = wave_comp_sum(sp);
-        if (!(s < 1.0))
-            s = 1.0;
-        if (s < 1.0)
-            tail_term = m.tail * log(1.0 - s);
-    }
-    if (__ballot(dead))
-        ll = isnan(ll) ? ll : -INFINITY;
-    double v = ll + tail_term;
-    if (__ballot(poisoned) || !(isfinite(par[0]) && isfinite(par[1])))
-        v = NAN;
-    return v;
-}
-
-// Chunked point list (tiles.h list_mode 2): one wave per point adds the chunks' shares of p_j in chunk order and
-// takes the logs.  point_par[5 n_points], point_T[n_points]: the points' parameters and threshold_o.
-__global__ __launch_bounds__(kWave) void ll_finish_partials(const DevModel m, const int32_t n_tiles, const int32_t n_items,
-                                                           const double *__restrict__ tile_dbl,
-                                                           const int32_t *__restrict__ tile_int,
-                                                           const double *__restrict__ partial,
-                                                           const int32_t *__restrict__ first_item,
-                                                           const double *__restrict__ point_par,
-                                                           const int32_t *__restrict__ point_T, double *__restrict__ out_ll)
-{
-    const TileView tv = tile_view_from(n_tiles, n_items, tile_dbl, tile_int);
-    const int p = blockIdx.x;
-    const int c0 = first_item[p], c1 = first_item[p + 1];
-    const int64_t n_rows = (int64_t)n_items * kTileBins;
-    double par[kMaxParams];
-#pragma unroll
-    for (int d = 0; d < kMaxParams; ++d)
-        par[d] = point_par[(int64_t)p * kMaxParams + d];
-    clamp_point<5>(m, par);
-    const double v = finish_point(m, tv, par, point_T[p], [&](int64_t row) {
-        double pj = 0.0;
-        for (int c = c0; c < c1; ++c)
-            pj += partial[(int64_t)c * n_rows + row];
-        return pj;
-    });
-    if (threadIdx.x == 0)
-        out_ll[p] = v;
-}
-
-// The long weight vectors of a dense grid (tiles.h list_mode 3: threshold_o beyond a workgroup's lanes): one wave
-// per ((c, e), slot) takes the logs of the p_j the chunk launches summed into `partial`.
-__global__ __launch_bounds__(kWave) void ll_finish_dense(const DevModel m, const int32_t n_tiles, const int32_t n_items,
-                                                        const double *__restrict__ tile_dbl,
-                                                        const int32_t *__restrict__ tile_int, const PointSource src,
-                                                        const double *__restrict__ partial, const int64_t ce_first,
-                                                        const int64_t n_cols, const int32_t *__restrict__ q_orig,
-                                                        const int64_t n_q, const int64_t flat_end,
-                                                        double *__restrict__ out_ll)
-{
-    const TileView tv = tile_view_from(n_tiles, n_items, tile_dbl, tile_int);
-    const int64_t ce_local = blockIdx.x / n_cols, slot = blockIdx.x - ce_local * n_cols;
-    const int32_t qo = q_orig[slot];
-    if (qo < 0)
-        return; // padding column
-    const int64_t flat = (ce_first + ce_local) * n_q + qo;
-    if (flat < src.flat_begin || flat >= flat_end)
-        return; // (ragged block ends)
-    double par[kMaxParams];
-    int T;
-    fetch_point<5>(src, flat - src.flat_begin, par, T);
-    clamp_point<5>(m, par);
-    const int64_t n_rows = (int64_t)n_items * kTileBins;
-    const double *mine = partial + (ce_local * n_cols + slot) * n_rows;
-    const double v = finish_point(m, tv, par, T, [&](int64_t row) { return mine[row]; });
-    if (threadIdx.x == 0)
-        out_ll[flat - src.flat_begin] = v;
-}
-
-#endif // COVEST_FACTORED_VARIANT
 
 } // namespace
 
-// HIP wraps a grid of more than 2^32 threads silently: at most 2^22 workgroups per launch ((c, e) rows per launch)
-inline int64_t factored_rows_per_launch(const FactoredPlan &plan) { return std::max<int64_t>(1, ((int64_t)1 << 22) / plan.n_qblocks); }
-
-// One instantiation per translation unit (COVEST_FACTORED_VARIANT, see the end of this file): the HIP runtime
-// loads a translation unit's code object when one of its kernels is first launched, and a process that evaluates a
-// plain dense grid should not pay for the seven other variants (75-98 KB of code each).
-template <int NT, bool TAIL, bool PLAIN, int LDC = 0>
+// Variant COVEST_FACTORED_VARIANT of factored_launch.h's table: its launcher, and with it the kernel, instantiated below.
+template <int V>
 hipError_t launch_ll_factored_variant(const DevModel &m, const TileView &tv, const FactoredPlan &plan,
                                       double *out_ll, const SubList &sub_list, hipStream_t stream)
 {
+    constexpr int NT = kFactoredVariantTable[V].nt, LDC = kFactoredVariantTable[V].ldc;
+    constexpr bool TAIL = kFactoredVariantTable[V].tail, PLAIN = kFactoredVariantTable[V].plain;
     constexpr int HU = kHalfUnits;
     const FactoredLds lay{NT, plan.n_buf, plan.ld, PLAIN && TAIL}; // (tiles.h)
     if (!lay.fits())
@@ -1431,144 +898,7 @@ hipError_t launch_ll_factored_variant(const DevModel &m, const TileView &tv, con
     return hipGetLastError();
 }
 
-#ifdef COVEST_FACTORED_VARIANT
-// this translation unit holds ONE variant: bit 2 = 512 threads (else 256), bit 1 = TAIL, bit 0 = PLAIN; 8 and 9: 512
-// threads, PLAIN, the row stride kLdWide at compile time, bit 0 = TAIL
-#if COVEST_FACTORED_VARIANT >= 8
-template hipError_t launch_ll_factored_variant<512, (COVEST_FACTORED_VARIANT & 1) != 0, true, kLdWide>(
-    const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
-#else
-template hipError_t launch_ll_factored_variant<(COVEST_FACTORED_VARIANT & 4) ? 512 : 256, (COVEST_FACTORED_VARIANT & 2) != 0,
-                                               (COVEST_FACTORED_VARIANT & 1) != 0>(const DevModel &, const TileView &,
-                                                                                   const FactoredPlan &, double *,
-                                                                                   const SubList &, hipStream_t);
-#endif
-#else
-// the common translation unit: the finishing kernels and the dispatcher; the variants are linked in
-extern template hipError_t launch_ll_factored_variant<256, false, false>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
-extern template hipError_t launch_ll_factored_variant<256, false, true>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
-extern template hipError_t launch_ll_factored_variant<256, true, false>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
-extern template hipError_t launch_ll_factored_variant<256, true, true>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
-extern template hipError_t launch_ll_factored_variant<512, false, false>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
-extern template hipError_t launch_ll_factored_variant<512, false, true>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
-extern template hipError_t launch_ll_factored_variant<512, true, false>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
-extern template hipError_t launch_ll_factored_variant<512, true, true>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
-extern template hipError_t launch_ll_factored_variant<512, false, true, kLdWide>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
-extern template hipError_t launch_ll_factored_variant<512, true, true, kLdWide>(const DevModel &, const TileView &, const FactoredPlan &, double *, const SubList &, hipStream_t);
-// their names, in the order of COVEST_FACTORED_VARIANT (the launch record, covest_compiled_variants)
-const char *const kFactoredVariantNames[kFactoredVariants] = {
-    "ll_factored<256>", "ll_factored<256,plain>", "ll_factored<256,tail>", "ll_factored<256,tail,plain>",
-    "ll_factored<512>", "ll_factored<512,plain>", "ll_factored<512,tail>", "ll_factored<512,tail,plain>",
-    "ll_factored<512,plain,ld290>", "ll_factored<512,tail,plain,ld290>"};
-const char *const kFactoredFinishNames[2] = {"ll_finish_dense", "ll_finish_partials"};
-static_assert(kLdWide == 290, "kFactoredVariantNames spell the row stride of kLdWide");
-
-namespace {
-
-// The layout of tiles.h FactoredLds over the shapes the planners make (row strides 34 .. 546, both workgroup sizes, one
-// and two buffers, with and without SPO, both parities of the walk's length): every area inside the allocation, the SPO
-// parts clear of what the last interval still reads -- the buffer it contracts (one buffer: the two rows of S in it) --
-// and of the slack, part_ll clear of part_hi / part_lo, and the allocation within the CU's LDS wherever the planners
-// choose that n_buf.
-constexpr bool lds_overlap(int a0, int a1, int b0, int b1) { return a0 < b1 && b0 < a1; }
-constexpr bool factored_lds_sound()
-{
-    for (int nt = 256; nt <= 512; nt += 256)
-        for (int n_buf = 1; n_buf <= 2; ++n_buf)
-            for (int k = 1; k <= 17; ++k)
-                for (int spo = 0; spo <= 1; ++spo)
-                    for (int t_end = 1; t_end <= 2; ++t_end) {
-                        const FactoredLds l{nt, n_buf, kTileBins * k + 2, spo != 0};
-                        const int ne = l.entries(), total = l.total();
-                        if (l.buf(n_buf - 1) + kTileBins * l.ld > l.slack() || l.slack() + FactoredLds::kSlack > total ||
-                            l.rates() + FactoredLds::kRates > total || l.pad(l.rows() - 1) + 2 > l.slack())
-                            return false;
-                        if (l.part_ll() + ne > total || l.part_hi(t_end) + ne > total || l.part_lo(t_end) + ne > total ||
-                            lds_overlap(l.part_ll(), l.part_ll() + ne, l.part_hi(t_end), l.part_lo(t_end) + ne))
-                            return false;
-                        if (spo) {
-                            const int s0 = l.spo_parts(t_end), s1 = s0 + 2 * ne, live = l.buf(t_end);
-                            if (s1 > total || lds_overlap(s0, s1, l.slack(), l.slack() + FactoredLds::kSlack) ||
-                                lds_overlap(s0, s1, live, live + (n_buf == 2 ? kTileBins : 2) * l.ld))
-                                return false;
-                            const int other = l.buf(t_end + 1);
-                            if (n_buf == 2 && s0 < l.slack() && (s0 < other || s1 > other + kTileBins * l.ld))
-                                return false;
-                        }
-                        if (factored_n_buf(l.ld) == n_buf && !l.fits())
-                            return false;
-                    }
-    return true;
-}
-static_assert(factored_lds_sound(), "K-factored's LDS layout (tiles.h FactoredLds)");
-// the headline shape (C3: 512 threads, plain, no tail, kLdWide) allocates two buffers and the slack, as it always has
-static_assert(FactoredLds{512, 2, kLdWide, false}.total() == 2 * kTileBins * kLdWide + FactoredLds::kSlack, "C3's LDS");
-
-template <int NT>
-hipError_t launch_nt(const DevModel &m, const TileView &tv, const FactoredPlan &plan, double *out_ll,
-                     const SubList &sub_list, hipStream_t stream)
-{
-    const bool plain = plan.list_mode == 0 && plan.n_pass == 1;
-    {
-        const bool tail = m.tail != 0.0;
-        const int v = NT == 512 && plain && plan.ld == kLdWide ? 8 + (tail ? 1 : 0)
-                                                                : (NT == 512 ? 4 : 0) + (tail ? 2 : 0) + (plain ? 1 : 0);
-        const int64_t rows = plan.ce_end - plan.ce_begin, per_launch = factored_rows_per_launch(plan);
-        record_launch(kFactoredVariantNames[v], (rows + per_launch - 1) / per_launch);
-    }
-    if (NT == 512 && plain && plan.ld == kLdWide) // the widest double-buffered shape: its row stride at compile time
-        return m.tail != 0.0 ? launch_ll_factored_variant<512, true, true, kLdWide>(m, tv, plan, out_ll, sub_list, stream)
-                             : launch_ll_factored_variant<512, false, true, kLdWide>(m, tv, plan, out_ll, sub_list, stream);
-    if (m.tail != 0.0)
-        return plain ? launch_ll_factored_variant<NT, true, true>(m, tv, plan, out_ll, sub_list, stream)
-                     : launch_ll_factored_variant<NT, true, false>(m, tv, plan, out_ll, sub_list, stream);
-    return plain ? launch_ll_factored_variant<NT, false, true>(m, tv, plan, out_ll, sub_list, stream)
-                 : launch_ll_factored_variant<NT, false, false>(m, tv, plan, out_ll, sub_list, stream);
-}
-
-} // namespace
-
-hipError_t launch_ll_finish_partials(const DevModel &m, const TileView &tv, const double *partial,
-                                     const int32_t *first_item, const double *point_par, const int32_t *point_T,
-                                     int64_t n_points, double *out_ll, hipStream_t stream)
-{
-    if (n_points <= 0)
-        return hipSuccess;
-    record_launch(kFactoredFinishNames[1]);
-    hipLaunchKernelGGL(ll_finish_partials, dim3((unsigned)n_points), dim3(kWave), 0, stream, m, tv.n_tiles, tv.n_items, tv.dbl_base,
-                       tv.int_base, partial, first_item, point_par, point_T, out_ll);
-    return hipGetLastError();
-}
-
-hipError_t launch_ll_finish_dense(const DevModel &m, const TileView &tv, const PointSource &src, const double *partial,
-                                  int64_t ce_first, int64_t n_ce, int64_t n_cols, const int32_t *q_orig, int64_t n_q,
-                                  int64_t flat_end, double *out_ll, hipStream_t stream)
-{
-    // HIP wraps a grid of more than 2^32 threads silently: at most 2^24 waves per launch
-    const int64_t per_launch = std::max<int64_t>(1, ((int64_t)1 << 24) / n_cols);
-    for (int64_t first = 0; first < n_ce; first += per_launch) {
-        const int64_t cnt = std::min(per_launch, n_ce - first);
-        record_launch(kFactoredFinishNames[0]);
-        hipLaunchKernelGGL(ll_finish_dense, dim3((unsigned)(cnt * n_cols)), dim3(kWave), 0, stream, m, tv.n_tiles, tv.n_items,
-                           tv.dbl_base, tv.int_base, src, partial + first * n_cols * (int64_t)tv.n_items * kTileBins,
-                           ce_first + first, n_cols, q_orig, n_q, flat_end, out_ll);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_ll_factored(const DevModel &m, const TileView &tv, const FactoredPlan &plan,
-                              double *out_ll, const SubList &sub_list, hipStream_t stream)
-{
-    if (plan.ce_end <= plan.ce_begin)
-        return hipSuccess;
-    if (m.kind != 1 || plan.n_columns > plan.n_threads || 8 * plan.n_pass < m.n_err)
-        return hipErrorInvalidValue;
-    if (plan.n_threads == 256 && plan.half_units == 3)
-        return launch_nt<256>(m, tv, plan, out_ll, sub_list, stream);
-    if (plan.n_threads == 512 && plan.half_units == 3)
-        return launch_nt<512>(m, tv, plan, out_ll, sub_list, stream);
-    return hipErrorInvalidValue;
-}
-#endif // COVEST_FACTORED_VARIANT
+template hipError_t launch_ll_factored_variant<COVEST_FACTORED_VARIANT>(const DevModel &, const TileView &, const FactoredPlan &,
+                                                                        double *, const SubList &, hipStream_t);
 
 } // namespace covest

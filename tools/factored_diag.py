@@ -22,7 +22,7 @@ L = _capi.lib()
 n = L.covest_grid_diag(g._handle, None, 0)
 buf = np.zeros(n, dtype=np.int64)
 L.covest_grid_diag(g._handle, buf.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n)
-if os.environ.get("COVEST_FACTORED_DIAG") == "4":  # the stages OUTSIDE the walk, per wave (ll_factored.hip dgx_*)
+if os.environ.get("COVEST_FACTORED_DIAG") == "4":  # the stages OUTSIDE the walk, per wave (factored_diag.h Stamps::dump_stages)
     st = buf.reshape(-1, 8, 8).astype(np.float64)
     print("workgroups", st.shape[0])
     print("mean cycles per wave: start -> first barrier | streams' constants | units' tables, first weights | the walk | "

@@ -11,12 +11,14 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 files = sys.argv[1:] or sorted(glob.glob(os.path.join(REPO, "covest_amd", "csrc", "*.hip")))
 print("%-60s %5s %5s %6s %6s %7s %4s %8s" % ("kernel", "VGPR", "AGPR", "vspill", "sspill", "scratch", "occ", "LDS"))
 # K-factored and K-basic are compiled once per template variant (covest_amd/build.py): the kernels live in those
-# translation units, one -D each
-VARIANTS = {"ll_factored.hip": ["-DCOVEST_FACTORED_VARIANT=%d" % v for v in range(10)],
+# translation units, one -D each (ll_factored.hip is compiled in no other way; ll_basic.hip also without)
+N_FACTORED = int(re.search(r"kFactoredVariants = (\d+)", open(os.path.join(REPO, "covest_amd", "csrc", "kernels.h")).read()).group(1))
+VARIANTS = {"ll_factored.hip": ["-DCOVEST_FACTORED_VARIANT=%d" % v for v in range(N_FACTORED)],
             "ll_basic.hip": ["-DCOVEST_BASIC_VARIANT=%d" % v for v in range(8)]}
 jobs = []
 for f in files:
-    jobs.append((f, []))
+    if os.path.basename(f) != "ll_factored.hip":
+        jobs.append((f, []))
     for flag in VARIANTS.get(os.path.basename(f), []):
         jobs.append((f, [flag]))
 seen = set()
