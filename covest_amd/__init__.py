@@ -21,3 +21,5 @@ from . import simulate  # noqa: F401,E402
 from .simulate import random_genome, simulate_reads, SimulatedReads  # noqa: F401,E402
 from .simulate import (repeat_plan, repeat_genome, repeat_genome_device, RepeatGenome, genome_spectrum,  # noqa: F401,E402
                        spectrum_to_q)
+from . import jackknife  # noqa: F401,E402
+from .jackknife import leave_group_out_histograms, read_jackknife, summarize_jackknife, jackknife_batch  # noqa: F401,E402

@@ -39,6 +39,7 @@ EXPORTS = (
     "covest_truncated_poisson", "covest_truncated_poisson_table",
     "covest_random_genome", "covest_random_genome_device", "covest_simulate_reads", "covest_simulate_reads_device",
     "covest_sample_reads", "covest_sample_reads_device",
+    "covest_split_reads", "covest_split_reads_device",
     "covest_repeat_plan", "covest_repeat_genome", "covest_repeat_genome_device",
     "covest_draw_thresholds", "covest_draw_histograms", "covest_draw_histograms_device",
     "covest_batch_create", "covest_batch_draw", "covest_batch_counts", "covest_batch_eval_cross", "covest_batch_eval_pairs",
@@ -237,6 +238,10 @@ def lib():
     L.covest_sample_reads.argtypes = [i32, vp, vp, i64, i64, i64, ctypes.c_double, u64, vp, vp, vp, i64p, i64p]
     L.covest_sample_reads_device.restype = ctypes.c_int
     L.covest_sample_reads_device.argtypes = [i32, vp, vp, i64, i64, i64, ctypes.c_double, u64, vp, vp, vp, vp, vp]
+    L.covest_split_reads.restype = ctypes.c_int
+    L.covest_split_reads.argtypes = [i32, vp, vp, i64, i64, i64, i32, u64, vp, vp, vp, vp]
+    L.covest_split_reads_device.restype = ctypes.c_int
+    L.covest_split_reads_device.argtypes = [i32, vp, vp, i64, i64, i64, i32, u64, vp, vp, vp, vp, vp]
     L.covest_repeat_plan.restype = ctypes.c_int
     L.covest_repeat_plan.argtypes = [i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, u64, i32, vp, i64p]
     L.covest_repeat_genome.restype = ctypes.c_int

@@ -1,6 +1,7 @@
 // abi_sample.cpp -- covest_sample_reads* of the C ABI over sample_reads.hip: the counterpart of the reference's
 // covest/data.py:57-63 sample_reads.  No handle: the device form launches on the caller's stream
 // and returns; the host form owns its device buffers for the call.
+#include "call_scratch.h"
 #include "host.h"
 #include "sample.h"
 
@@ -28,71 +29,6 @@ int check_sample_args(const char *who, const void *offsets, int64_t n_reads, int
     return COVEST_OK;
 }
 
-// Scratch of the device form.  The call returns before its kernels have run, so what they work on cannot go with the
-// call: a block is handed to ONE call at a time and to the next only once the event recorded behind that call's last
-// launch has come to pass.  Blocks stay with the process (as the device cache's do); calls that overlap on several
-// streams get a block each.
-struct SampleScratch {
-    DevBuf buf;
-    hipEvent_t done = nullptr;
-    int device = -1;
-    bool in_use = false;
-};
-struct ScratchPool {
-    std::mutex mu;
-    std::deque<SampleScratch> blocks; // (a deque: growing it moves no block a call holds)
-};
-ScratchPool &scratch_pool()
-{
-    static ScratchPool *pool = new ScratchPool; // (never destroyed: no HIP call after the runtime has gone)
-    return *pool;
-}
-
-int scratch_take(int device, size_t bytes, SampleScratch **out)
-{
-    ScratchPool &pool = scratch_pool();
-    SampleScratch *got = nullptr;
-    {
-        std::lock_guard<std::mutex> hold(pool.mu);
-        for (SampleScratch &s : pool.blocks)
-            if (!s.in_use && s.device == device && hipEventQuery(s.done) == hipSuccess) {
-                got = &s;
-                break;
-            }
-        (void)hipGetLastError(); // (hipErrorNotReady of a query is no failure of this call)
-        if (!got) {
-            pool.blocks.emplace_back();
-            got = &pool.blocks.back();
-            got->device = device;
-        }
-        got->in_use = true;
-    }
-    hipError_t e = hipSuccess;
-    if (!got->done)
-        e = hipEventCreateWithFlags(&got->done, hipEventDisableTiming);
-    if (e == hipSuccess) {
-        // a block much larger than this call needs goes back to the device (the one 4 * 10^9-base call of a process
-        // must not keep its scratch for ever)
-        if (got->buf.cap > ((size_t)64 << 20) && got->buf.cap / 4 > bytes)
-            got->buf.release();
-        e = got->buf.reserve(bytes);
-    }
-    if (e != hipSuccess) {
-        std::lock_guard<std::mutex> hold(pool.mu);
-        got->in_use = false;
-        return fail_hip(e, "scratch of covest_sample_reads_device");
-    }
-    *out = got;
-    return COVEST_OK;
-}
-
-void scratch_give(SampleScratch *s, hipStream_t stream)
-{
-    (void)hipEventRecord(s->done, stream);
-    std::lock_guard<std::mutex> hold(scratch_pool().mu);
-    s->in_use = false;
-}
-
 } // namespace
 
 extern "C" {
@@ -115,11 +51,11 @@ int covest_sample_reads_device(int32_t device, const uint8_t *d_bases, const int
             HIP_TRY(hipMemsetAsync(d_out_offsets, 0, sizeof(int64_t), st));
         return COVEST_OK;
     }
-    SampleScratch *scratch = nullptr;
-    COVEST_TRY(scratch_take(call.device(), sample_scratch_bytes(n_reads), &scratch));
+    CallScratch *scratch = nullptr; // (call_scratch.h: the call returns before its kernels have run)
+    COVEST_TRY(call_scratch_take(call.device(), sample_scratch_bytes(n_reads), "scratch of covest_sample_reads_device", &scratch));
     const hipError_t e = launch_sample_reads(d_bases, d_offsets, n_reads, read_len, first_read, thr, seed, d_out_bases,
                                              d_out_offsets, d_kept_index, d_counts, scratch->buf.ptr, st);
-    scratch_give(scratch, st); // (whatever was launched before a failure still works on the block)
+    call_scratch_give(scratch, st); // (whatever was launched before a failure still works on the block)
     HIP_TRY(e);
     return COVEST_OK;
 }

@@ -23,5 +23,13 @@ hipError_t launch_sample_reads(const unsigned char *bases, const int64_t *offset
                                int64_t first_read, uint64_t thr, uint64_t seed, unsigned char *out_bases,
                                int64_t *out_offsets, int64_t *kept_index, int64_t *counts, void *scratch,
                                hipStream_t stream);
+// The sampler's last launch on its own, for any table of reads to gather (split_reads.hip): rank q of the
+// counts[0] reads (device: counts[2] = (reads, bases in all)) goes from bases + src_off[q] to out_bases +
+// out_offsets[q], the output offsets ascending from 0 (nullptr: q * read_len, read_len > 0).  most_bases: an upper
+// bound of counts[1] the host knows (> 0), or -1.  Any alignment of both buffers; nothing is written outside
+// out_bases[0 .. counts[1]).
+hipError_t launch_sample_gather(const unsigned char *bases, const int64_t *counts, const int64_t *out_offsets,
+                                int64_t read_len, int64_t most_bases, const int64_t *src_off, unsigned char *out_bases,
+                                hipStream_t stream);
 
 } // namespace covest

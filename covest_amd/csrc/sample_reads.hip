@@ -385,15 +385,23 @@ hipError_t launch_sample_reads(const unsigned char *bases, const int64_t *offset
     }
     if (!offsets && read_len == 0)
         return hipSuccess; // nothing but empty reads: no byte to move
-    // the tile count is known on the device only: a fixed number of workgroups share the tiles (fewer where the input
-    // itself, the upper bound, has fewer tiles)
+    return launch_sample_gather(bases, counts, offsets ? out_offsets : nullptr, read_len,
+                                offsets ? -1 : n_reads * read_len, reinterpret_cast<const int64_t *>(src_off), out_bases, stream);
+}
+
+hipError_t launch_sample_gather(const unsigned char *bases, const int64_t *counts, const int64_t *out_offsets,
+                                int64_t read_len, int64_t most_bases, const int64_t *src_off, unsigned char *out_bases,
+                                hipStream_t stream)
+{
+    // the tile count is known on the device only: a fixed number of workgroups share the tiles (fewer where the
+    // upper bound the caller knows has fewer tiles)
     int64_t n_groups = kSampleGatherGroups;
-    if (!offsets)
-        n_groups = std::min<int64_t>(n_groups, image_tiles(n_reads * read_len, 15));
+    if (most_bases >= 0)
+        n_groups = std::min<int64_t>(n_groups, image_tiles(most_bases, 15));
     const int lead = image_lead(out_bases);
     hipLaunchKernelGGL(sample_gather_kernel, dim3((unsigned)n_groups), dim3(kThreads), 0, stream, bases,
-                       reinterpret_cast<const long long *>(counts), offsets ? reinterpret_cast<const long long *>(out_offsets) : nullptr,
-                       (long long)read_len, src_off, out_bases, lead);
+                       reinterpret_cast<const long long *>(counts), reinterpret_cast<const long long *>(out_offsets),
+                       (long long)read_len, reinterpret_cast<const long long *>(src_off), out_bases, lead);
     return hipGetLastError();
 }
 

@@ -57,9 +57,10 @@ COVEST_HD uint32_t mod3(uint32_t w)
 //   shuffle     unit-list entry j 0                             w0 | w1 << 32 the sort key, w2 & 1 the orientation
 //   divergence  genome base i>>2  0                             one a base: substituted()
 //   draw        draw d >> 1       replicate b                   (w0 | w1 << 32) >> 1 an even d, (w2 | w3 << 32) >> 1 an odd
+//   group       read r            0                             (w0 * G) >> 32: the read's group of G (split_reads.hip)
 // A new generator takes the next free number (and a row here and in the header); c2 is free in all but `read` and `draw`.
 constexpr uint32_t kStreamRead = 0, kStreamGenome = 1, kStreamKeep = 2, kStreamFamily = 3, kStreamCopies = 4,
-                   kStreamShuffle = 5, kStreamDivergence = 6, kStreamDraw = 7;
+                   kStreamShuffle = 5, kStreamDivergence = 6, kStreamDraw = 7, kStreamGroup = 8;
 
 struct PhiloxKey { uint32_t k0, k1; };
 COVEST_HD PhiloxKey philox_key(uint64_t seed) { return PhiloxKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }

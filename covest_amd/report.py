@@ -26,7 +26,7 @@ def _finite_int(x):
 
 def print_output(hist_orig, model, success, sample_factor, estimated=None, guess=None, orig=None,
                  reads_size=None, silent=False, orig_sample_factor=1, starting_points=1,
-                 use_grid_search=False, intervals=None, information=None, bootstrap=None):
+                 use_grid_search=False, intervals=None, information=None, bootstrap=None, jackknife=None):
     """`intervals`: the dict covest_amd.profile.coverage_interval returns; the record then carries the likelihood-ratio
     interval of the coverage, of the genome size and its level.  Without it the record is the reference's, key for key.
     `information`: the dict covest_amd.information.observed_information returns (a key 'level' in it chooses the Wald
@@ -42,7 +42,12 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
     bootstrap_interval_<param> (the coverage's times sample_factor, like its neighbours), and
     bootstrap_interval_genome_size where the bootstrap was given hist_orig; and, only where the bootstrap was studentized
     (it carries 't_intervals'), bootstrap_t_interval_<param> and bootstrap_t_interval_genome_size, scaled alike
-    (DESIGN.md 6x).  They share the model's independence assumption.  Without it the record is unchanged."""
+    (DESIGN.md 6x).  They share the model's independence assumption.  Without it the record is unchanged.
+    `jackknife`: the dict covest_amd.jackknife.read_jackknife returns (sample factor 1 by its own rule, so nothing is
+    scaled); the record then carries jackknife_groups, jackknife_used, jackknife_failed, jackknife_level and, per free
+    parameter and for genome_size, jackknife_se_<name>, jackknife_bias_<name> and jackknife_interval_<name>: the
+    delete-a-group jackknife over READS, which sees the dependence between the k-mers of one read.
+    Without it the record is unchanged."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -133,6 +138,19 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
             record['bootstrap_interval_genome_size'] = [float(v) for v in size['interval']]
         if size is not None and size.get('t_interval') is not None:
             record['bootstrap_t_interval_genome_size'] = [float(v) for v in size['t_interval']]
+    if jackknife is not None:
+        record['jackknife_groups'] = int(jackknife['groups'])
+        record['jackknife_used'] = int(jackknife['used'])
+        record['jackknife_failed'] = int(jackknife['failed'])
+        record['jackknife_level'] = float(jackknife['level'])
+        for name in list(model.params) + ['genome_size']:
+            for key, source in (('se', 'standard_errors'), ('bias', 'bias')):
+                value = jackknife[source].get(name)
+                if value is not None:
+                    record['jackknife_%s_%s' % (key, name)] = float(value)
+            interval = jackknife['intervals'].get(name)
+            if interval is not None:
+                record['jackknife_interval_%s' % name] = [float(v) for v in interval]
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

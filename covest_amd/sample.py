@@ -176,11 +176,127 @@ def sample_reads_device(bases_ptr, n_reads, out_bases_ptr, counts_ptr, factor, s
         ctypes.c_void_p(counts_ptr), ctypes.c_void_p(stream or 0)), "covest_sample_reads_device")
 
 
+# the split's constants (csrc/split.h; tests/test_split_cpu.py compares): the cap on the groups, the reads a workgroup of
+# the flag and place kernels owns, and the pairs of a group's row one pass of its scan holds
+MAX_GROUPS = 256
+SPLIT_SHARE = 1024
+SPLIT_SCAN_PASS = 1024
+
+
+def _check_split(groups, seed, first_read):
+    """The argument rules of covest_split_reads, before the library is asked (ValueError)."""
+    if isinstance(groups, bool) or not isinstance(groups, (int, np.integer)):
+        raise ValueError("groups must be an integer")
+    if not 1 <= groups <= MAX_GROUPS:
+        raise ValueError("groups must be within 1 .. %d" % MAX_GROUPS)
+    _check_seed(seed, whole=True)
+    if int(first_read) != first_read or first_read < 0:
+        raise ValueError("first_read must not be negative")
+    return int(groups), int(seed), int(first_read)
+
+
+class SplitReads:
+    """What split_reads returns: the reads in the order of their groups, input order within a group.  `bases` ((n, L)
+    for reads of one length, else back to back), `offsets` (n + 1,) int64, `read_index` (n,) int64: the global index of
+    the read at each output rank, `group_first` (groups + 1,) int64: the rank at which each group starts; `groups`,
+    `seed`."""
+
+    def __init__(self, bases, offsets, read_index, group_first, seed):
+        self.bases = bases
+        self.offsets = offsets
+        self.read_index = read_index
+        self.group_first = group_first
+        self.groups = int(group_first.size - 1)
+        self.seed = int(seed)
+
+    @property
+    def n_reads(self):
+        return int(self.read_index.size)
+
+    def group(self, g):
+        """The reads of group g: rows of `bases` for reads of one length, else (bases, offsets from 0)."""
+        if not 0 <= g < self.groups:
+            raise IndexError("group %r of %d" % (g, self.groups))
+        lo, hi = int(self.group_first[g]), int(self.group_first[g + 1])
+        if self.bases.ndim == 2:
+            return self.bases[lo:hi]
+        return self.bases[self.offsets[lo]:self.offsets[hi]], self.offsets[lo:hi + 1] - self.offsets[lo]
+
+
+def _split_host(blob, offsets, n, read_len, first_read, groups, seed, device, want_bases=True):
+    """covest_split_reads on host arrays: (out_bases, out_offsets, read_index, group_first)."""
+    total = int(offsets[-1] - offsets[0]) if offsets is not None else n * read_len
+    out = np.empty(total if want_bases else 0, dtype=np.uint8)
+    out_offsets = np.empty(n + 1, dtype=np.int64)
+    index = np.empty(n, dtype=np.int64)
+    first = np.empty(groups + 1, dtype=np.int64)
+    _capi.check(_capi.lib().covest_split_reads(
+        int(device), blob.ctypes.data if blob is not None else None, offsets.ctypes.data if offsets is not None else None,
+        n, int(read_len), first_read, groups, seed, out.ctypes.data, out_offsets.ctypes.data, index.ctypes.data,
+        first.ctypes.data), "covest_split_reads")
+    return out, out_offsets, index, first
+
+
+def read_groups(n_reads, groups, seed=0, first_read=0, device=-1):
+    """The group of each of `n_reads` reads numbered from `first_read`, as covest_split_reads deals them: an (n_reads,)
+    int64 array.  One device call on reads of no bases (the rule does not look at them): its read_index and
+    group_first turned round."""
+    groups, seed, first_read = _check_split(groups, seed, first_read)
+    if int(n_reads) != n_reads or n_reads < 0:
+        raise ValueError("n_reads must not be negative")
+    n = int(n_reads)
+    _, _, index, first = _split_host(None, None, n, 0, first_read, groups, seed, device, want_bases=False)
+    out = np.empty(n, dtype=np.int64)
+    out[index - first_read] = np.repeat(np.arange(groups, dtype=np.int64), np.diff(first))
+    return out
+
+
+def split_reads(reads, groups, seed=0, first_read=None, device=-1):
+    """Deal the reads of `reads` -- a SimulatedReads, an (n, L) uint8 array or a pair (bases, offsets) in the packed
+    layout -- into `groups` seeded groups (1 .. 256) and return them group by group, in input order within a group, as a
+    SplitReads.  Read r (its index + `first_read`; default: a SimulatedReads' own first_read, else 0) is of group
+    (w * groups) >> 32, w = word 0 of Philox4x32-10 on the counter (lo32(r), hi32(r), 0, 8), key = seed
+    (include/covest_amd.h)."""
+    groups, seed, first = _check_split(groups, seed, 0 if first_read is None else first_read)
+    blob, offsets, n, read_len, source = _packed(reads)
+    if first_read is None and source is not None:
+        first = int(source.first_read)
+    out, out_offsets, index, group_first = _split_host(blob, offsets, n, read_len, first, groups, seed, device)
+    if offsets is None:
+        out = out.reshape(n, read_len)
+    return SplitReads(out, out_offsets, index, group_first, seed)
+
+
+def split_reads_device(bases_ptr, n_reads, out_bases_ptr, group_first_ptr, groups, seed=0, first_read=0, read_len=0,
+                       offsets_ptr=None, out_offsets_ptr=None, read_index_ptr=None, stream=None, device=-1):
+    """The same between buffers resident in HBM (raw device pointers, e.g. a torch tensor's data_ptr()), asynchronous on
+    `stream`: `n_reads` reads at `bases_ptr`, `read_len` bases each unless `offsets_ptr` (n_reads + 1 int64) is given;
+    the reads in group order to `out_bases_ptr` / `out_offsets_ptr` (n_reads + 1 int64; needed with `offsets_ptr`) /
+    `read_index_ptr` (n_reads int64, optional); the ranks at which the groups start to the groups + 1 int64 at
+    `group_first_ptr`."""
+    groups, seed, first_read = _check_split(groups, seed, first_read)
+    if n_reads < 0:
+        raise ValueError("n_reads must not be negative")
+    if not offsets_ptr and read_len < 0:
+        raise ValueError("read_len must not be negative")
+    if offsets_ptr and not out_offsets_ptr:
+        raise ValueError("reads of their own lengths need out_offsets_ptr")
+    if not group_first_ptr:
+        raise ValueError("group_first_ptr must not be null")
+    _capi.require_shared_runtime("split_reads_device")
+    _capi.check(_capi.lib().covest_split_reads_device(
+        int(device), ctypes.c_void_p(bases_ptr), ctypes.c_void_p(offsets_ptr or 0), int(n_reads), int(read_len), first_read,
+        groups, seed, ctypes.c_void_p(out_bases_ptr), ctypes.c_void_p(out_offsets_ptr or 0),
+        ctypes.c_void_p(read_index_ptr or 0), ctypes.c_void_p(group_first_ptr), ctypes.c_void_p(stream or 0)),
+        "covest_split_reads_device")
+
+
 class _DeviceArena:
     """The device buffers of sampled_histogram, through the HIP runtime the library is bound to (already mapped into
     the process): they grow on demand and go with the arena."""
 
-    def __init__(self):
+    def __init__(self, who="sampled_histogram"):
+        self.who = who
         _capi.lib()
         mapped = _capi.hip_runtimes_mapped()
         if mapped is not None and len(mapped) > 1:
@@ -188,12 +304,12 @@ class _DeviceArena:
             # bound to the other one
             mapped = [p for p in mapped if "torch" not in p]
             if len(mapped) != 1:
-                raise _capi.CovestHipError("sampled_histogram: cannot tell which of the HIP runtimes of this process "
+                raise _capi.CovestHipError(who + ": cannot tell which of the HIP runtimes of this process "
                                            "the library is bound to -- `import torch` before the first covest_amd call")
         try:
             self.hip = ctypes.CDLL(mapped[0] if mapped else "libamdhip64.so")
         except OSError as e:
-            raise _capi.CovestHipError("sampled_histogram: cannot reach the HIP runtime: %s" % e)
+            raise _capi.CovestHipError("%s: cannot reach the HIP runtime: %s" % (who, e))
         vp, sz = ctypes.c_void_p, ctypes.c_size_t
         self.hip.hipMalloc.argtypes = [ctypes.POINTER(vp), sz]
         self.hip.hipFree.argtypes = [vp]
@@ -204,7 +320,7 @@ class _DeviceArena:
 
     def _ok(self, rc, what):
         if rc != 0:
-            raise _capi.CovestHipError("sampled_histogram: %s failed (HIP error %d)" % (what, rc))
+            raise _capi.CovestHipError("%s: %s failed (HIP error %d)" % (self.who, what, rc))
 
     def reserve(self, name, n_bytes):
         ptr, cap = self.bufs.get(name, (None, 0))

@@ -489,6 +489,40 @@ int covest_sample_reads(int32_t device, const uint8_t *bases, const int64_t *off
                         uint8_t *out_bases, int64_t *out_offsets, int64_t *kept_index,
                         int64_t *n_kept, int64_t *bases_kept);
 
+/* ---- read groups: a stable G-way split of the packed reads ----
+ * Deals every read into one of `groups` = G groups (1 <= G <= 256) and writes the reads group by group -- group 0's
+ * first, then group 1's, ... --, IN INPUT ORDER WITHIN A GROUP (a stable partition), in the layout they came in: the
+ * packed layout of covest_kmer_add_device (bases back to back at any alignment; offsets[n_reads + 1] ascending, or NULL
+ * when every read is read_len bases long).  Every group is then one contiguous run of reads: "all reads but group g"
+ * is two sub-ranges of one buffer (the delete-a-group jackknife over reads, covest_amd/jackknife.py).  Empty reads are
+ * reads.  The group is a function of (seed, read index) alone:
+ *   read r = index within the call + first_read (64-bit);
+ *   w = word 0 of Philox4x32-10 (as above; key = seed's low and high word) on the counter (lo32(r), hi32(r), 0, 8)
+ *   (stream 8, `group`: the next row of the table of streams above);
+ *   group(r) = (w * G) >> 32, the product formed in 64-bit integer arithmetic.
+ * So the group does not depend on the read's content, on the sampler's stream (.., 0, 2) or the simulator's, or on how
+ * a run is cut into chunks: a chunk [a, a + m) split with first_read = a gives its reads the groups the whole run gives
+ * those rows.
+ * Output: out_bases (any alignment, the size of the input), out_offsets[n_reads + 1] absolute into out_bases (may be
+ * NULL where offsets is), read_index[n_reads] (may be NULL): the global index r of the read at each output rank;
+ * group_first[G + 1]: the output rank at which each group starts, group_first[G] = n_reads; an empty group has
+ * group_first[g] == group_first[g + 1].  Nothing is written outside out_bases[0 .. bases in all), out_offsets[0 ..
+ * n_reads], read_index[0 .. n_reads) and group_first[0 .. G].  Scratch is the library's own: at most 24 bytes a read of
+ * the input plus a constant, at every G.
+ * COVEST_E_INVALID: groups outside 1 .. 256; n_reads < 0 or first_read < 0; offsets == NULL with read_len < 0; offsets
+ * without out_offsets; a NULL group_first.  n_reads == 0: COVEST_OK, no kernel launched, group_first[0 .. G] = 0 and
+ * out_offsets[0] = 0 (the device form sets them by a memset on the stream).  COVEST_E_NOMEM where the device buffers of
+ * the call do not fit.  device < 0 = the calling thread's current device.
+ * The _device form takes DEVICE buffers, is asynchronous on `stream` and does not look at the offsets; the other takes
+ * HOST buffers, copies and waits, and answers COVEST_E_INVALID for offsets that are negative or descend. */
+int covest_split_reads_device(int32_t device, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                              int64_t read_len, int64_t first_read, int32_t groups, uint64_t seed,
+                              uint8_t *d_out_bases, int64_t *d_out_offsets, int64_t *d_read_index,
+                              int64_t *d_group_first, void *stream);
+int covest_split_reads(int32_t device, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
+                       int64_t read_len, int64_t first_read, int32_t groups, uint64_t seed,
+                       uint8_t *out_bases, int64_t *out_offsets, int64_t *read_index, int64_t *group_first);
+
 /* ---- replicate histograms drawn from a weight vector: the parametric bootstrap's generator ----
  * INPUT: m >= 1 weights w_0 .. w_{m-1} (doubles, finite, >= 0, sum > 0) and a number of draws n >= 0.  A call covers
  * the replicates first_rep .. first_rep + n_rep - 1, every replicate index < 2^32, under a 64-bit seed.
@@ -502,7 +536,8 @@ int covest_sample_reads(int32_t device, const uint8_t *bases, const int64_t *off
  *   cell after it, is never reached from above; a cell of weight 0 (t_i == t_{i-1}) never counts.
  * The streams of the generators, by the counter's last word (the key is always the seed's two words):
  *   0 read (c2: 0 the header, 1 + j the bases 4j .. 4j + 3)   1 genome   2 keep (the sampler)   3 family   4 copies
- *   5 shuffle   6 divergence   7 draw (c2: the replicate) -- c2 is 0 in all but `read` and `draw`.
+ *   5 shuffle   6 divergence   7 draw (c2: the replicate)   8 group (covest_split_reads) -- c2 is 0 in all but `read`
+ *   and `draw`.
  * OUTPUT: counts[b - first_rep][i] (int64, row-major n_rep x m) = the number of draws d < n of replicate b in cell i.
  * The call OVERWRITES the output: the caller does not zero it.  A run of replicates [a, a + k) equals the same rows
  * of a larger run, and the row for n equals the row for n' > n restricted to its first n draws.  All arithmetic on the
