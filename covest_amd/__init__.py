@@ -23,3 +23,5 @@ from .simulate import (repeat_plan, repeat_genome, repeat_genome_device, RepeatG
                        spectrum_to_q)
 from . import jackknife  # noqa: F401,E402
 from .jackknife import leave_group_out_histograms, read_jackknife, summarize_jackknife, jackknife_batch  # noqa: F401,E402
+from . import posterior  # noqa: F401,E402
+from .posterior import posterior_classes, PosteriorClasses  # noqa: F401,E402

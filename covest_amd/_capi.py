@@ -46,6 +46,7 @@ EXPORTS = (
     "covest_batch_argmin_cross", "covest_batch_info", "covest_batch_destroy",
     "covest_batch_eval_cross_grad", "covest_batch_eval_pairs_grad", "covest_batch_score_table",
     "covest_batch_eval_cross_hess", "covest_batch_eval_pairs_hess", "covest_batch_score_table2",
+    "covest_posterior_classes", "covest_posterior_classes_chunked",
 )
 
 
@@ -278,6 +279,10 @@ def lib():
     L.covest_batch_eval_pairs_hess.argtypes = [vp, i64, vp, vp, vp]
     L.covest_batch_score_table2.restype = ctypes.c_int
     L.covest_batch_score_table2.argtypes = [vp, i64, vp, vp, vp]
+    L.covest_posterior_classes.restype = ctypes.c_int
+    L.covest_posterior_classes.argtypes = [vp, i64, dp, i32, i32, dp, dp, dp, dp]
+    L.covest_posterior_classes_chunked.restype = ctypes.c_int
+    L.covest_posterior_classes_chunked.argtypes = [vp, i64, dp, i32, i32, i64, dp, dp, dp, dp]
     L.covest_batch_info.restype = ctypes.c_int
     L.covest_batch_info.argtypes = [vp, i64p]
     L.covest_batch_destroy.restype = None

@@ -12,6 +12,7 @@
 //   abi_repeat.cpp    covest_repeat_plan, covest_repeat_genome*
 //   abi_draw.cpp      covest_draw_thresholds, covest_draw_histograms*
 //   abi_batch.cpp     covest_batch_*
+//   abi_posterior.cpp covest_posterior_classes
 // ).  Nothing here is part of the C ABI (include/covest_amd.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -279,6 +280,7 @@ struct covest_model {
     // values (and gradients, Hessians), or list mode 1's parts.
     HostBuf ws_stage, ws_result;
     DevBuf ws_sub_index, ws_sub_word, ws_sub_ctl; // the queue of handed-back points of a point-list launch (handback.h)
+    DevBuf ws_post_table, ws_post_out; // covest_posterior_classes: a chunk's component tables and its results (posterior.h)
     LaunchRecord record; // what the last covest_eval_points launched (covest_model_launch_record)
     std::mutex lock;
 };

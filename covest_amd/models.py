@@ -354,6 +354,40 @@ class BasicModel:
                                                      _as_dp(out)), "covest_probabilities")
         return dict(zip(self.hist.keys(), out.tolist()))
 
+    def posterior_classes_points(self, points, copy_columns=4, clamp=True, _chunk_points=None):
+        """Per key, what the mixture at each point of an (n, param_count) array says about the k-mers of that abundance
+        (covest_posterior_classes, formed in logs throughout) -> (log_p[n, K], error_share[n, K, max_error],
+        copy_share[n, K, copy_columns], mean_copies[n, K]), K keys in the order of `hist`.  error_share[.., s]: the
+        k-mer has s wrong bases; copy_share[.., c]: it has c + 1 copies, the last column copy_columns or more (columns
+        beyond the point's threshold_o - 1 are 0; the basic model has one copy number).  A key at which no component
+        has weight has log_p = -inf and NaN shares.  clamp as in compute_probabilities.  The raw call;
+        covest_amd.posterior.posterior_classes summarises one point.  (_chunk_points: the library's internal chunk of
+        points capped, for tests of the chunk edge; it changes no number.)"""
+        copy_columns = int(copy_columns)
+        if copy_columns < 1 or copy_columns > 65536:
+            raise ValueError('copy_columns must be in 1..65536')
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        if pts.ndim == 1:
+            pts = pts.reshape(1, -1)
+        if pts.ndim != 2 or pts.shape[1] != self.param_count:
+            raise ValueError('points: an (n, %d) array' % self.param_count)
+        n, K = len(pts), len(self._keys) if self._keys is not None else len(self._hist)
+        log_p = np.empty((n, K), dtype=np.float64)
+        err = np.empty((n, K, self.max_error), dtype=np.float64)
+        cop = np.empty((n, K, copy_columns), dtype=np.float64)
+        mean = np.empty((n, K), dtype=np.float64)
+        if n and K:
+            L = _capi.lib()
+            if _chunk_points is None:
+                rc = L.covest_posterior_classes(self.handle, n, _as_dp(pts), 1 if clamp else 0, copy_columns,
+                                                _as_dp(log_p), _as_dp(err), _as_dp(cop), _as_dp(mean))
+            else:
+                rc = L.covest_posterior_classes_chunked(self.handle, n, _as_dp(pts), 1 if clamp else 0, copy_columns,
+                                                        int(_chunk_points), _as_dp(log_p), _as_dp(err), _as_dp(cop),
+                                                        _as_dp(mean))
+            _capi.check(rc, "covest_posterior_classes")
+        return log_p, err, cop, mean
+
     def compute_loglikelihood(self, *args):
         """covest/models.py:100-107."""
         return float(self.loglikelihood_points(self._points_array([args]))[0])

@@ -26,7 +26,8 @@ def _finite_int(x):
 
 def print_output(hist_orig, model, success, sample_factor, estimated=None, guess=None, orig=None,
                  reads_size=None, silent=False, orig_sample_factor=1, starting_points=1,
-                 use_grid_search=False, intervals=None, information=None, bootstrap=None, jackknife=None):
+                 use_grid_search=False, intervals=None, information=None, bootstrap=None, jackknife=None,
+                 posterior=None):
     """`intervals`: the dict covest_amd.profile.coverage_interval returns; the record then carries the likelihood-ratio
     interval of the coverage, of the genome size and its level.  Without it the record is the reference's, key for key.
     `information`: the dict covest_amd.information.observed_information returns (a key 'level' in it chooses the Wald
@@ -47,7 +48,13 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
     scaled); the record then carries jackknife_groups, jackknife_used, jackknife_failed, jackknife_level and, per free
     parameter and for genome_size, jackknife_se_<name>, jackknife_bias_<name> and jackknife_interval_<name>: the
     delete-a-group jackknife over READS, which sees the dependence between the k-mers of one read.
-    Without it the record is unchanged."""
+    Without it the record is unchanged.
+    `posterior`: the PosteriorClasses covest_amd.posterior.posterior_classes returns; the record then carries
+    posterior_error_cutoff (error_cutoff at level 0.5, None where there is none), posterior_erroneous_kmers,
+    posterior_error_free_kmers, one posterior_copies_* per copy column (expected_kmers), posterior_undefined_kmers and
+    posterior_sample_factor.  They are numbers of the histogram the model was fitted to: for a sample factor other than
+    1 they are recorded as such, with the factor beside them, and are NOT scaled back to the un-sampled data (DESIGN.md
+    6ab).  Without it the record is unchanged."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -151,6 +158,12 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
             interval = jackknife['intervals'].get(name)
             if interval is not None:
                 record['jackknife_interval_%s' % name] = [float(v) for v in interval]
+    if posterior is not None:
+        cutoff = posterior.error_cutoff()
+        record['posterior_error_cutoff'] = None if cutoff is None else int(cutoff)
+        for name, value in posterior.expected_kmers().items():
+            record['posterior_%s%s' % (name, '' if name.startswith('copies_') else '_kmers')] = float(value)
+        record['posterior_sample_factor'] = sample_factor
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

@@ -186,6 +186,42 @@ int covest_truncated_poisson_table(int32_t device, int64_t n_l, const double *l,
  * method as plot_probs calls it.  Used by --plot and by the parity tests. */
 int covest_probabilities(covest_model *m, const double *params, int32_t clamp, double *out_p);
 
+/* ---- what the fitted mixture says about the k-mers of abundance j: posterior classes, in the log domain ----
+ * (DESIGN.md section 6ab).  The shares are the terms of the sum compute_probabilities adds up, before they are added.
+ * A point is params[i][param_count], taken as given (clamp == 0) or clamped as fit_to_bounds clamps it (clamp != 0:
+ * the meaning it has in covest_probabilities).  S = max_error classes; T = threshold_o of the point by the host rule of
+ * covest_threshold_o (of the clamped point where clamp != 0), T = 2 in the basic model: one copy number, b_1 = 1.  With
+ * x_os = o l_s, and a_os and b_o exactly as models.py:77, 87-90, 194-206, 221-233 forms them (1.0 - exp(-x), not expm1,
+ * and fix_zero included), for every key j of the model, all keys, in the order of model.hist:
+ *   ln w_os(j) = ln b_o + ln a_os + j ln x_os - D(x_os) - ln j!      (-inf where a_os b_o = 0 or x_os = 0)
+ *   ln p_j     = logsumexp over (o, s) of ln w_os(j)
+ *   E_s(j)     = sum_o w_os(j) / p_j        s = 0 .. S-1      error share: the k-mer has s wrong bases
+ *   C_o(j)     = sum_s w_os(j) / p_j        o = 1 .. T-1      copy share
+ *   M(j)       = sum_o o C_o(j)                               mean copy number
+ * D is the reference's normaliser (c_src/covest_poissonmodule.c:20,25-31).  Each of the three is formed as
+ * sum exp(ln w - max) over its own sum, never by a division by a p_j held as a double, so a share exists where p_j
+ * itself is subnormal or 0 in double; each family is normalised by its own total.  These are shares of the model as
+ * the reference evaluates it: a class whose 1.0 - exp(-x) is 0 in double has share exactly 0.
+ * The copy shares come in copy_columns = Cc >= 1 columns: columns 0 .. Cc-2 are o = 1 .. Cc-1, the last column is
+ * everything from o = Cc on; where T - 1 < Cc the columns beyond T - 1 are 0.  A key at which every component is -inf
+ * has ln p_j = -inf, and NaN shares and NaN mean copy number: no posterior exists there.  The tail cell (mass at or
+ * beyond the trim) is not covered: only keys are.
+ * HOST arrays; an output that is NULL is not computed for the caller, the others do not change by it.  A point's numbers
+ * do not depend on what else is in the call.  COVEST_E_INVALID for each of: a null model; n < 0; n > 0 with null params;
+ * copy_columns < 1 or > 65536; all four outputs null with n > 0.  n == 0 or a model with no keys: COVEST_OK, nothing
+ * written.  Two launches per chunk of points (posterior.hip), not entered in the launch record. */
+int covest_posterior_classes(covest_model *m, int64_t n, const double *params, int32_t clamp, int32_t copy_columns,
+                             double *out_log_p,        /* [n][n_keys]            or NULL */
+                             double *out_error_share,  /* [n][n_keys][S]         or NULL */
+                             double *out_copy_share,   /* [n][n_keys][Cc]        or NULL */
+                             double *out_mean_copies); /* [n][n_keys]            or NULL */
+/* The same call with the points walked in chunks of at most chunk_points (0: the library's own choice, which bounds the
+ * device memory of a call; negative: COVEST_E_INVALID).  The chunk changes no number: it is here so that the chunk edge
+ * can be tested on a short list. */
+int covest_posterior_classes_chunked(covest_model *m, int64_t n, const double *params, int32_t clamp, int32_t copy_columns,
+                                     int64_t chunk_points, double *out_log_p, double *out_error_share,
+                                     double *out_copy_share, double *out_mean_copies);
+
 /* Dense grid = itertools.product(*axes), last axis fastest (covest/grid.py:39-43,
  * notebooks/VisualiseLikelihood.ipynb cell 5).  n_axes must equal param_count; a
  * fixed parameter is an axis of length 1 (covest/grid.py:27-28).  The handle
