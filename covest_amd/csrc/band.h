@@ -27,6 +27,7 @@
 // The lower edge is not cut: step_lo is 0 (step 0, o = 1 .. 4 with the weights that are not geometric, is always taken).
 #pragma once
 #include <math.h>
+#include <stdint.h>
 
 #ifndef COVEST_HD
 #ifdef __HIPCC__
@@ -118,6 +119,60 @@ COVEST_HD inline Band band_of_unit(const Math &mth, double rate0, double ln_1mq,
     if (!(base + t.key_first * ln_o + t.cls_first <= 0.0) || !(base + t.key_last * ln_o + t.cls_last <= 0.0))
         return full;
     return Band{0, step_hi};
+}
+
+// THE COLUMN LIMIT (ll_factored.hip col_hi).  The steps below a band's upper edge hold the copy numbers
+// 1 .. 4 step_hi: the largest one the unit reads with a weight that matters in the tile.  The maximum of it over the units of a
+// workgroup -- and, for the units without a band, of their largest copy number -- is a limit above which NO unit needs a
+// column of G in that tile, and a builder wave whose 64 copy numbers all lie above it need not build them: the columns
+// hold zeros instead.  What a unit then loses are terms the proof above already drops, or terms of the steps that the
+// clamped step loops run beyond the band's edge (factored_contract.h): both below 2^-68 of P_j together, for every key
+// of the tile and every column of the unit.  WITH A TAIL the same columns are missing from S[o] = sum_j G[o][j]
+// (ll_factored.hip SPO), whose contraction is sp = sum_j P_j: the bound holds key by key, so the share lost from sp is
+// below 2^-68 sp as well.
+COVEST_HD inline int band_top_column(const Band &b) { return 4 * b.step_hi; }
+
+// What the planner knows of the limit (plan_factored.cpp; tiles.h FactoredPlan::col_floor, band_extra), for the slots
+// of ONE workgroup, [n_waves][slots_per_wave]: tile (-1: none), shared steps, "continues the slot before" per slot,
+// top[tile] = the largest copy number a unit of the q-tile reads.  Waves n_build .. n_waves - 1 build nothing: they
+// make the bands of their own long units (kBandMinShared shared steps or more, in one piece) and of up to n_extra_max
+// long units of the builders, one per q-tile none of them holds -- their slots go to extra[] (-1: none).  Every other
+// unit keeps its full range: returns the largest copy number such a unit reads, at least floor_min.  Not `plain`, or no
+// wave that builds nothing: no unit has a band.
+inline int column_limit_of_block(const int32_t *tile, const int32_t *nsh, const int32_t *cont, const int32_t *top, int n_waves,
+                                 int slots_per_wave, int n_build, bool plain, int floor_min, int32_t *extra, int n_extra_max)
+{
+    const bool bands = plain && n_build < n_waves;
+    int floor = floor_min, n_made = 0, n_extra = 0;
+    int32_t made[64]; // q-tiles with a band
+    for (int j = 0; j < n_extra_max; ++j)
+        extra[j] = -1;
+    for (int round = 0; round < 2; ++round) // the waves that build nothing first: what they hold they make anyway
+        for (int w = round == 0 ? n_build : 0; w < (round == 0 ? n_waves : (n_build < n_waves ? n_build : n_waves)); ++w)
+            for (int k = 0; k < slots_per_wave; ++k) {
+                const int at = w * slots_per_wave + k;
+                if (tile[at] < 0)
+                    continue;
+                bool has_band = false;
+                if (bands && nsh[at] >= kBandMinShared && !cont[at] && !(k + 1 < slots_per_wave && tile[at + 1] == tile[at] && cont[at + 1])) {
+                    bool known = false;
+                    for (int i = 0; i < n_made; ++i)
+                        known = known || made[i] == tile[at];
+                    if (round == 0 || known) {
+                        has_band = true;
+                    } else if (n_extra < n_extra_max) {
+                        extra[n_extra++] = at;
+                        has_band = true;
+                    }
+                    if (has_band && !known && n_made < 64)
+                        made[n_made++] = tile[at];
+                    else if (has_band && !known)
+                        has_band = round == 0; // (the list is full: a builder's unit keeps its full range)
+                }
+                if (!has_band)
+                    floor = floor > top[tile[at]] ? floor : top[tile[at]];
+            }
+    return floor;
 }
 
 // The upper edges (step_hi) of a wave's six slots as the kernel keeps them: a byte a slot in two registers, 255: not

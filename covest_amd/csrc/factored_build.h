@@ -184,10 +184,16 @@ __device__ __forceinline__ bool sum_item_matters(const TileView &tv, const Strea
 }
 
 // One item into `dst`: a plain tile, or (TAIL) the per-tile sums of up to 32 count-less tiles as its rows.
-template <bool TAIL, bool SPO>
+// SKIP (a plain grid), `skip`: the item's column limit (ll_factored.hip col_hi, band.h) lies below every copy number of
+// this wave -- wave-uniform.  A tile that holds a count is then neither entered nor walked: the wave's columns of the
+// buffer get zeros (readers without a band, and the clamped steps beyond a band's edge, read them with a weight) --
+// once a buffer, `zeroed` bit buf_bit: they stay zero through a run of skipped items --, the streams are switched off
+// and anchored afresh at the next tile the wave walks (resync: the run-start path), and `gone` is left alone (a stream
+// that has gone stays gone at every later key).  A sum item is walked as ever: it is judged by what a sum can hold.
+template <bool TAIL, bool SPO, bool SKIP>
 __device__ __forceinline__ void build_item(const TileView &tv, const FactoredPlan &plan, StreamSet<8> &st, CompSum &so,
-                                           bool &resync, int tid, int ld, bool in_row, Stamps &stamps, int it,
-                                           bool seg_start, double *dst)
+                                           bool &resync, unsigned &zeroed, int tid, int ld, bool in_row, Stamps &stamps, int it,
+                                           bool seg_start, bool skip, int buf_bit, double *dst)
 {
     const BuildLane ln = {tid, ld, in_row};
     const int first = TAIL ? __builtin_amdgcn_readfirstlane(tv.item_first[it]) : it;
@@ -225,7 +231,26 @@ __device__ __forceinline__ void build_item(const TileView &tv, const FactoredPla
             if (ln.in_row)
                 colp[r * ln.ld] = 0.0;
     } else {
-        const double tsum = build_tile<SPO, true>(tv, plan, st, ln, stamps, first, seg_start || (SPO && resync), dst);
+        if (SKIP && skip) { // (wave-uniform)
+            if (!((zeroed >> buf_bit) & 1u)) {
+                zeroed |= 1u << buf_bit;
+                if (ln.in_row) {
+                    double *colp = ln.column(dst);
+#pragma unroll
+                    for (int b = 0; b < kTileBins; ++b)
+                        colp[b * ln.ld] = 0.0;
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < 8; ++s)
+                st.v[s] = 0.0;
+            resync = true;
+            stamps.count_skipped_item();
+            return;
+        }
+        if (SKIP)
+            zeroed &= ~(1u << buf_bit);
+        const double tsum = build_tile<SPO, true>(tv, plan, st, ln, stamps, first, seg_start || ((SPO || SKIP) && resync), dst);
         resync = false;
         if (SPO)
             so.add(tsum);

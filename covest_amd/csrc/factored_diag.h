@@ -20,7 +20,7 @@ struct StampNames {
         kLog,      // phase C
         kWait,     // the barrier
         kShared,   // of phase B: the first MFMAs and the shared steps
-        kZero,     // (a count) key tiles whose G columns of this (builder) wave were all zero
+        kZero,     // (a count) key tiles whose G columns of this (builder) wave were all zero; times 2^20: items it skipped
         kEnter,    // of phase A: StreamSet::enter_tile
         kFirst,    // of phase B: waiting for the first A fragments (LDS) and the tile's weights (HBM / L2)
     };
@@ -63,6 +63,12 @@ struct Stamps : StampNames {
     {
         if (out)
             lap_sum[kZero] += 1;
+    }
+    // (items a builder wave skipped by the column limit, factored_build.h: counted in the same word, from bit 20 up)
+    __device__ void count_skipped_item()
+    {
+        if (out)
+            lap_sum[kZero] += 1ll << 20;
     }
     // until the first fragments and the weights are there
     template <int MU>
@@ -117,6 +123,7 @@ struct Stamps : StampNames {
     __device__ void walk_begins() {}
     __device__ void lap(Lap) {}
     __device__ void count_zero_tile() {}
+    __device__ void count_skipped_item() {}
     template <int MU>
     __device__ void first_fragments(const double (&)[MU], const double (&)[MU])
     {

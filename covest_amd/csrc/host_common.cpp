@@ -369,7 +369,8 @@ void record_factored_plan(const FactoredPlan &plan, int shared_tiles, bool long_
     if (!r || r->n_plans >= (int)(sizeof r->plans / sizeof r->plans[0]))
         return;
     r->plans[r->n_plans++] = LaunchRecord::Plan{plan.n_threads, plan.n_buf,  plan.ld,        plan.n_qblocks,
-                                                shared_tiles,   plan.n_pass, plan.list_mode, long_part};
+                                                shared_tiles,   plan.n_pass, plan.list_mode, long_part,
+                                                plan.col_floor};
 }
 
 // "launch <name> <count>" and "plan <key>=<value> ..." lines; the whole text's length is returned, at most cap - 1
@@ -385,8 +386,8 @@ int64_t launch_record_text(const LaunchRecord &r, char *buf, int64_t cap)
     for (int i = 0; i < r.n_plans; ++i) {
         const LaunchRecord::Plan &p = r.plans[i];
         std::snprintf(line, sizeof line,
-                      "plan n_threads=%d n_buf=%d ld=%d n_qblocks=%d shared_tiles=%d long=%d n_pass=%d list_mode=%d\n",
-                      p.n_threads, p.n_buf, p.ld, p.n_qblocks, p.shared_tiles, p.long_part ? 1 : 0, p.n_pass, p.list_mode);
+                      "plan n_threads=%d n_buf=%d ld=%d n_qblocks=%d shared_tiles=%d long=%d n_pass=%d list_mode=%d col_floor=%d\n",
+                      p.n_threads, p.n_buf, p.ld, p.n_qblocks, p.shared_tiles, p.long_part ? 1 : 0, p.n_pass, p.list_mode, p.col_floor);
         t += line;
     }
     if (buf && cap > 0) {

@@ -26,6 +26,7 @@ struct LaunchRecord {
     struct Plan { // a K-factored work description as the host built it (tiles.h FactoredPlan)
         int32_t n_threads, n_buf, ld, n_qblocks, shared_tiles, n_pass, list_mode;
         bool long_part; // a chunk of the long weight vectors (list_mode 3)
+        int32_t col_floor; // tiles.h FactoredPlan::col_floor
     };
     Entry entries[16];
     int n_entries = 0;

@@ -131,10 +131,15 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     __shared__ __attribute__((aligned(16))) double rho_tab[PLAIN ? NW * MU * 4 : 4];
     __shared__ double lconst_s; // the constant the rows' scales add to every point's sum (tiles.h item_lconst)
     __shared__ double band_ln[PLAIN ? kBandClasses : 1]; // ln of the error classes' rates, for the units' bands (band.h)
+    // THE COLUMN LIMIT (band.h; tiles.h FactoredPlan::col_floor): per item of the walk (the last entry: every item from the
+    // 64th on, as the bands) the largest copy number a unit of this workgroup reads with a weight that matters.  Made in
+    // the prologue by the waves that build nothing, read by the builders from the walk's first barrier on: a builder
+    // wave whose copy numbers all lie above an item's limit skips the item (factored_build.h build_item).
+    __shared__ int col_hi[PLAIN ? kWave : 1];
     static_assert(MU == kMaxUnits, "the LDS layout counts kMaxUnits slots a wave");
     // (+ 15 bytes of alignment in front of each array at most)
     static_assert(sizeof(log_tab) + sizeof(sub_rec) + sizeof(rowc) + sizeof(rows) + sizeof(rho_tab) + sizeof(lconst_s) +
-                          sizeof(band_ln) + 7 * 15 <= kFactoredStaticLds, "the planners' LDS budget (tiles.h) must hold the kernel's static LDS");
+                          sizeof(band_ln) + sizeof(col_hi) + 8 * 15 <= kFactoredStaticLds, "the planners' LDS budget (tiles.h) must hold the kernel's static LDS");
 
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
@@ -230,6 +235,9 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     // counts for more than it is worth, never for less)
     if (PLAIN && tid < kBandClasses)
         band_ln[tid] = fast_log(Gs[lay.rates() + tid], log_tab);
+    // (the column limit starts from what the planner knows; the bands raise it behind the next barrier)
+    if (PLAIN && tid >= NT - kWave)
+        col_hi[tid - (NT - kWave)] = plan.col_floor;
     double n_total = -1.0;
     if (n_pass > 1) { // the mixture weights a_os are normalised over ALL classes: covest/models.py:225-233
         n_total = 0.0;
@@ -367,7 +375,11 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
 #pragma unroll
     for (int k = 0; k < MU; ++k)
         wave_bands = wave_bands || (PLAIN && !wave_builds && nsh[k] >= kBandMinShared);
-    if (PLAIN && wave_bands) {
+    // ... and THE COLUMN LIMIT with them: the largest copy number below a band's edge, over the wave's own banded units and
+    // over the builders' long units the planner hands it (tiles.h band_extra: entry j to the (j mod makers)-th of these
+    // waves) -- where the planner's floor leaves a column to skip at all.  A maximum in LDS per lane = item.
+    const bool wave_limit = PLAIN && !wave_builds && plan.col_floor < plan.max_o; // (wave-uniform)
+    if (PLAIN && (wave_bands || wave_limit)) {
         // (the kernel's own logarithm, 2e-16 absolute, and the hardware's reciprocal with one Newton step: band.h, roundings)
         struct {
             const double *tab;
@@ -382,12 +394,31 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
         const double key_first = tv.rec[TAIL ? tv.item_first[it] : it].k0;
         const double key_last = (lane < kWave - 1 ? key_first : tv.rec[n_tiles - 1].k0) + (double)(kTileBins - 1);
         const BandTile bt = band_tile(band_ln, m.ln_comb, key_first, key_last);
+        int hi = 0; // the largest copy number this wave's bands leave in the lane's item
 #pragma unroll
         for (int k = 0; k < MU; ++k) {
             if (nsh[k] < kBandMinShared) // wave-uniform
                 continue;
             const Band b = band_of_unit(mth, lam[0], rho_tab[4 * (wave * MU + k) + 1], 4 + 4 * nsh[k], nsh[k] + len[k], bt);
             bands.set(k, b.step_hi);
+            hi = max(hi, band_top_column(b));
+        }
+        if (wave_limit) {
+            const int n_build_waves = (plan.n_columns + kWave - 1) / kWave; // (this wave is none of them)
+#pragma unroll 1
+            for (int j = wave - n_build_waves; j < kBandExtra; j += NW - n_build_waves) {
+                const int e = __builtin_amdgcn_readfirstlane(plan.band_extra[(int)blockIdx.y * kBandExtra + j]);
+                if (e < 0)
+                    continue;
+                // (a builder's unit: its shared steps and length from the tables, its ln(1-q) from rho_tab as above)
+                const int at = (int)blockIdx.y * NW * MU + e;
+                const int nsh_x = __builtin_amdgcn_readfirstlane(plan.unit_nsh[at]);
+                const int len_x = __builtin_amdgcn_readfirstlane(plan.unit_len[at]);
+                const Band b = band_of_unit(mth, lam[0], rho_tab[4 * e + 1], 4 + 4 * nsh_x, nsh_x + len_x, bt);
+                hi = max(hi, band_top_column(b));
+            }
+            if (hi > 0)
+                atomicMax(&col_hi[lane], hi);
         }
     }
     // b_o of every slot's first (wfirst) and second (wrun, then advanced by (1-q)^4 per step) MFMA step:
@@ -410,12 +441,13 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
     // here and kept, the six masks held twelve scalar registers through the whole kernel, which spills them).
 
     // ================= phase A (factored_build.h): G'[key][o] of an item into a buffer =================
-    bool resync = false; // (SPO, wave-uniform) tiles were skipped: the next one walked anchors every stream afresh
+    bool resync = false; // (PLAIN, wave-uniform) tiles were skipped: the next one walked anchors every stream afresh
+    unsigned zeroed = 0; // (PLAIN, wave-uniform) bit b: this wave's columns of buffer b hold the zeros of a skipped item
     // (A local lambda forwards to the stage, here and below, and the stages take the kernel's variables one by one, where
     // they are declared: called directly, or with the state gathered into a struct, the compiler numbers the streams'
     // registers otherwise and fuses other products of a key's sum -- DESIGN.md 6z.)
-    auto build = [&](int it, bool seg_start, double *dst) __attribute__((always_inline)) {
-        build_item<TAIL, SPO>(tv, plan, st, so, resync, tid, LD, lane_in_row, stamps, it, seg_start, dst);
+    auto build = [&](int it, bool seg_start, bool skip, int buf_bit, double *dst) __attribute__((always_inline)) {
+        build_item<TAIL, SPO, PLAIN>(tv, plan, st, so, resync, zeroed, tid, LD, lane_in_row, stamps, it, seg_start, skip, buf_bit, dst);
     };
     stamps.walk_begins();
     stamps.stage(Stamps::kUnits);
@@ -479,7 +511,14 @@ __global__ __launch_bounds__(NT) void ll_factored_kernel(const DevModel m, const
             if (wave_builds) {
                 if (last_first && pb == t_begin + 1)
                     st.gone = 0u;
-                build(tile_at(pb), pb == t_begin || (last_first && (pb == t_begin + 1 || pb == last_item + 1)), Gs + lay.buf(pb));
+                const int it = tile_at(pb);
+                // the item's column limit: below all of this wave's copy numbers (wave-uniform) -- not at the walk's
+                // first position: the table is there from the first barrier on, and the last tile is built in full
+                bool skip = false;
+                if (PLAIN && pb > t_begin)
+                    skip = wave * kWave + 1 > __builtin_amdgcn_readfirstlane(col_hi[min(it, kWave - 1)]);
+                build(it, pb == t_begin || (last_first && (pb == t_begin + 1 || pb == last_item + 1)), skip, dbuf ? pb & 1 : 0,
+                      Gs + lay.buf(pb));
             }
         }
         stamps.lap(Stamps::kBuild);

@@ -9,9 +9,11 @@
 //   planner_charges                     the cost model's constants (and, in tuning builds, their overrides)
 //   deal_qblock                         units to waves, pieces, slots -> UnitTables
 //   slot_weights, pair_halves           per-lane starting weights; the half-1 partner of every half-0 unit
+//   column_limit                        what the kernel's column limit cannot learn from the bands (band.h)
 //   build_plan_part                     the driver over the stages above, for one part
 //   plain_order / shared_order ...      build_factored_plan's own stages: the order of the weight vectors, the parts
 //   build_list_plan                     the point lists of list mode, on the same UnitTables and PlanPack
+#include "band.h"
 #include "host.h"
 
 #include <initializer_list>
@@ -62,7 +64,7 @@ struct UnitTables {
 // follow from that list.  An array a builder does not list has no device pointer (nullptr).
 class PlanPack {
   public:
-    enum Array { Axes, QR4, PieceW, UnitRho, QT, QOrig, UnitTile, UnitHalf, UnitS0, UnitO0, UnitLen, UnitCont, UnitNsh, UnitPair, kArrays };
+    enum Array { Axes, QR4, PieceW, UnitRho, QT, QOrig, UnitTile, UnitHalf, UnitS0, UnitO0, UnitLen, UnitCont, UnitNsh, UnitPair, BandExtra, kArrays };
     PlanPack(std::initializer_list<std::pair<Array, const std::vector<double> *>> dbl,
              std::initializer_list<std::pair<Array, const std::vector<int32_t> *>> ints)
     {
@@ -171,6 +173,8 @@ void fill_plan(FactoredPlan &pl, const PartGeometry &geo, int n_pass, const Plan
     pl.unit_cont = pack.i32(PlanPack::UnitCont);
     pl.unit_nsh = pack.i32(PlanPack::UnitNsh); // (list modes are not the PLAIN kernel: not packed, never read)
     pl.unit_pair = pack.i32(PlanPack::UnitPair);
+    pl.band_extra = pack.i32(PlanPack::BandExtra); // (a dense grid's parts only)
+    pl.col_floor = geo.max_o;                      // (nothing above it is built: no wave skips)
     pl.unit_rho = pack.f64(PlanPack::UnitRho);
     pl.piece_w = pack.f64(PlanPack::PieceW);
     pl.q_r4 = pack.f64(PlanPack::QR4);
@@ -501,6 +505,25 @@ void pair_halves(UnitTables &ut, size_t block_slots)
     }
 }
 
+// The column limit (tiles.h FactoredPlan::col_floor, band_extra): the rule is band.h column_limit_of_block, q-block by
+// q-block; one floor for the part, the largest of its q-blocks'.
+int column_limit(const PartSpec &ps, const PartColumns &pc, const PartGeometry &geo, const UnitTables &ut, std::vector<int32_t> &extra)
+{
+    std::vector<int32_t> top((size_t)ps.n_qtiles(), 0); // the largest copy number a unit of the q-tile reads
+    for (size_t ls = 0; ls < pc.q_t.size(); ++ls)
+        top[ls / kQTileSlots] = std::max(top[ls / kQTileSlots], pc.q_t[ls] - 1);
+    const bool plain = ps.list_mode == 0 && ps.n_pass == 1;
+    const int n_build = std::min(geo.n_waves(), (geo.n_columns + 63) / 64);
+    extra.assign((size_t)geo.n_qblocks * kBandExtra, -1);
+    int floor = 1; // (copy number 1 is always read: the first builder wave never skips)
+    for (int blk = 0; blk < geo.n_qblocks; ++blk) {
+        const size_t b0 = (size_t)blk * geo.block_slots();
+        floor = std::max(floor, column_limit_of_block(&ut.tile[b0], &ut.nsh[b0], &ut.cont[b0], top.data(), geo.n_waves(), kMaxUnits,
+                                                      n_build, plain, 1, &extra[(size_t)blk * kBandExtra], kBandExtra));
+    }
+    return floor;
+}
+
 // Diagnostic builds only (tiles.h): the shipped library has no knob that changes values.
 void apply_diag_env(FactoredPlan &pl)
 {
@@ -549,12 +572,14 @@ int build_plan_part(covest_grid *g, const double *const *axes, const std::vector
         if (ut.tile[at] >= 0)
             slot_weights(at, ps, pc, ut, piece_w.data(), unit_rho.data());
     pair_halves(ut, geo.block_slots());
+    std::vector<int32_t> band_extra;
+    const int col_floor = column_limit(ps, pc, geo, ut, band_extra);
     // one buffer: doubles first (r4 | piece_w | rho), then int32 (q_T | q_orig | unit tables)
     PlanPack pack({{PlanPack::QR4, &pc.r4}, {PlanPack::PieceW, &piece_w}, {PlanPack::UnitRho, &unit_rho}},
                   {{PlanPack::QT, &pc.q_t}, {PlanPack::QOrig, &pc.q_orig}, {PlanPack::UnitTile, &ut.tile},
                    {PlanPack::UnitHalf, &ut.half}, {PlanPack::UnitS0, &ut.s0}, {PlanPack::UnitO0, &ut.o0},
                    {PlanPack::UnitLen, &ut.len}, {PlanPack::UnitCont, &ut.cont}, {PlanPack::UnitNsh, &ut.nsh},
-                   {PlanPack::UnitPair, &ut.pair}});
+                   {PlanPack::UnitPair, &ut.pair}, {PlanPack::BandExtra, &band_extra}});
     const int rc = upload_to_grid(g, buf, pack);
     if (rc != COVEST_OK)
         return rc;
@@ -573,6 +598,7 @@ int build_plan_part(covest_grid *g, const double *const *axes, const std::vector
     pl.p_clamp = clamp_for(m, qo.t_max);
     pl.ce_first = pl.ce_begin;
     pl.n_cols_partial = (int64_t)ps.n_qtiles() * kQTileSlots;
+    pl.col_floor = col_floor;
     apply_diag_env(pl);
     return COVEST_OK;
 }

@@ -157,6 +157,7 @@ constexpr int kSharedStepsPerMfma = 4; // cost of the shared steps in the assign
 constexpr int kMinSharedSteps = 3; // fewer shared steps than this are left to the MFMA steps
 constexpr int kLastBuilderExtra = 4; // extra charge of the builder of the top copy numbers when it shares a SIMD with another builder
 constexpr int kUnitOverhead = 2;   // per-unit cost besides its MFMA steps (logs, setup), same unit
+constexpr int kBandExtra = 4;      // builder-held long units a q-block whose bands the band-making waves make as well (FactoredPlan::band_extra)
 
 struct FactoredPlan {
     const double *c_axis, *e_axis; // device copies of axes 0 and 1
@@ -227,6 +228,15 @@ struct FactoredPlan {
                                    //   weight vectors (threshold_o beyond a workgroup's lanes), summed chunk by chunk
     int64_t ce_first;              // list_mode 3: the (c, e) of partial's first row
     int64_t n_cols_partial;        // list_mode 3: weight-vector slots per (c, e) in partial
+    // THE COLUMN LIMIT of a plain grid (ll_factored.hip col_hi): per item of the walk the largest copy
+    // number any unit of the workgroup reads with a weight that matters; a builder wave whose copy numbers all lie above
+    // it skips the item.  The waves that build nothing make it from their units' bands (band.h); what they cannot know:
+    int32_t col_floor;             // the largest copy number read by a unit whose band no wave makes: the units with fewer
+                                   //   than kBandMinShared shared steps, pieces, every unit where all waves build or the grid
+                                   //   is not PLAIN, and the builders' long units beyond band_extra (the largest over the q-blocks)
+    const int32_t *band_extra;     // [n_qblocks][kBandExtra] slots (wave * kMaxUnits + slot, inside the workgroup; -1: none)
+                                   //   of long units held by BUILDER waves, one per q-tile that no band-making wave holds:
+                                   //   the band-making waves make their bands too, entry j the (j mod makers)-th of them
     // The two fields below are read by DIAGNOSTIC builds only (-DCOVEST_DIAG, built to tools/bin/ by
     // `python -m covest_amd.build --out tools/bin/libcovest_amd_diag.so -DCOVEST_DIAG` and loaded through
     // COVEST_AMD_LIB): the shipped library never looks at them -- a knob that changes VALUES is a parity hazard.

@@ -315,9 +315,9 @@ int covest_grid_work(const covest_grid *g, double *pmf_terms, double *flops, con
 /* What the last evaluation launched, for tests: covest_grid_launch_record covers the last covest_grid_eval(_scan) of
  * the handle, covest_model_launch_record the last covest_eval_points of the model.  Text, one line each:
  *   "launch <instantiation> <launches>"   e.g. "launch ll_factored<512,tail,plain,ld290> 1"
- *   "plan n_threads=.. n_buf=.. ld=.. n_qblocks=.. shared_tiles=.. long=0|1 n_pass=.. list_mode=.."
+ *   "plan n_threads=.. n_buf=.. ld=.. n_qblocks=.. shared_tiles=.. long=0|1 n_pass=.. list_mode=.. col_floor=.."
  *     (a K-factored work description: shared_tiles = q-tiles with shared steps, long = a chunk of the long
- *     weight vectors).
+ *     weight vectors, col_floor = the largest copy number read by a unit that keeps its full range).
  * covest_compiled_variants lists every instantiation of the likelihood kernels linked into the library, one name a
  * line, from the tables the dispatchers record from (K-direct, the yardstick, is recorded as "ll_direct" or
  * "ll_direct_ref" and not listed).  All three are host bookkeeping: nothing is read from the device.  They write at

@@ -49,7 +49,10 @@ d = buf.reshape(-1, 8, 8)[:, :, :4].astype(np.float64)  # [wg][wave][build, cont
 extra = buf.reshape(-1, 8, 8)
 print("workgroups", d.shape[0])
 print("key tiles (of %d) whose 64 G columns of a builder wave were all zero: " % m.bins_evaluated +
-      "  ".join("wave %d: %.1f" % (w, extra[:, w, 5].mean()) for w in range(5)))
+      "  ".join("wave %d: %.2f" % (w, (extra[:, w, 5] & 0xFFFFF).mean()) for w in range(5)))
+# (the same word from bit 20 up: items the wave skipped by the column limit)
+print("items a builder wave skipped by the column limit: " +
+      "  ".join("wave %d: %.2f" % (w, (extra[:, w, 5] >> 20).mean()) for w in range(5)))
 tot = d.sum(axis=2)
 print("mean cycles per wave (s_memtime ticks): total %.0f" % tot.mean())
 for w in range(8):
