@@ -119,12 +119,7 @@ __global__ __launch_bounds__(256) void kmer_stats_kernel(const KmerTable t, unsi
             mx = e.count > mx ? e.count : mx;
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        distinct += __shfl_xor(distinct, off, kWave);
-        const unsigned long long o = __shfl_xor(mx, off, kWave);
-        mx = o > mx ? o : mx;
-    }
+    wave_fold_distinct_max(distinct, mx);
     if ((threadIdx.x & (kWave - 1)) == 0) {
         atomicMax(&stats[0], mx);
         atomicAdd(&stats[1], distinct);
@@ -178,20 +173,19 @@ hipError_t launch_kmer_count(const unsigned char *bases, const int64_t *offsets,
         // reads of one length: 64 consecutive windows per wave (kmer_count_fixed_kernel), at most 2^23 workgroups
         // of 256 windows per launch, cut at whole reads
         const int64_t n_windows = fixed_len - k + 1;
-        const int64_t reads_per_launch = std::max<int64_t>(1, (((int64_t)1 << 31) - 256) / n_windows);
+        const int64_t reads_per_launch = kmer_plan::window_reads_per_launch(n_windows);
         for (int64_t first = 0; first < n_reads; first += reads_per_launch) {
-            const int64_t n = std::min(n_reads - first, reads_per_launch);
+            const int64_t n = kmer_plan::reads_of_launch(first, n_reads, reads_per_launch);
             const int64_t total = n * n_windows;
             hipLaunchKernelGGL(kmer_count_fixed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
                                bases + first * fixed_len, n, fixed_len, k, canonical, t, overflow);
         }
         return hipGetLastError();
     }
-    // HIP wraps a grid of more than 2^32 threads silently: at most 2^23 workgroups per launch
     const int reads_per_block = 4;
-    const int64_t reads_per_launch = (int64_t)reads_per_block << 23;
+    const int64_t reads_per_launch = kmer_plan::wave_reads_per_launch(reads_per_block);
     for (int64_t first = 0; first < n_reads; first += reads_per_launch) {
-        const int64_t n = n_reads - first < reads_per_launch ? n_reads - first : reads_per_launch;
+        const int64_t n = kmer_plan::reads_of_launch(first, n_reads, reads_per_launch);
         const dim3 grid((unsigned)((n + reads_per_block - 1) / reads_per_block));
         hipLaunchKernelGGL(kmer_count_kernel, grid, dim3(reads_per_block * kWave), 0, stream,
                            offsets ? bases : bases + first * fixed_len, offsets ? offsets + first : nullptr, n,

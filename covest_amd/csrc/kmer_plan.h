@@ -33,6 +33,26 @@ inline int kmer_wide_words(int k)
     return k <= 31 ? 0 : k <= 63 ? 2 : k <= 127 ? 4 : 8;
 }
 
+// ---- the table paths' launches (kmer_count.hip, kmer_wide.hip): whole reads, `per` of them a launch ---------------------
+// A wave a read, reads_per_block reads a workgroup: HIP wraps a grid of more than 2^32 threads silently, so at most
+// 2^23 workgroups of 256 threads a launch.
+inline int64_t wave_reads_per_launch(int reads_per_block)
+{
+    return (int64_t)reads_per_block << 23;
+}
+
+// A thread a window, the windows of reads of one length numbered through: a launch's windows, rounded up to workgroups
+// of 256, stay below 2^31.
+inline int64_t window_reads_per_launch(int64_t n_windows)
+{
+    return std::max<int64_t>(1, (((int64_t)1 << 31) - 256) / n_windows);
+}
+
+inline int64_t reads_of_launch(int64_t first, int64_t n_reads, int64_t per) // reads of the launch that starts at `first`
+{
+    return std::min(n_reads - first, per);
+}
+
 // ---- pass 0 / 1: tiles of kTile bytes, kTilesPerBlock of them a workgroup --------------------------------------------
 constexpr int kTile = 256;        // bytes (threads) of a tile
 constexpr int kTilesPerBlock = 8; // consecutive tiles a workgroup works through (the unit of pass 0's sample)

@@ -1,29 +1,19 @@
 // kmer_table.h -- the open-addressing k-mer table of K-kmer (k <= 31) as device functions: shared by
 // kmer_count.hip (every occurrence goes to the table) and kmer_bulk.hip (only what its LDS path hands back does).
 // See kmer_count.hip for the reference it restates and for why a key's first slot is a function of its minimizer.
+// The arithmetic on the codes themselves: kmer_codes.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "kmer_codes.h"
+#include "wave.h"
 
 namespace covest {
 namespace kmer {
 
 constexpr unsigned long long kEmptyKey = ~0ull;
 constexpr int kMaxProbe = 1 << 16;
-
-// ASCII base -> 2-bit code for a/c/g/t in either case: bits 2:1 give a=0 c=1 t=2 g=3; x ^ (x>>1) swaps g,t.
-__device__ __forceinline__ unsigned base_code(unsigned char ch)
-{
-    const unsigned x = (ch >> 1) & 3u;
-    return x ^ (x >> 1);
-}
-
-// the low 2k bits: a k-mer's code
-__device__ __forceinline__ unsigned long long kmer_mask(int k)
-{
-    return k < 32 ? (1ull << (2 * k)) - 1ull : ~0ull;
-}
 
 // canonical keys: the smaller of a code and its reverse complement's comes first
 __device__ __forceinline__ void canonical_pair(unsigned long long &h, unsigned long long &rc, int canonical)
@@ -63,16 +53,6 @@ __device__ __forceinline__ unsigned long long slot_of(unsigned long long key, in
 // complement of `key` as a 2k-bit code (the function is symmetric in the two up to the mirrored position).
 constexpr int kLineLog2 = 3;
 constexpr int kLineSlots = 1 << kLineLog2;
-
-__device__ __forceinline__ unsigned long long revcomp_code(unsigned long long x, int k)
-{
-    unsigned long long rc = 0;
-    for (int i = 0; i < k; ++i) {
-        rc = (rc << 2) | (3ull - (x & 3ull));
-        x >>= 2;
-    }
-    return rc;
-}
 
 __device__ __forceinline__ bool has_first_slot(const KmerTable &t)
 {
@@ -130,6 +110,14 @@ __device__ __forceinline__ void table_add(const KmerTable t, unsigned long long 
     *overflow = 1;
 }
 
+// from the little-endian code of a window (base i at bits 2i, masked to 2k bits): the window's own code (mirrored:
+// first base in the highest bits) and its reverse complement's
+__device__ __forceinline__ void codes_from_le(unsigned long long le, int k, unsigned long long &h, unsigned long long &rc)
+{
+    rc = ~le & kmer_mask(k);
+    h = reverse_pairs64(le) >> (64 - 2 * k);
+}
+
 // The window starting at seq[s] of a read of `len` bases as 2-bit codes, little-endian (base i of the window at bits
 // 2i) -- that IS the reverse complement's code once complemented -- and mirrored (first base in the highest bits:
 // hash_kmer, bin/kmer_hist.py:18-23).  Four bases per (unaligned) 32-bit load where the read has them.
@@ -137,24 +125,17 @@ __device__ __forceinline__ void window_codes(const unsigned char *__restrict__ s
                                              unsigned long long &h, unsigned long long &rc)
 {
     const int n_words = (k + 3) >> 2; // 32-bit words of 4 bases that cover a window
-    const unsigned long long kmask = kmer_mask(k);
-    h = 0;
-    rc = 0;
     if (s + 4 * n_words <= len) {
         unsigned long long le = 0;
         for (int j = 0; j < n_words; ++j) {
             unsigned w;
             __builtin_memcpy(&w, seq + s + 4 * j, 4);
-            unsigned x = (w >> 1) & 0x03030303u;
-            x ^= (x >> 1) & 0x01010101u;
-            le |= (unsigned long long)((x * 0x01041040u) >> 24) << (8 * j);
+            le |= (unsigned long long)pack4(w) << (8 * j);
         }
-        le &= kmask;
-        rc = ~le & kmask;
-        unsigned long long r = __brevll(le);
-        r = ((r & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((r & 0x5555555555555555ull) << 1);
-        h = r >> (64 - 2 * k);
+        codes_from_le(low_bases(le, k), k, h, rc);
     } else { // the last windows of a read: byte by byte (a word would reach past the read's end)
+        h = 0;
+        rc = 0;
         for (int i = 0; i < k; ++i) {
             const unsigned long long c = base_code(seq[s + i]);
             h = (h << 2) | c;                  // hash_kmer, :18-23 (rehash :26-31 yields the same window code)
@@ -163,15 +144,16 @@ __device__ __forceinline__ void window_codes(const unsigned char *__restrict__ s
     }
 }
 
-// from the little-endian code of a window (base i at bits 2i, masked to 2k bits): the window's own code and its
-// reverse complement's
-__device__ __forceinline__ void codes_from_le(unsigned long long le, int k, unsigned long long &h, unsigned long long &rc)
+// {distinct keys, largest count} of a wave's lanes, in every lane (the stats kernels of both tables and pass 2 of
+// kmer_bulk.hip end with it)
+__device__ __forceinline__ void wave_fold_distinct_max(unsigned long long &distinct, unsigned long long &mx)
 {
-    const unsigned long long kmask = kmer_mask(k);
-    rc = ~le & kmask;
-    unsigned long long r = __brevll(le);
-    r = ((r & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((r & 0x5555555555555555ull) << 1);
-    h = r >> (64 - 2 * k);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        distinct += __shfl_xor(distinct, off, kWave);
+        const unsigned long long o = __shfl_xor(mx, off, kWave);
+        mx = o > mx ? o : mx;
+    }
 }
 
 } // namespace kmer

@@ -246,12 +246,7 @@ __global__ __launch_bounds__(256) void kmer_wide_stats_kernel(const KmerWideTabl
             mx = s > mx ? s : mx;
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        distinct += __shfl_xor(distinct, off, kWave);
-        const u64 o = __shfl_xor(mx, off, kWave);
-        mx = o > mx ? o : mx;
-    }
+    kmer::wave_fold_distinct_max(distinct, mx);
     if ((threadIdx.x & (kWave - 1)) == 0) {
         atomicMax(&stats[0], mx);
         atomicAdd(&stats[1], distinct);
@@ -273,11 +268,10 @@ template <int W>
 hipError_t count_w(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t fixed_len, int canonical,
                    const KmerWideTable &t, int *overflow, hipStream_t stream)
 {
-    // HIP wraps a grid of more than 2^32 threads silently: at most 2^23 workgroups per launch
     const int reads_per_block = 4;
-    const int64_t reads_per_launch = (int64_t)reads_per_block << 23;
+    const int64_t reads_per_launch = kmer_plan::wave_reads_per_launch(reads_per_block);
     for (int64_t first = 0; first < n_reads; first += reads_per_launch) {
-        const int64_t n = n_reads - first < reads_per_launch ? n_reads - first : reads_per_launch;
+        const int64_t n = kmer_plan::reads_of_launch(first, n_reads, reads_per_launch);
         const dim3 grid((unsigned)((n + reads_per_block - 1) / reads_per_block));
         hipLaunchKernelGGL((kmer_wide_count_kernel<W>), grid, dim3(reads_per_block * kWave), 0, stream,
                            offsets ? bases : bases + first * fixed_len, offsets ? offsets + first : nullptr, n, fixed_len,

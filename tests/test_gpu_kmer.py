@@ -316,7 +316,7 @@ for r in range(len(misled)):
 info = run("misled sample", misled, 21, True, fixed_len=100, expect="partitioned")
 assert info["overflowed_records"] > 0 and info["buckets_through_table"] > 0, info
 # one minimizer, thousands of distinct k-mers around it: more than a workgroup's LDS table holds -- to the table.
-# (white box: the m-mer hash of kmer_bulk.hip restated to find a 13-mer that wins wherever it occurs)
+# (white box: the m-mer hash of kmer_scatter.h restated to find a 13-mer that wins wherever it occurs)
 def mmer_hash(code, m=13):
     rc = 0
     for j in range(m):
