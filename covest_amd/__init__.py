@@ -25,3 +25,5 @@ from . import jackknife  # noqa: F401,E402
 from .jackknife import leave_group_out_histograms, read_jackknife, summarize_jackknife, jackknife_batch  # noqa: F401,E402
 from . import posterior  # noqa: F401,E402
 from .posterior import posterior_classes, PosteriorClasses  # noqa: F401,E402
+from . import read_errors  # noqa: F401,E402
+from .read_errors import abundance_weights, read_error_scores, ReadErrorScores  # noqa: F401,E402

@@ -1,5 +1,6 @@
 // kmer_table.h -- the open-addressing k-mer table of K-kmer (k <= 31) as device functions: shared by
-// kmer_count.hip (every occurrence goes to the table) and kmer_bulk.hip (only what its LDS path hands back does).
+// kmer_count.hip (every occurrence goes to the table), kmer_bulk.hip (only what its LDS path hands back does) and
+// kmer_lookup.hip (which only reads it: table_find).
 // See kmer_count.hip for the reference it restates and for why a key's first slot is a function of its minimizer.
 // The arithmetic on the codes themselves: kmer_codes.h.
 #pragma once
@@ -108,6 +109,40 @@ __device__ __forceinline__ void table_add(const KmerTable t, unsigned long long 
         h = (h + 1) & t.mask;
     }
     *overflow = 1;
+}
+
+// A slot as ONE 16-byte load of {key, count} (x = key, y = count): a plain load -- the kernels that look counts up run
+// after the kernels that added them, so no atomic and no agent-scope load is needed (kmer_lookup.hip).
+__device__ __forceinline__ ulonglong2 slot_load(const KmerTable &t, unsigned long long h)
+{
+    static_assert(sizeof(KmerSlot) == sizeof(ulonglong2), "a slot is one 16-byte load");
+    return *reinterpret_cast<const ulonglong2 *>(t.slots + h);
+}
+
+// The count the table holds for `key` (0: it holds none), without a store.  It replays table_add's decisions: the
+// first slot holds the key (its count), is empty (0: the key would have been put there) or holds another key; then
+// from the plain hash on, a slot with the key gives its count and an empty one 0; after kMaxProbe probes 0 -- the add
+// would have overflowed.  Slots never change their key and nothing is deleted, so every slot an add of `key` passed
+// over still holds the key it held then: exact for every key, also after a rehash (it inserts by table_add).
+__device__ __forceinline__ unsigned long long table_find(const KmerTable &t, unsigned long long key, unsigned long long rc)
+{
+    if (has_first_slot(t)) {
+        const ulonglong2 e = slot_load(t, first_slot(key, rc, t));
+        if (e.x == key)
+            return e.y;
+        if (e.x == kEmptyKey)
+            return 0ull;
+    }
+    unsigned long long h = slot_of(key, t.log2_slots);
+    for (int probe = 0; probe < kMaxProbe; ++probe) {
+        const ulonglong2 e = slot_load(t, h);
+        if (e.x == key)
+            return e.y;
+        if (e.x == kEmptyKey)
+            return 0ull;
+        h = (h + 1) & t.mask;
+    }
+    return 0ull;
 }
 
 // from the little-endian code of a window (base i at bits 2i, masked to 2k bits): the window's own code (mirrored:

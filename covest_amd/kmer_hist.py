@@ -77,6 +77,87 @@ def scatter_rate(slots, ops=1 << 28, device=0):
     return out.value
 
 
+NO_WINDOW = 0xFFFFFFFF  # in the flat abundance array: no window starts at this base
+
+
+def _packed_reads(reads):
+    """(bases uint8[...], offsets int64[n + 1]) of what KmerCounts.lookup takes: a list of strings, a pair (bases,
+    offsets), an (n, L) uint8 array or an object that carries one as `.bases` (SimulatedReads).  ValueError for
+    malformed arrays, KeyError for a base outside acgt -- both before the library is asked."""
+    if hasattr(reads, "bases") and getattr(reads.bases, "ndim", 0) == 2:
+        reads = reads.bases
+    if isinstance(reads, np.ndarray):
+        if reads.dtype != np.uint8 or reads.ndim != 2:
+            raise ValueError("reads as one array must be (n, L) uint8")
+        blob = np.ascontiguousarray(reads).reshape(-1)
+        offsets = np.arange(reads.shape[0] + 1, dtype=np.int64) * reads.shape[1]
+    elif isinstance(reads, tuple) and len(reads) == 2 and not isinstance(reads[0], str):
+        blob, offsets = np.asarray(reads[0]), np.asarray(reads[1])
+        if blob.dtype != np.uint8 or blob.ndim != 1:
+            raise ValueError("bases must be a one-dimensional uint8 array")
+        if offsets.ndim != 1 or offsets.size < 1 or offsets.dtype.kind not in "iu":
+            raise ValueError("offsets must be a one-dimensional integer array of n_reads + 1 entries")
+        blob, offsets = np.ascontiguousarray(blob), np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets[0] < 0 or (np.diff(offsets) < 0).any():
+            raise ValueError("offsets must ascend from a non-negative start")
+        if offsets[-1] > blob.size:
+            raise ValueError("offsets reach beyond the bases")
+    else:
+        reads = [r if isinstance(r, str) else str(r) for r in reads]
+        lens = np.fromiter((len(r) for r in reads), dtype=np.int64, count=len(reads))
+        offsets = np.zeros(len(reads) + 1, dtype=np.int64)
+        np.cumsum(lens, out=offsets[1:])
+        try:
+            blob = np.frombuffer("".join(reads).encode("ascii"), dtype=np.uint8)
+        except UnicodeEncodeError:
+            raise KeyError("base outside acgt")
+    used = blob[int(offsets[0]):int(offsets[-1])]
+    if used.size and not _VALID[used].all():
+        raise KeyError("base outside acgt")  # single_hash raises KeyError (bin/kmer_hist.py:15)
+    return blob, offsets
+
+
+def _or_minus_one(column):
+    out = column.astype(np.int64)
+    out[column == NO_WINDOW] = -1
+    return out
+
+
+class ReadAbundances:
+    """What KmerCounts.lookup returns.  `abundance`: the flat uint32 array indexed like the bases from offsets[0] on
+    (None with per_window=False) -- at a window's first base min(count, 0xFFFFFFFE), NO_WINDOW at the last k - 1 bases
+    of a read; `offsets` (n + 1,) int64 from 0; `windows(i)`: the valid entries of read i; per read, int64 with -1 for
+    "none": `min_abundance` (no window), `weak` (never -1), `first_weak` / `last_weak` (window indices; no weak
+    window); `score` (float64, None without weights); `k`, `cutoff`."""
+
+    def __init__(self, k, offsets, abundance, summary, score, cutoff):
+        self.k = int(k)
+        self.offsets = offsets
+        self.abundance = abundance
+        self.summary = summary
+        self.score = score
+        self.cutoff = int(cutoff)
+        self.min_abundance = _or_minus_one(summary[:, 0])
+        self.weak = summary[:, 1].astype(np.int64)
+        self.first_weak = _or_minus_one(summary[:, 2])
+        self.last_weak = _or_minus_one(summary[:, 3])
+
+    @property
+    def n_reads(self):
+        return self.offsets.size - 1
+
+    @property
+    def n_windows(self):
+        """Windows per read: max(length - k + 1, 0)."""
+        return np.maximum(np.diff(self.offsets) - self.k + 1, 0)
+
+    def windows(self, i):
+        if self.abundance is None:
+            raise ValueError("the lookup was made with per_window=False")
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        return self.abundance[a:max(a, b - self.k + 1)]
+
+
 class KmerCounts:
     """The `counts` of compute_counts: an open-addressing table in HBM (covest_kmer*)."""
 
@@ -185,6 +266,49 @@ class KmerCounts:
         else:
             self.add_device(d_bases_ptr, n_reads, read_len, stream=stream)
         return "table"
+
+    def lookup(self, reads, cutoff=0, weights=None, per_window=True):
+        """The abundance the table holds for every k-mer of `reads` (covest_kmer_lookup_reads; k <= 31, read-only) ->
+        ReadAbundances.  `reads`: a list of preprocessed strings (KeyError for a base outside acgt, like add_reads) or a
+        pair (bases, offsets) in the packed layout.  `cutoff`: a window is weak when its abundance is below it (0: none
+        is).  `weights`: a table of doubles; the score of a read is the sum over its windows of
+        weights[min(abundance, len(weights) - 1)], in a fixed order (the same bits on every run).  per_window=False:
+        only the per-read summaries come back.  A read shorter than k has no window (the key add_reads counts for it is
+        not looked up)."""
+        blob, offsets = _packed_reads(reads)
+        cutoff = int(cutoff)
+        if not 0 <= cutoff <= 0xFFFFFFFF:
+            raise ValueError("cutoff must fit 32 bits, not negative")
+        if weights is not None:
+            weights = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+            if weights.ndim != 1 or weights.size < 1 or weights.size >= 1 << 31:
+                raise ValueError("weights must be a one-dimensional table of at least one number")
+        n = offsets.size - 1
+        n_pos = int(offsets[-1] - offsets[0])
+        abundance = np.empty(n_pos, dtype=np.uint32) if per_window else None
+        summary = np.empty((n, 4), dtype=np.uint32)
+        score = np.empty(n, dtype=np.float64) if weights is not None else None
+        if n:
+            def ptr(a):
+                return ctypes.c_void_p(a.ctypes.data if a is not None else 0)
+            _capi.check(_capi.lib().covest_kmer_lookup_reads(
+                self._handle, ptr(blob), ptr(offsets), n, cutoff, ptr(weights), 0 if weights is None else weights.size,
+                ptr(abundance), ptr(summary), ptr(score)), "covest_kmer_lookup_reads")
+        return ReadAbundances(self.k, offsets - offsets[0], abundance, summary, score, cutoff)
+
+    def lookup_device(self, d_bases_ptr, n_reads, read_len, d_offsets_ptr=None, cutoff=0, d_weights_ptr=None, n_weights=0,
+                      d_abundance_ptr=None, d_summary_ptr=None, d_score_ptr=None, stream=None):
+        """The same for reads resident in HBM into device arrays (raw pointers; covest_kmer_lookup_reads_device):
+        asynchronous on `stream`, which must be the stream of the adds it is to see (or ordered after them by the
+        caller).  Every output is optional; `d_abundance_ptr` is indexed like the bases, `d_summary_ptr` holds
+        uint32[n_reads][4] (16-byte aligned), `d_score_ptr` doubles.  It does not look at the overflow flag."""
+        _capi.require_shared_runtime("KmerCounts.lookup_device")
+        _capi.check(_capi.lib().covest_kmer_lookup_reads_device(
+            self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0), int(n_reads), int(read_len),
+            int(cutoff), ctypes.c_void_p(d_weights_ptr or 0), int(n_weights), ctypes.c_void_p(d_abundance_ptr or 0),
+            ctypes.c_void_p(d_summary_ptr or 0), ctypes.c_void_p(d_score_ptr or 0), ctypes.c_void_p(stream or 0)),
+            "covest_kmer_lookup_reads_device")
+        return self
 
     def memory_limit(self, max_bytes):
         """Bytes the partitioned path may allocate for its buckets' records (0: no cap but the free device memory); a

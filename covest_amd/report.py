@@ -27,7 +27,7 @@ def _finite_int(x):
 def print_output(hist_orig, model, success, sample_factor, estimated=None, guess=None, orig=None,
                  reads_size=None, silent=False, orig_sample_factor=1, starting_points=1,
                  use_grid_search=False, intervals=None, information=None, bootstrap=None, jackknife=None,
-                 posterior=None):
+                 posterior=None, read_errors=None):
     """`intervals`: the dict covest_amd.profile.coverage_interval returns; the record then carries the likelihood-ratio
     interval of the coverage, of the genome size and its level.  Without it the record is the reference's, key for key.
     `information`: the dict covest_amd.information.observed_information returns (a key 'level' in it chooses the Wald
@@ -54,7 +54,11 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
     posterior_error_free_kmers, one posterior_copies_* per copy column (expected_kmers), posterior_undefined_kmers and
     posterior_sample_factor.  They are numbers of the histogram the model was fitted to: for a sample factor other than
     1 they are recorded as such, with the factor beside them, and are NOT scaled back to the un-sampled data (DESIGN.md
-    6ab).  Without it the record is unchanged."""
+    6ab).  Without it the record is unchanged.
+    `read_errors`: the ReadErrorScores covest_amd.read_errors.read_error_scores returns; the record then carries
+    read_errors_cutoff, read_errors_level, read_errors_reads, read_errors_flagged_share, read_errors_predicted_share
+    (the model's share of reads with a wrong base, NOT the detector's expectation: DESIGN.md 6ae) and
+    read_errors_mean_expected_erroneous_kmers.  Without it the record is unchanged."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -164,6 +168,15 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
         for name, value in posterior.expected_kmers().items():
             record['posterior_%s%s' % (name, '' if name.startswith('copies_') else '_kmers')] = float(value)
         record['posterior_sample_factor'] = sample_factor
+    if read_errors is not None:
+        n = int(read_errors.n_reads)
+        record['read_errors_cutoff'] = int(read_errors.cutoff)
+        record['read_errors_level'] = None if read_errors.level is None else float(read_errors.level)
+        record['read_errors_reads'] = n
+        record['read_errors_flagged_share'] = float(read_errors.flagged_share)
+        record['read_errors_predicted_share'] = float(read_errors.predicted_share)
+        record['read_errors_mean_expected_erroneous_kmers'] = (
+            float(sum(read_errors.expected_erroneous_kmers.tolist()) / n) if n else float('nan'))
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

@@ -400,6 +400,35 @@ int64_t covest_kmer_slots(const covest_kmer *c);
 /* Forget every count (counts = defaultdict(int) again), keeping the table's size; asynchronous on `stream`.  After
  * covest_kmer_count_reads_device it also frees the buckets' records (gigabytes the handle keeps from call to call). */
 int covest_kmer_clear(covest_kmer *c, void *stream);
+/* The per-read use of the table (k <= 31; no reference counterpart): for every window of every read the count the
+ * table holds for its key, and reductions of those counts per read.  Read-only: nothing is written to the table.
+ * Every output is optional (NULL: not wanted).
+ *   abundance  uint32, indexed like the bases: the entry at a window's first base is min(count, 0xFFFFFFFE); the last
+ *              k - 1 positions of a read (all of a read shorter than k) hold 0xFFFFFFFF, "no window starts here".
+ *              Every position in [offsets[0], offsets[n_reads]) -- reads of one length: [0, n_reads * read_len) -- is
+ *              written exactly once, nothing outside.
+ *   summary    uint32[n_reads][4] = {min_abundance, weak, first_weak, last_weak}: weak = windows with abundance <
+ *              cutoff, first_weak / last_weak their first and last window index.  A read without windows gives
+ *              {0xFFFFFFFF, 0, 0xFFFFFFFF, 0xFFFFFFFF}; one without a weak window has both indices 0xFFFFFFFF;
+ *              cutoff 0: no window is weak.  A read has fewer than 2^32 - 1 windows.
+ *   score      double[n_reads] = sum over the windows of weights[min(count, n_weights - 1)], n_weights >= 1, summed in
+ *              a fixed order (csrc/kmer_lookup.h): the same bits on every run.  A read without windows scores 0.0.
+ * A read shorter than k has no window: the key covest_kmer_add counts for it (the hash of what there is) is
+ * deliberately NOT looked up.
+ * Device form: asynchronous on `stream`; d_bases at any alignment, the outputs naturally aligned (a summary row is
+ * one 16-byte store); d_offsets NULL: every read is read_len bases.  The call must be ORDERED AFTER the adds it is to
+ * see -- the same stream, or the caller's own synchronisation -- and never looks at the overflow flag.
+ * Host form: copies, waits, and answers COVEST_E_NOMEM if an add overflowed (sticky until covest_kmer_clear: the
+ * counts are then partial); `abundance` holds offsets[n_reads] - offsets[0] entries, indexed relative to offsets[0].
+ * COVEST_E_UNSUPPORTED: k > 31.  COVEST_E_INVALID: a null counter, negative sizes, a score without weights or with
+ * n_weights < 1, no offsets and read_len < 0, or a counter that holds a covest_kmer_count_reads_device result (its
+ * keys are not in the table).  n_reads == 0: COVEST_OK, nothing launched. */
+int covest_kmer_lookup_reads_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                                    int64_t read_len, uint32_t cutoff, const double *d_weights, int32_t n_weights,
+                                    uint32_t *d_abundance, uint32_t *d_summary, double *d_score, void *stream);
+int covest_kmer_lookup_reads(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
+                             uint32_t cutoff, const double *weights, int32_t n_weights, uint32_t *abundance,
+                             uint32_t *summary, double *score);
 
 /* ---- FASTA / FASTQ front-end of the k-mer histogram: bin/kmer_hist.py:44-54 preprocess, :67-74 load_reads ----
  * HOST code (the only HIP calls: a device count and the allocation of page-locked buffers): the mapped file
