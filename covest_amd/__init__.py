@@ -27,3 +27,4 @@ from . import posterior  # noqa: F401,E402
 from .posterior import posterior_classes, PosteriorClasses  # noqa: F401,E402
 from . import read_errors  # noqa: F401,E402
 from .read_errors import abundance_weights, read_error_scores, ReadErrorScores  # noqa: F401,E402
+from .read_errors import correct_reads, ReadCorrections  # noqa: F401,E402

@@ -34,6 +34,7 @@ EXPORTS = (
     "covest_kmer_add_device", "covest_kmer_histogram", "covest_kmer_slots", "covest_kmer_clear",
     "covest_kmer_count_reads_device", "covest_kmer_partition_info", "covest_kmer_partition_ms", "covest_kmer_memory_limit",
     "covest_kmer_scatter_rate", "covest_kmer_lookup_reads", "covest_kmer_lookup_reads_device",
+    "covest_kmer_correct_reads", "covest_kmer_correct_reads_device",
     "covest_reads_open", "covest_reads_close", "covest_reads_next", "covest_reads_bytes",
     "covest_thin_histogram", "covest_thin_histogram_timed",
     "covest_truncated_poisson", "covest_truncated_poisson_table",
@@ -213,6 +214,10 @@ def lib():
     L.covest_kmer_lookup_reads_device.argtypes = [vp, vp, vp, i64, i64, ctypes.c_uint32, vp, i32, vp, vp, vp, vp]
     L.covest_kmer_lookup_reads.restype = ctypes.c_int
     L.covest_kmer_lookup_reads.argtypes = [vp, vp, vp, i64, ctypes.c_uint32, vp, i32, vp, vp, vp]
+    L.covest_kmer_correct_reads_device.restype = ctypes.c_int
+    L.covest_kmer_correct_reads_device.argtypes = [vp, vp, vp, i64, i64, ctypes.c_uint32, vp, vp, vp]
+    L.covest_kmer_correct_reads.restype = ctypes.c_int
+    L.covest_kmer_correct_reads.argtypes = [vp, vp, vp, i64, ctypes.c_uint32, vp, vp]
     L.covest_reads_open.restype = ctypes.c_int
     L.covest_reads_open.argtypes = [ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.covest_reads_close.restype = None

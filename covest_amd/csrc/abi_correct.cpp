@@ -1,0 +1,89 @@
+// abi_correct.cpp -- covest_kmer_correct_reads* of the C ABI over kmer_correct.hip: isolated substitutions of reads
+// corrected from the counter's table.  Nothing here, or below it, writes to the table.
+#include "host.h"
+#include "kmer_correct.h"
+
+using namespace covest;
+
+extern "C" {
+
+int covest_kmer_correct_reads_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                                     int64_t read_len, uint32_t cutoff, uint8_t *d_out, uint32_t *d_fix, void *stream)
+{
+    const std::string name("covest_kmer_correct_reads_device");
+    if (!c)
+        return fail(COVEST_E_INVALID, name + ": null counter");
+    std::lock_guard<std::mutex> guard(c->lock);
+    if (n_reads < 0 || (!d_offsets && (read_len < 0 || read_len >= ((int64_t)1 << 32))))
+        return fail(COVEST_E_INVALID, name + ": negative size, or no offsets and no read_len below 2^32");
+    if ((uintptr_t)d_fix % (4 * sizeof(uint32_t)))
+        return fail(COVEST_E_INVALID, name + ": fix is not aligned to its rows of 16 bytes");
+    if (c->wide)
+        return fail(COVEST_E_UNSUPPORTED, name + ": k must be at most 31 (keys of one word)");
+    if (c->bulk)
+        return fail(COVEST_E_INVALID, name + ": the counter holds a covest_kmer_count_reads_device result "
+                                             "(its keys are not in the table); covest_kmer_clear first");
+    if (n_reads == 0)
+        return COVEST_OK;
+    if (!d_bases || !d_out)
+        return fail(COVEST_E_INVALID, name + ": null bases or null out");
+    if (!d_offsets && d_out != d_bases) { // (with offsets the extent of the reads is on the device: not seen from here)
+        const uintptr_t a = (uintptr_t)d_bases, b = (uintptr_t)d_out, n_bytes = (uintptr_t)n_reads * (uintptr_t)read_len;
+        if (a < b + n_bytes && b < a + n_bytes)
+            return fail(COVEST_E_INVALID, name + ": out overlaps the bases without being the bases (in place: out == bases)");
+    }
+    DeviceGuard dev_guard(c->device);
+    if (dev_guard.status() != COVEST_OK)
+        return dev_guard.status();
+    HIP_TRY(launch_kmer_correct(d_bases, d_offsets, n_reads, read_len, c->canonical, c->table, cutoff, d_out, d_fix,
+                                static_cast<hipStream_t>(stream)));
+    return COVEST_OK;
+}
+
+int covest_kmer_correct_reads(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
+                              uint32_t cutoff, uint8_t *out, uint32_t *fix)
+{
+    if (!c || n_reads < 0 || (n_reads > 0 && !offsets))
+        return fail(COVEST_E_INVALID, "covest_kmer_correct_reads: bad argument");
+    if (c->wide)
+        return fail(COVEST_E_UNSUPPORTED, "covest_kmer_correct_reads: k must be at most 31 (keys of one word)");
+    if (n_reads == 0)
+        return COVEST_OK;
+    const int64_t n_bytes = offsets[n_reads] - offsets[0];
+    if (n_bytes < 0 || (n_bytes > 0 && !bases) || !out)
+        return fail(COVEST_E_INVALID, "covest_kmer_correct_reads: bad offsets, or null bases or null out");
+    DeviceGuard dev_guard(c->device);
+    if (dev_guard.status() != COVEST_OK)
+        return dev_guard.status();
+    const size_t n_pos = (size_t)n_bytes, n = (size_t)n_reads;
+    DevBuf d_fix; // (goes with the call; the copies back have waited for the kernel)
+    {
+        std::lock_guard<std::mutex> guard(c->lock);
+        HIP_TRY(c->ws_bases.reserve(std::max<size_t>(n_pos, 1)));
+        HIP_TRY(c->ws_offsets.reserve((n + 1) * sizeof(int64_t)));
+        if (n_pos)
+            HIP_TRY(hipMemcpy(c->ws_bases.ptr, bases + offsets[0], n_pos, hipMemcpyHostToDevice));
+        std::vector<int64_t> rel(n + 1);
+        for (size_t i = 0; i <= n; ++i)
+            rel[i] = offsets[i] - offsets[0];
+        HIP_TRY(hipMemcpy(c->ws_offsets.ptr, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    }
+    if (fix)
+        HIP_TRY(d_fix.reserve(n * 4 * sizeof(uint32_t)));
+    // in place on the staged copy of the bases: only the corrected bytes are stored
+    COVEST_TRY(covest_kmer_correct_reads_device(c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(), n_reads, 0, cutoff,
+                                                c->ws_bases.as<uint8_t>(), fix ? d_fix.as<uint32_t>() : nullptr, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    int flag = 0; // sticky until covest_kmer_clear: an add overflowed, so the counts are partial
+    HIP_TRY(hipMemcpy(&flag, c->flag.ptr, sizeof(int), hipMemcpyDeviceToHost));
+    if (flag)
+        return fail(COVEST_E_NOMEM, "covest_kmer_correct_reads: k-mer table overflow, the counts are partial: "
+                                    "covest_kmer_clear and recount with more slots");
+    if (n_pos)
+        HIP_TRY(hipMemcpy(out, c->ws_bases.ptr, n_pos, hipMemcpyDeviceToHost));
+    if (fix)
+        HIP_TRY(hipMemcpy(fix, d_fix.ptr, n * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return COVEST_OK;
+}
+
+} // extern "C"

@@ -158,6 +158,30 @@ class ReadAbundances:
         return self.abundance[a:max(a, b - self.k + 1)]
 
 
+class CorrectedReads:
+    """What KmerCounts.correct returns.  `bases`: the flat uint8 array of the reads after correction, indexed from
+    offsets[0] on; `offsets` (n + 1,) int64 from 0; per read, int64: `runs` of weak windows, and how many of them were
+    `corrected`, `ambiguous`, `unfixable` (runs is their sum); `changed`: the flat positions where `bases` differs from
+    the input; `strings()`: the reads as strings; `k`, `cutoff`."""
+
+    def __init__(self, k, bases, offsets, fix, changed, cutoff):
+        self.k = int(k)
+        self.bases = bases
+        self.offsets = offsets
+        self.fix = fix
+        self.changed = changed
+        self.cutoff = int(cutoff)
+        self.runs, self.corrected, self.ambiguous, self.unfixable = (fix[:, j].astype(np.int64) for j in range(4))
+
+    @property
+    def n_reads(self):
+        return self.offsets.size - 1
+
+    def strings(self):
+        text = self.bases.tobytes().decode("ascii")
+        return [text[int(a):int(b)] for a, b in zip(self.offsets[:-1], self.offsets[1:])]
+
+
 class KmerCounts:
     """The `counts` of compute_counts: an open-addressing table in HBM (covest_kmer*)."""
 
@@ -308,6 +332,40 @@ class KmerCounts:
             int(cutoff), ctypes.c_void_p(d_weights_ptr or 0), int(n_weights), ctypes.c_void_p(d_abundance_ptr or 0),
             ctypes.c_void_p(d_summary_ptr or 0), ctypes.c_void_p(d_score_ptr or 0), ctypes.c_void_p(stream or 0)),
             "covest_kmer_lookup_reads_device")
+        return self
+
+    def correct(self, reads, cutoff):
+        """Isolated substitutions of `reads` corrected from the table (covest_kmer_correct_reads; k <= 31, read-only on
+        the table) -> CorrectedReads.  `reads`: what lookup takes.  A window is weak when its abundance is below
+        `cutoff`; for every run of weak windows the other three bases are tried at the position(s) the run names, and
+        the base is replaced when exactly one alternative lifts every window of the run to the cutoff (the rule:
+        include/covest_amd.h).  Two errors closer than k + 1 merge into one run and stay."""
+        blob, offsets = _packed_reads(reads)
+        cutoff = int(cutoff)
+        if not 0 <= cutoff <= 0xFFFFFFFF:
+            raise ValueError("cutoff must fit 32 bits, not negative")
+        n = offsets.size - 1
+        before = blob[int(offsets[0]):int(offsets[-1])]
+        out = np.empty(before.size, dtype=np.uint8)
+        fix = np.zeros((n, 4), dtype=np.uint32)
+        if n:
+            _capi.check(_capi.lib().covest_kmer_correct_reads(
+                self._handle, ctypes.c_void_p(blob.ctypes.data), ctypes.c_void_p(offsets.ctypes.data), n, cutoff,
+                ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(fix.ctypes.data)), "covest_kmer_correct_reads")
+        return CorrectedReads(self.k, out, offsets - offsets[0], fix, np.flatnonzero(out != before), cutoff)
+
+    def correct_device(self, d_bases_ptr, n_reads, read_len, d_out_ptr, d_offsets_ptr=None, cutoff=0, d_fix_ptr=None,
+                       stream=None):
+        """The same for reads resident in HBM into device arrays (raw pointers; covest_kmer_correct_reads_device):
+        asynchronous on `stream`, which must be the stream of the adds it is to see (or ordered after them by the
+        caller).  `d_out_ptr` is indexed like the bases and may be `d_bases_ptr` itself (in place); otherwise the two
+        must not overlap.  `d_fix_ptr` (optional) holds uint32[n_reads][4] = {runs, corrected, ambiguous, unfixable},
+        16-byte aligned.  It does not look at the overflow flag."""
+        _capi.require_shared_runtime("KmerCounts.correct_device")
+        _capi.check(_capi.lib().covest_kmer_correct_reads_device(
+            self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0), int(n_reads), int(read_len),
+            int(cutoff), ctypes.c_void_p(d_out_ptr or 0), ctypes.c_void_p(d_fix_ptr or 0), ctypes.c_void_p(stream or 0)),
+            "covest_kmer_correct_reads_device")
         return self
 
     def memory_limit(self, max_bytes):

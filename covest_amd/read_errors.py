@@ -5,6 +5,8 @@ the fitted mixture's posterior classes.
     scores = read_error_scores(model, estimate, counts, reads)
     scores.flagged            # reads with a k-mer below the posterior's error cutoff
     scores.locate_single_errors()
+    fixed = correct_reads(model, estimate, counts, reads)
+    fixed.strings()           # the reads with their isolated substitutions corrected (section 6af)
 
 The lookup is the device's (KmerCounts.lookup: csrc/kmer_lookup.hip); everything here is plain numpy on what it
 returns.  A flag is a statement about a READ under the model's assumption that k-mers are independent draws of the
@@ -13,6 +15,7 @@ genomic one's, nothing is said about its sequence.
 """
 import numpy as np
 
+from .kmer_hist import CorrectedReads
 from .posterior import posterior_classes
 
 KINDS = ("erroneous", "log_error_free")
@@ -110,3 +113,36 @@ def read_error_scores(model, estimate, counts, reads, level=0.5, cutoff=None):
     found = counts.lookup(reads, cutoff=int(cutoff), weights=weights, per_window=False)
     return ReadErrorScores(counts.k, np.diff(found.offsets), found.min_abundance, found.weak, found.first_weak,
                            found.last_weak, found.score, cutoff, level, estimate[1], weights=weights)
+
+
+class ReadCorrections(CorrectedReads):
+    """What correct_reads returns: the CorrectedReads of KmerCounts.correct (`bases`, `offsets`, `runs`, `corrected`,
+    `ambiguous`, `unfixable`, `changed`, `strings()`, `k`, `cutoff`) and `level`.  `corrected_share`: the share of
+    reads that had runs of weak windows, all of them corrected; `unresolved_share`: the share of reads that keep a run
+    (ambiguous or unfixable)."""
+
+    def __init__(self, found, level):
+        super().__init__(found.k, found.bases, found.offsets, found.fix, found.changed, found.cutoff)
+        self.level = None if level is None else float(level)
+
+    @property
+    def corrected_share(self):
+        return float(((self.runs > 0) & (self.corrected == self.runs)).mean()) if self.n_reads else float("nan")
+
+    @property
+    def unresolved_share(self):
+        return float((self.corrected < self.runs).mean()) if self.n_reads else float("nan")
+
+
+def correct_reads(model, estimate, counts, reads, level=0.5, cutoff=None):
+    """The isolated substitutions of `reads` corrected from `counts` (a KmerCounts that holds them, k = model.k) at the
+    posterior's error cutoff -> ReadCorrections.  `cutoff` defaults to posterior_classes(model, estimate)
+    .error_cutoff(level), as in read_error_scores; ValueError where the posterior gives none.  The same caveat holds:
+    the table holds the abundances of the whole read set, so `model` must have been fitted to their histogram at sample
+    factor 1.  Only isolated substitutions are corrected (KmerCounts.correct); the table is not changed, so a second
+    pass needs a recount of the corrected reads."""
+    if cutoff is None:
+        cutoff = posterior_classes(model, estimate).error_cutoff(level)
+        if cutoff is None:
+            raise ValueError("the posterior classes give no error cutoff at level %g" % level)
+    return ReadCorrections(counts.correct(reads, int(cutoff)), level)

@@ -27,7 +27,7 @@ def _finite_int(x):
 def print_output(hist_orig, model, success, sample_factor, estimated=None, guess=None, orig=None,
                  reads_size=None, silent=False, orig_sample_factor=1, starting_points=1,
                  use_grid_search=False, intervals=None, information=None, bootstrap=None, jackknife=None,
-                 posterior=None, read_errors=None):
+                 posterior=None, read_errors=None, corrections=None):
     """`intervals`: the dict covest_amd.profile.coverage_interval returns; the record then carries the likelihood-ratio
     interval of the coverage, of the genome size and its level.  Without it the record is the reference's, key for key.
     `information`: the dict covest_amd.information.observed_information returns (a key 'level' in it chooses the Wald
@@ -58,7 +58,10 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
     `read_errors`: the ReadErrorScores covest_amd.read_errors.read_error_scores returns; the record then carries
     read_errors_cutoff, read_errors_level, read_errors_reads, read_errors_flagged_share, read_errors_predicted_share
     (the model's share of reads with a wrong base, NOT the detector's expectation: DESIGN.md 6ae) and
-    read_errors_mean_expected_erroneous_kmers.  Without it the record is unchanged."""
+    read_errors_mean_expected_erroneous_kmers.  Without it the record is unchanged.
+    `corrections`: what covest_amd.read_errors.correct_reads (or KmerCounts.correct) returns; the record then carries
+    corrections_cutoff, corrections_reads and the totals corrections_runs, corrections_corrected,
+    corrections_ambiguous and corrections_unfixable.  Without it the record is unchanged."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -177,6 +180,11 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
         record['read_errors_predicted_share'] = float(read_errors.predicted_share)
         record['read_errors_mean_expected_erroneous_kmers'] = (
             float(sum(read_errors.expected_erroneous_kmers.tolist()) / n) if n else float('nan'))
+    if corrections is not None:
+        record['corrections_cutoff'] = int(corrections.cutoff)
+        record['corrections_reads'] = int(corrections.runs.size)
+        for name in ('runs', 'corrected', 'ambiguous', 'unfixable'):
+            record['corrections_' + name] = int(getattr(corrections, name).sum())
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

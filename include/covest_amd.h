@@ -429,6 +429,34 @@ int covest_kmer_lookup_reads_device(covest_kmer *c, const uint8_t *d_bases, cons
 int covest_kmer_lookup_reads(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
                              uint32_t cutoff, const double *weights, int32_t n_weights, uint32_t *abundance,
                              uint32_t *summary, double *score);
+/* Isolated substitutions corrected from the table (k <= 31; no reference counterpart; read-only on the table).  Per
+ * read, last = len - k: a window is WEAK when the table's count for its key is below `cutoff` (0: none is); a RUN is a
+ * maximal set of consecutive weak windows [f, l], judged against the original bytes whatever happens to other runs; its
+ * CANDIDATE POSITIONS are the bases p whose covering windows [max(0, p - k + 1), min(p, last)] are exactly [f, l]
+ * (none when the run is longer than k; p = f + k - 1 when f > 0, and only if l == min(p, last); p = l when f == 0 and
+ * l < last; every p in [last, min(k - 1, len - 1)] when the run is the whole read).  An alternative -- a candidate
+ * position and one of the three other bases -- is VALID when every window of the run, with that base replaced, has a
+ * count >= cutoff.  Exactly one valid alternative: the run is CORRECTED, the byte becomes that base in the case of the
+ * old byte; more than one: AMBIGUOUS; none: UNFIXABLE; the bytes then stay.  Two errors closer than k + 1 merge into one
+ * run longer than k and stay.
+ *   out  uint8, indexed like the bases: the input except at corrected positions; every byte of every read is stored
+ *        exactly once, nothing outside.  It may be the very pointer of the bases (in place: only the corrected bytes are
+ *        stored); otherwise it must not overlap them.
+ *   fix  uint32[n_reads][4] = {runs, corrected, ambiguous, unfixable}, runs being the sum of the other three; optional
+ *        (NULL).  A read shorter than k has no window: its bytes are copied, its row is {0, 0, 0, 0}.
+ * Device form: asynchronous on `stream`; d_bases and d_out at any alignment, d_fix 16-byte aligned; d_offsets NULL:
+ * every read is read_len bases.  It must be ORDERED AFTER the adds it is to see and never looks at the overflow flag.
+ * A d_out that overlaps the reads without being d_bases is COVEST_E_INVALID where the host can see it: reads of one
+ * length; with d_offsets the extent of the reads is known on the device alone, and it is the caller's to keep apart.
+ * Host form: copies, waits, and answers COVEST_E_NOMEM if an add overflowed; `out` holds offsets[n_reads] -
+ * offsets[0] bytes, indexed relative to offsets[0].
+ * COVEST_E_UNSUPPORTED: k > 31.  COVEST_E_INVALID: a null counter, negative sizes, no offsets and read_len < 0, a null
+ * out with n_reads > 0, a d_fix that is not 16-byte aligned, or a counter that holds a covest_kmer_count_reads_device
+ * result.  n_reads == 0: COVEST_OK, nothing launched. */
+int covest_kmer_correct_reads_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                                     int64_t read_len, uint32_t cutoff, uint8_t *d_out, uint32_t *d_fix, void *stream);
+int covest_kmer_correct_reads(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
+                              uint32_t cutoff, uint8_t *out, uint32_t *fix);
 
 /* ---- FASTA / FASTQ front-end of the k-mer histogram: bin/kmer_hist.py:44-54 preprocess, :67-74 load_reads ----
  * HOST code (the only HIP calls: a device count and the allocation of page-locked buffers): the mapped file
