@@ -57,28 +57,14 @@ int covest_kmer_correct_reads(covest_kmer *c, const uint8_t *bases, const int64_
         return dev_guard.status();
     const size_t n_pos = (size_t)n_bytes, n = (size_t)n_reads;
     DevBuf d_fix; // (goes with the call; the copies back have waited for the kernel)
-    {
-        std::lock_guard<std::mutex> guard(c->lock);
-        HIP_TRY(c->ws_bases.reserve(std::max<size_t>(n_pos, 1)));
-        HIP_TRY(c->ws_offsets.reserve((n + 1) * sizeof(int64_t)));
-        if (n_pos)
-            HIP_TRY(hipMemcpy(c->ws_bases.ptr, bases + offsets[0], n_pos, hipMemcpyHostToDevice));
-        std::vector<int64_t> rel(n + 1);
-        for (size_t i = 0; i <= n; ++i)
-            rel[i] = offsets[i] - offsets[0];
-        HIP_TRY(hipMemcpy(c->ws_offsets.ptr, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    }
+    COVEST_TRY(stage_reads_in_counter(c, bases, offsets, n_reads));
     if (fix)
         HIP_TRY(d_fix.reserve(n * 4 * sizeof(uint32_t)));
     // in place on the staged copy of the bases: only the corrected bytes are stored
     COVEST_TRY(covest_kmer_correct_reads_device(c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(), n_reads, 0, cutoff,
                                                 c->ws_bases.as<uint8_t>(), fix ? d_fix.as<uint32_t>() : nullptr, nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    int flag = 0; // sticky until covest_kmer_clear: an add overflowed, so the counts are partial
-    HIP_TRY(hipMemcpy(&flag, c->flag.ptr, sizeof(int), hipMemcpyDeviceToHost));
-    if (flag)
-        return fail(COVEST_E_NOMEM, "covest_kmer_correct_reads: k-mer table overflow, the counts are partial: "
-                                    "covest_kmer_clear and recount with more slots");
+    COVEST_TRY(kmer_check_partial(c, "covest_kmer_correct_reads"));
     if (n_pos)
         HIP_TRY(hipMemcpy(out, c->ws_bases.ptr, n_pos, hipMemcpyDeviceToHost));
     if (fix)

@@ -72,17 +72,7 @@ int covest_kmer_lookup_reads(covest_kmer *c, const uint8_t *bases, const int64_t
         return dev_guard.status();
     const size_t n_pos = (size_t)n_bytes, n = (size_t)n_reads;
     DevBuf d_weights, d_abundance, d_summary, d_score; // (go with the call; the copies back have waited for the kernel)
-    {
-        std::lock_guard<std::mutex> guard(c->lock);
-        HIP_TRY(c->ws_bases.reserve(std::max<size_t>(n_pos, 1)));
-        HIP_TRY(c->ws_offsets.reserve((n + 1) * sizeof(int64_t)));
-        if (n_pos)
-            HIP_TRY(hipMemcpy(c->ws_bases.ptr, bases + offsets[0], n_pos, hipMemcpyHostToDevice));
-        std::vector<int64_t> rel(n + 1);
-        for (size_t i = 0; i <= n; ++i)
-            rel[i] = offsets[i] - offsets[0];
-        HIP_TRY(hipMemcpy(c->ws_offsets.ptr, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    }
+    COVEST_TRY(stage_reads_in_counter(c, bases, offsets, n_reads));
     if (score) {
         HIP_TRY(d_weights.reserve((size_t)n_weights * sizeof(double)));
         HIP_TRY(hipMemcpy(d_weights.ptr, weights, (size_t)n_weights * sizeof(double), hipMemcpyHostToDevice));
@@ -98,11 +88,7 @@ int covest_kmer_lookup_reads(covest_kmer *c, const uint8_t *bases, const int64_t
                                                summary ? d_summary.as<uint32_t>() : nullptr,
                                                score ? d_score.as<double>() : nullptr, nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    int flag = 0; // sticky until covest_kmer_clear: an add overflowed, so the counts are partial
-    HIP_TRY(hipMemcpy(&flag, c->flag.ptr, sizeof(int), hipMemcpyDeviceToHost));
-    if (flag)
-        return fail(COVEST_E_NOMEM, "covest_kmer_lookup_reads: k-mer table overflow, the counts are partial: "
-                                    "covest_kmer_clear and recount with more slots");
+    COVEST_TRY(kmer_check_partial(c, "covest_kmer_lookup_reads"));
     if (abundance && n_pos)
         HIP_TRY(hipMemcpy(abundance, d_abundance.ptr, n_pos * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (summary)

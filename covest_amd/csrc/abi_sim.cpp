@@ -20,9 +20,7 @@ int check_reads_args(const char *who, const void *genome, int64_t genome_len, in
         return fail(COVEST_E_INVALID, name + ": n_reads and first_read must not be negative");
     if (!(error_rate >= 0.0 && error_rate <= 1.0)) // (NaN fails both)
         return fail(COVEST_E_INVALID, name + ": error_rate must be in [0, 1]");
-    const int64_t i64_max = std::numeric_limits<int64_t>::max();
-    if (n_reads > i64_max / read_len || first_read > i64_max - n_reads)
-        return fail(COVEST_E_INVALID, name + ": more reads than 64-bit offsets reach");
+    COVEST_TRY(fail_if(check_reads_reach(name, first_read, n_reads, read_len)));
     if (n_reads > 0 && (!genome || !bases))
         return fail(COVEST_E_INVALID, name + ": null buffer");
     *thr = (uint64_t)std::floor(error_rate * 4294967296.0);

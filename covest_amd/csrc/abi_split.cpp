@@ -16,15 +16,7 @@ int check_split_args(const char *who, const void *offsets, int64_t n_reads, int6
     const std::string name(who);
     if (groups < 1 || groups > kSplitMaxGroups)
         return fail(COVEST_E_INVALID, name + ": groups must be within 1 .. " + std::to_string(kSplitMaxGroups));
-    if (n_reads < 0 || first_read < 0)
-        return fail(COVEST_E_INVALID, name + ": n_reads and first_read must not be negative");
-    if (!offsets && read_len < 0)
-        return fail(COVEST_E_INVALID, name + ": without offsets read_len must not be negative");
-    const int64_t i64_max = std::numeric_limits<int64_t>::max();
-    if (first_read > i64_max - n_reads || (!offsets && read_len > 0 && n_reads > i64_max / read_len))
-        return fail(COVEST_E_INVALID, name + ": more reads than 64-bit offsets reach");
-    if (n_reads > 0 && offsets && !out_offsets)
-        return fail(COVEST_E_INVALID, name + ": reads of their own lengths need an array for the output offsets");
+    COVEST_TRY(fail_if(check_reads_args(name, offsets != nullptr, n_reads, read_len, first_read, out_offsets != nullptr)));
     if (!group_first)
         return fail(COVEST_E_INVALID, name + ": group_first is null");
     return COVEST_OK;
@@ -65,13 +57,7 @@ int covest_split_reads(int32_t device, const uint8_t *bases, const int64_t *offs
 {
     COVEST_TRY(check_split_args("covest_split_reads", offsets, n_reads, read_len, first_read, groups, out_offsets,
                                 group_first));
-    if (offsets) {
-        if (offsets[0] < 0)
-            return fail(COVEST_E_INVALID, "covest_split_reads: negative offset");
-        for (int64_t i = 0; i < n_reads; ++i)
-            if (offsets[i + 1] < offsets[i])
-                return fail(COVEST_E_INVALID, "covest_split_reads: offsets descend at read " + std::to_string(i));
-    }
+    COVEST_TRY(fail_if(check_ascending_offsets("covest_split_reads", offsets, n_reads)));
     const int64_t end_byte = offsets ? offsets[n_reads] : n_reads * read_len; // (the bases are copied from byte 0)
     if (n_reads > 0 && end_byte > 0 && (!bases || !out_bases))
         return fail(COVEST_E_INVALID, "covest_split_reads: null buffer");
@@ -83,38 +69,19 @@ int covest_split_reads(int32_t device, const uint8_t *bases, const int64_t *offs
     }
     DeviceCall call(device, "covest_split_reads");
     COVEST_TRY(call.status());
-    const size_t n_bytes = (size_t)end_byte, index_bytes = (size_t)n_reads * sizeof(int64_t);
     const size_t first_bytes = (size_t)(groups + 1) * sizeof(int64_t);
-    // (go with the call, on every path; the copies back have waited for the kernels)
-    DevBuf d_bases, d_offsets, d_out_bases, d_out_offsets, d_index, d_first, d_scratch;
-    HIP_TRY(d_bases.reserve(std::max<size_t>(n_bytes, 16)));
-    HIP_TRY(d_out_bases.reserve(std::max<size_t>(n_bytes, 16)));
-    if (offsets)
-        HIP_TRY(d_offsets.reserve(index_bytes + sizeof(int64_t)));
-    if (out_offsets)
-        HIP_TRY(d_out_offsets.reserve(index_bytes + sizeof(int64_t)));
-    if (read_index)
-        HIP_TRY(d_index.reserve(index_bytes));
+    ReadsStage stage; // (goes with the call, on every path, as the two below; the copies back have waited for the kernels)
+    DevBuf d_first, d_scratch;
+    COVEST_TRY(stage.upload(bases, offsets, n_reads, (size_t)end_byte, out_offsets != nullptr, read_index != nullptr));
     HIP_TRY(d_first.reserve(first_bytes));
     HIP_TRY(d_scratch.reserve(split_scratch_bytes(n_reads, groups)));
-    if (n_bytes)
-        HIP_TRY(hipMemcpy(d_bases.ptr, bases, n_bytes, hipMemcpyHostToDevice));
-    if (offsets)
-        HIP_TRY(hipMemcpy(d_offsets.ptr, offsets, index_bytes + sizeof(int64_t), hipMemcpyHostToDevice));
-    HIP_TRY(launch_split_reads(d_bases.as<uint8_t>(), offsets ? d_offsets.as<int64_t>() : nullptr, n_reads, read_len,
-                               first_read, groups, seed, d_out_bases.as<uint8_t>(),
-                               out_offsets ? d_out_offsets.as<int64_t>() : nullptr,
-                               read_index ? d_index.as<int64_t>() : nullptr, d_first.as<int64_t>(), d_scratch.ptr, nullptr));
+    HIP_TRY(launch_split_reads(stage.d_bases.as<uint8_t>(), stage.d_offsets.as<int64_t>(), n_reads, read_len, first_read,
+                               groups, seed, stage.d_out_bases.as<uint8_t>(), stage.d_out_offsets.as<int64_t>(),
+                               stage.d_index.as<int64_t>(), d_first.as<int64_t>(), d_scratch.ptr, nullptr));
     HIP_TRY(hipMemcpy(group_first, d_first.ptr, first_bytes, hipMemcpyDeviceToHost));
     // a ragged input's bytes in all are offsets[n_reads] - offsets[0]: the reads need not start at byte 0
-    const size_t out_bytes = offsets ? (size_t)(offsets[n_reads] - offsets[0]) : n_bytes;
-    if (out_bytes)
-        HIP_TRY(hipMemcpy(out_bases, d_out_bases.ptr, out_bytes, hipMemcpyDeviceToHost));
-    if (out_offsets)
-        HIP_TRY(hipMemcpy(out_offsets, d_out_offsets.ptr, index_bytes + sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (read_index)
-        HIP_TRY(hipMemcpy(read_index, d_index.ptr, index_bytes, hipMemcpyDeviceToHost));
-    return COVEST_OK;
+    const size_t out_bytes = offsets ? (size_t)(offsets[n_reads] - offsets[0]) : (size_t)end_byte;
+    return stage.download(out_bases, out_bytes, out_offsets, (size_t)n_reads + 1, read_index, (size_t)n_reads);
 }
 
 } // extern "C"

@@ -34,12 +34,14 @@
 #include "device_model.h"
 #include "handback.h"
 #include "kernels.h"
+#include "reads_args.h"
 
 namespace covest {
 
 // the message covest_last_error returns (thread-local), and the status codes of a failed HIP call
 int set_error(int code, const std::string &msg);
 inline int fail(int code, const std::string &msg) { return set_error(code, msg); }
+inline int fail_if(const ArgCheck &a) { return a.status == COVEST_OK ? COVEST_OK : fail(a.status, a.message); } // (reads_args.h)
 int fail_hip(hipError_t e, const char *what);
 
 #define HIP_TRY(expr)                                \
@@ -397,6 +399,14 @@ double lgamma_at(int64_t j); // (after lgamma_ensure(j) or larger)
 double lgamma_of_factorial(int64_t j);
 
 int64_t launch_record_text(const LaunchRecord &r, char *buf, int64_t cap); // (kernels.h)
+
+// ---- kmer_host.cpp: what the host forms over the counter's table share (abi_lookup.cpp, abi_correct.cpp)
+// The reads of bases / offsets[n_reads + 1] (n_reads > 0, offsets[n_reads] >= offsets[0]) into c->ws_bases and, counted
+// from 0, c->ws_offsets.  Takes the counter's lock for the reserve and the copies, and lets it go.
+int stage_reads_in_counter(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads);
+// The sticky overflow flag (until covest_kmer_clear: an add overflowed, so the counts are partial), read after the
+// device has been waited for: COVEST_E_NOMEM in `who`'s name if it is set.
+int kmer_check_partial(covest_kmer *c, const char *who);
 
 // ---- tiles_host.cpp
 constexpr int64_t kListModeMaxPoints = 4096; // longer point lists are throughput work: K-direct

@@ -306,6 +306,35 @@ int finish(BulkCall &b)
 
 } // namespace
 
+namespace covest {
+
+int stage_reads_in_counter(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads)
+{
+    const size_t n_pos = (size_t)(offsets[n_reads] - offsets[0]), n = (size_t)n_reads;
+    std::lock_guard<std::mutex> guard(c->lock);
+    HIP_TRY(c->ws_bases.reserve(std::max<size_t>(n_pos, 1)));
+    HIP_TRY(c->ws_offsets.reserve((n + 1) * sizeof(int64_t)));
+    if (n_pos)
+        HIP_TRY(hipMemcpy(c->ws_bases.ptr, bases + offsets[0], n_pos, hipMemcpyHostToDevice));
+    std::vector<int64_t> rel(n + 1);
+    for (size_t i = 0; i <= n; ++i)
+        rel[i] = offsets[i] - offsets[0];
+    HIP_TRY(hipMemcpy(c->ws_offsets.ptr, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    return COVEST_OK;
+}
+
+int kmer_check_partial(covest_kmer *c, const char *who)
+{
+    int flag = 0;
+    HIP_TRY(hipMemcpy(&flag, c->flag.ptr, sizeof(int), hipMemcpyDeviceToHost));
+    if (flag)
+        return fail(COVEST_E_NOMEM, std::string(who) + ": k-mer table overflow, the counts are partial: "
+                                                       "covest_kmer_clear and recount with more slots");
+    return COVEST_OK;
+}
+
+} // namespace covest
+
 extern "C" {
 
 int covest_kmer_create(int32_t k, int32_t canonical, int64_t min_slots, int32_t device, covest_kmer **out)
@@ -467,17 +496,7 @@ int covest_kmer_add(covest_kmer *c, const uint8_t *bases, const int64_t *offsets
     DeviceGuard dev_guard(c->device);
     if (dev_guard.status() != COVEST_OK)
         return dev_guard.status();
-    {
-        std::lock_guard<std::mutex> guard(c->lock);
-        HIP_TRY(c->ws_bases.reserve((size_t)(n_bytes > 0 ? n_bytes : 1)));
-        HIP_TRY(c->ws_offsets.reserve((size_t)(n_reads + 1) * sizeof(int64_t)));
-        if (n_bytes > 0)
-            HIP_TRY(hipMemcpy(c->ws_bases.ptr, bases + offsets[0], (size_t)n_bytes, hipMemcpyHostToDevice));
-        std::vector<int64_t> rel((size_t)n_reads + 1);
-        for (int64_t i = 0; i <= n_reads; ++i)
-            rel[(size_t)i] = offsets[i] - offsets[0];
-        HIP_TRY(hipMemcpy(c->ws_offsets.ptr, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    }
+    COVEST_TRY(stage_reads_in_counter(c, bases, offsets, n_reads));
     int rc = covest_kmer_add_device(c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(), n_reads, 0, nullptr);
     if (rc != COVEST_OK)
         return rc;

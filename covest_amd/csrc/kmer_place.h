@@ -5,7 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
-#include "wave.h"
+#include "scan.h"
 
 namespace covest {
 
@@ -37,36 +37,11 @@ __device__ __forceinline__ u64 thread_rooms(const KmerBulk &p, unsigned first, u
     return sum;
 }
 
-// exclusive prefix of `v` over the 256 threads of the workgroup (lds: 4 words); `total` = the sum over all of them
-__device__ __forceinline__ u64 block_exclusive_scan(u64 v, u64 *lds, u64 &total)
-{
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    u64 inc = v;
-    for (int off = 1; off < kWave; off <<= 1) {
-        const u64 o = __shfl_up(inc, off, kWave);
-        if (lane >= off)
-            inc += o;
-    }
-    __syncthreads(); // (lds may still be read from the call before)
-    if (lane == kWave - 1)
-        lds[wave] = inc;
-    __syncthreads();
-    u64 before = 0;
-    total = 0;
-    for (int wv = 0; wv < 4; ++wv) {
-        const u64 s = lds[wv];
-        if (wv < wave)
-            before += s;
-        total += s;
-    }
-    return before + inc - v;
-}
-
 __global__ __launch_bounds__(256) void kmer_caps_partial_kernel(const KmerBulk p, u64 *__restrict__ partial)
 {
     __shared__ u64 lds[4];
     u64 room[kScanItems], total;
-    block_exclusive_scan(thread_rooms(p, blockIdx.x * kScanBlock + threadIdx.x * kScanItems, room), lds, total);
+    block_exclusive_scan<4>(thread_rooms(p, blockIdx.x * kScanBlock + threadIdx.x * kScanItems, room), lds, total);
     if (threadIdx.x == 0)
         partial[blockIdx.x] = total;
 }
@@ -81,7 +56,7 @@ __global__ __launch_bounds__(256) void kmer_caps_scan_kernel(u64 *__restrict__ p
     for (unsigned j = first; j < first + per && j < n; ++j)
         mine += partial[j];
     u64 total;
-    u64 run = block_exclusive_scan(mine, lds, total);
+    u64 run = block_exclusive_scan<4>(mine, lds, total);
     for (unsigned j = first; j < first + per && j < n; ++j) {
         const u64 v = partial[j];
         partial[j] = run;
@@ -96,7 +71,7 @@ __global__ __launch_bounds__(256) void kmer_caps_place_kernel(const KmerBulk p, 
     __shared__ u64 lds[4];
     const unsigned first = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
     u64 room[kScanItems], total;
-    u64 at = partial[blockIdx.x] + block_exclusive_scan(thread_rooms(p, first, room), lds, total);
+    u64 at = partial[blockIdx.x] + block_exclusive_scan<4>(thread_rooms(p, first, room), lds, total);
     for (int j = 0; j < kScanItems; ++j) {
         p.ctl[first + j] = make_ulonglong2(at, at + room[j]);
         at += room[j];

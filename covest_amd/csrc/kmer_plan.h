@@ -53,6 +53,18 @@ inline int64_t reads_of_launch(int64_t first, int64_t n_reads, int64_t per) // r
     return std::min(n_reads - first, per);
 }
 
+// A lane a read (or a few), workgroups of 256 threads (sample_reads.hip, split_reads.hip): 2^22 workgroups, 2^30 threads,
+// a launch, for the same wrap.
+inline int64_t lane_blocks_per_launch()
+{
+    return (int64_t)1 << 22;
+}
+
+inline int64_t blocks_of_launch(int64_t b0, int64_t n_blocks) // workgroups of the launch that starts at workgroup b0
+{
+    return std::min(n_blocks - b0, lane_blocks_per_launch());
+}
+
 // ---- pass 0 / 1: tiles of kTile bytes, kTilesPerBlock of them a workgroup --------------------------------------------
 constexpr int kTile = 256;        // bytes (threads) of a tile
 constexpr int kTilesPerBlock = 8; // consecutive tiles a workgroup works through (the unit of pass 0's sample)

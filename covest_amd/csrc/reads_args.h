@@ -1,0 +1,62 @@
+// reads_args.h -- the argument checks the entry points over packed reads that take no handle share (abi_sample.cpp,
+// abi_split.cpp; the reach check: abi_sim.cpp too), in plain C++.  No HIP in it:
+// tests/reads_args_check.cpp runs it under the host compiler's sanitizers.  A check returns the status and the text of
+// the message; the caller passes them to `fail` (host.h fail_if).
+#pragma once
+#include <cstdint>
+#include <limits>
+#include <string>
+
+#include "../../include/covest_amd.h"
+
+namespace covest {
+
+struct ArgCheck {
+    int status = COVEST_OK;
+    std::string message;
+};
+
+inline ArgCheck arg_invalid(const std::string &name, const std::string &what)
+{
+    return ArgCheck{COVEST_E_INVALID, name + ": " + what};
+}
+
+// first_read + n_reads, and n_reads * read_len where read_len > 0 (0: reads with offsets of their own), within int64
+inline ArgCheck check_reads_reach(const std::string &name, int64_t first_read, int64_t n_reads, int64_t read_len)
+{
+    const int64_t i64_max = std::numeric_limits<int64_t>::max();
+    if (first_read > i64_max - n_reads || (read_len > 0 && n_reads > i64_max / read_len))
+        return arg_invalid(name, "more reads than 64-bit offsets reach");
+    return ArgCheck{};
+}
+
+// Of both forms of a call: the sizes, their 64-bit reach, and the output offsets that reads of their own lengths need.
+inline ArgCheck check_reads_args(const std::string &name, bool has_offsets, int64_t n_reads, int64_t read_len,
+                                 int64_t first_read, bool has_out_offsets)
+{
+    if (n_reads < 0 || first_read < 0)
+        return arg_invalid(name, "n_reads and first_read must not be negative");
+    if (!has_offsets && read_len < 0)
+        return arg_invalid(name, "without offsets read_len must not be negative");
+    const ArgCheck reach = check_reads_reach(name, first_read, n_reads, has_offsets ? 0 : read_len);
+    if (reach.status != COVEST_OK)
+        return reach;
+    if (n_reads > 0 && has_offsets && !has_out_offsets)
+        return arg_invalid(name, "reads of their own lengths need an array for the output offsets");
+    return ArgCheck{};
+}
+
+// Of the host form: offsets[0 .. n_reads] (or nullptr) start at no negative byte and never descend.
+inline ArgCheck check_ascending_offsets(const std::string &name, const int64_t *offsets, int64_t n_reads)
+{
+    if (!offsets)
+        return ArgCheck{};
+    if (offsets[0] < 0)
+        return arg_invalid(name, "negative offset");
+    for (int64_t i = 0; i < n_reads; ++i)
+        if (offsets[i + 1] < offsets[i])
+            return arg_invalid(name, "offsets descend at read " + std::to_string(i));
+    return ArgCheck{};
+}
+
+} // namespace covest

@@ -1,4 +1,4 @@
-// split.h -- K-split: what split_reads.hip offers abi_split.cpp (covest_split_reads*; DESIGN.md section 6y).
+// split.h -- K-split: what split_reads.hip offers abi_split.cpp (covest_split_reads*; DESIGN.md section 6aa).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -21,14 +21,14 @@
 //                    the workgroup's lengths are written to LDS in the order of (group, rank) and scanned there, which
 //                    gives every read the bases of its group that lie before it.  A read writes, at its global rank, its
 //                    output offset, its global index and its SOURCE offset (scratch)
-//   5. the sampler's gather (sample.h launch_sample_gather) over that table, through the tile image
+//   5. the gather (gather_reads.hip launch_gather_reads, which the sampler shares) over that table, through the tile image
 // Nothing is written outside d_out_bases[0 .. bases), d_out_offsets[0 .. n_reads], d_read_index[0 .. n_reads),
 // d_group_first[0 .. G] and the library's scratch.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
-#include "sample.h"
+#include "gather_reads.h"
+#include "kmer_plan.h"
+#include "scan.h"
 #include "sim_philox.h"
 #include "split.h"
 
@@ -40,7 +40,6 @@ constexpr int kThreads = kSplitThreads;
 constexpr int kWaves = kThreads / 64;
 constexpr int kPerLane = kSplitPerLane;
 constexpr int kMaxG = kSplitMaxGroups;
-constexpr int64_t kBlocksPerLaunch = (int64_t)1 << 22; // 2^30 threads a launch (HIP wraps grids beyond 2^32 threads)
 static_assert(kMaxG <= kThreads, "a lane a group where the groups are walked");
 static_assert(kMaxG <= 256, "the in-wave match takes eight ballots");
 
@@ -49,29 +48,6 @@ __device__ __forceinline__ unsigned group_of(unsigned long long r, unsigned grou
     uint32_t w[4];
     philox_block(r, 0u, kStreamGroup, PhiloxKey{key0, key1}, w);
     return (unsigned)(((unsigned long long)w[0] * groups) >> 32);
-}
-
-// inclusive scan over the wave's 64 lanes
-__device__ __forceinline__ long long wave_scan_i64(long long v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const long long up = __shfl_up(v, off, 64);
-        if (lane >= off)
-            v += up;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int wave_scan_i32(int v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int up = __shfl_up(v, off, 64);
-        if (lane >= off)
-            v += up;
-    }
-    return v;
 }
 
 // The read of lane tid in round j of workgroup blk: the workgroup's reads in input order are round 0's lanes, round 1's, ...
@@ -115,52 +91,10 @@ __global__ __launch_bounds__(kSplitScanThreads) void split_rows_kernel(long long
                                                                        long long *__restrict__ totals)
 {
     __shared__ long long wsum[2][kSplitScanThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long *row = pairs + 2 * (long long)blockIdx.x * n_blocks;
-    long long carry_c = 0, carry_b = 0; // (uniform: every lane keeps its own copy)
-    for (long long base = 0; base < n_blocks; base += kSplitScanPass) {
-        const long long at = base + (long long)tid * kSplitScanPerLane;
-        long long c[kSplitScanPerLane], b[kSplitScanPerLane], sc = 0, sb = 0;
-#pragma unroll
-        for (int j = 0; j < kSplitScanPerLane; ++j) {
-            const bool in = at + j < n_blocks;
-            c[j] = in ? row[2 * (at + j)] : 0;
-            b[j] = in ? row[2 * (at + j) + 1] : 0;
-            sc += c[j];
-            sb += b[j];
-        }
-        const long long ic = wave_scan_i64(sc, lane), ib = wave_scan_i64(sb, lane);
-        if (lane == 63) {
-            wsum[0][wave] = ic;
-            wsum[1][wave] = ib;
-        }
-        __syncthreads();
-        long long before_c = 0, before_b = 0, all_c = 0, all_b = 0;
-#pragma unroll
-        for (int w = 0; w < kSplitScanThreads / 64; ++w) {
-            const long long wc = wsum[0][w], wb = wsum[1][w];
-            if (w < wave) {
-                before_c += wc;
-                before_b += wb;
-            }
-            all_c += wc;
-            all_b += wb;
-        }
-        long long ec = carry_c + before_c + ic - sc, eb = carry_b + before_b + ib - sb;
-#pragma unroll
-        for (int j = 0; j < kSplitScanPerLane; ++j) {
-            if (at + j < n_blocks) {
-                row[2 * (at + j)] = ec;
-                row[2 * (at + j) + 1] = eb;
-            }
-            ec += c[j];
-            eb += b[j];
-        }
-        carry_c += all_c;
-        carry_b += all_b;
-        __syncthreads(); // (wsum is written again in the next pass)
-    }
-    if (tid == 0) {
+    long long carry_c, carry_b;
+    scan_pair_row<kSplitScanThreads, kSplitScanPerLane>(pairs + 2 * (long long)blockIdx.x * n_blocks, n_blocks, &wsum[0][0],
+                                                        carry_c, carry_b);
+    if (threadIdx.x == 0) {
         totals[2 * blockIdx.x] = carry_c;
         totals[2 * blockIdx.x + 1] = carry_b;
     }
@@ -173,28 +107,15 @@ __global__ __launch_bounds__(kThreads) void split_totals_kernel(long long *__res
                                                                 long long *__restrict__ out_offsets)
 {
     __shared__ long long wsum[2][kWaves];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const bool in = (unsigned)tid < groups;
-    const long long c = in ? totals[2 * tid] : 0, b = in ? totals[2 * tid + 1] : 0;
-    const long long ic = wave_scan_i64(c, lane), ib = wave_scan_i64(b, lane);
-    if (lane == 63) {
-        wsum[0][wave] = ic;
-        wsum[1][wave] = ib;
-    }
-    __syncthreads();
-    long long ec = ic - c, eb = ib - b, all_b = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        if (w < wave) {
-            ec += wsum[0][w];
-            eb += wsum[1][w];
-        }
-        all_b += wsum[1][w];
-    }
+    long long e[2] = {in ? totals[2 * tid] : 0, in ? totals[2 * tid + 1] : 0}, all[2];
+    block_exclusive_scan<kWaves, 2>(e, &wsum[0][0], all);
+    const long long all_b = all[1];
     if (in) {
-        totals[2 * tid] = ec;
-        totals[2 * tid + 1] = eb;
-        group_first[tid] = ec;
+        totals[2 * tid] = e[0];
+        totals[2 * tid + 1] = e[1];
+        group_first[tid] = e[0];
     }
     if (tid == 0) {
         group_first[groups] = n_reads;
@@ -289,17 +210,8 @@ __global__ __launch_bounds__(kThreads) void split_place_kernel(
 
     // where each group starts in (group, rank) order: the exclusive scan of run[]
     {
-        const int c = run[tid];
-        const int ic = wave_scan_i32(c, lane);
-        if (lane == 63)
-            part[wave] = ic;
-        __syncthreads();
-        int e = ic - c;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w)
-            if (w < wave)
-                e += part[w];
-        lstart[tid] = e;
+        int all;
+        lstart[tid] = block_exclusive_scan<kWaves>(run[tid], part, all);
     }
     __syncthreads();
 #pragma unroll
@@ -316,15 +228,7 @@ __global__ __launch_bounds__(kThreads) void split_place_kernel(
             v[j] = kPerLane * tid + j < have ? lens[kPerLane * tid + j] : 0;
             s += v[j];
         }
-        const long long is = wave_scan_i64(s, lane);
-        if (lane == 63)
-            lpart[wave] = is;
-        __syncthreads();
-        long long e = is - s;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w)
-            if (w < wave)
-                e += lpart[w];
+        long long all, e = block_exclusive_scan<kWaves>(s, lpart, all);
 #pragma unroll
         for (int j = 0; j < kPerLane; ++j) {
             lens[kPerLane * tid + j] = e;
@@ -368,8 +272,8 @@ hipError_t launch_split_reads(const unsigned char *bases, const int64_t *offsets
     const long long *offs = reinterpret_cast<const long long *>(offsets);
     long long *out_offs = reinterpret_cast<long long *>(out_offsets);
     const uint32_t key0 = philox_key(seed).k0, key1 = philox_key(seed).k1;
-    for (int64_t b0 = 0; b0 < n_blocks; b0 += kBlocksPerLaunch) {
-        const dim3 grid((unsigned)std::min(n_blocks - b0, kBlocksPerLaunch));
+    for (int64_t b0 = 0; b0 < n_blocks; b0 += kmer_plan::lane_blocks_per_launch()) {
+        const dim3 grid((unsigned)kmer_plan::blocks_of_launch(b0, n_blocks));
         hipLaunchKernelGGL(split_flags_kernel, grid, dim3(kThreads), 0, stream, offs, (long long)read_len, (long long)n_reads,
                            (unsigned long long)first_read, (unsigned)groups, key0, key1, (long long)b0, (long long)n_blocks,
                            pairs);
@@ -387,8 +291,8 @@ hipError_t launch_split_reads(const unsigned char *bases, const int64_t *offsets
     e = hipGetLastError();
     if (e != hipSuccess)
         return e;
-    for (int64_t b0 = 0; b0 < n_blocks; b0 += kBlocksPerLaunch) {
-        const dim3 grid((unsigned)std::min(n_blocks - b0, kBlocksPerLaunch));
+    for (int64_t b0 = 0; b0 < n_blocks; b0 += kmer_plan::lane_blocks_per_launch()) {
+        const dim3 grid((unsigned)kmer_plan::blocks_of_launch(b0, n_blocks));
         hipLaunchKernelGGL(split_place_kernel, grid, dim3(kThreads), 0, stream, offs, (long long)read_len, (long long)n_reads,
                            (unsigned long long)first_read, (unsigned)groups, key0, key1, (long long)b0, (long long)n_blocks,
                            pairs, totals, out_offs, reinterpret_cast<long long *>(read_index), src_off);
@@ -398,9 +302,9 @@ hipError_t launch_split_reads(const unsigned char *bases, const int64_t *offsets
     }
     if (!offsets && read_len == 0)
         return hipSuccess; // nothing but empty reads: no byte to move
-    return launch_sample_gather(bases, reinterpret_cast<const int64_t *>(counts), offsets ? out_offsets : nullptr, read_len,
-                                offsets ? -1 : n_reads * read_len, reinterpret_cast<const int64_t *>(src_off), out_bases,
-                                stream);
+    return launch_gather_reads(bases, reinterpret_cast<const int64_t *>(counts), offsets ? out_offsets : nullptr, read_len,
+                               offsets ? -1 : n_reads * read_len, reinterpret_cast<const int64_t *>(src_off), out_bases,
+                               stream);
 }
 
 } // namespace covest

@@ -156,6 +156,29 @@ static void check_ragged(int w)
     }
 }
 
+// A lane a read: 2^22 workgroups a launch -- 2^30 threads of 256 -- so 2^22 blocks are one launch and one more is two.
+static void check_lane_blocks()
+{
+    const int64_t per = lane_blocks_per_launch();
+    CHECK(per == (int64_t)1 << 22 && per * 256 == (int64_t)1 << 30, "lane_blocks_per_launch %lld", (long long)per);
+    const int64_t totals[] = {1, per - 1, per, per + 1, 2 * per - 1, 2 * per, 2 * per + 1, 3 * per};
+    for (const int64_t n_blocks : totals) {
+        int64_t next = 0;
+        int launches = 0;
+        for (int64_t b0 = 0; b0 < n_blocks; b0 += per, ++launches) {
+            const int64_t n = blocks_of_launch(b0, n_blocks);
+            CHECK(b0 == next && n >= 1 && n <= per, "n_blocks %lld b0 %lld: %lld blocks", (long long)n_blocks, (long long)b0, (long long)n);
+            CHECK(n == per || b0 + n == n_blocks, "n_blocks %lld b0 %lld: a launch that is not the last is not full", (long long)n_blocks,
+                  (long long)b0);
+            next = b0 + n;
+        }
+        CHECK(next == n_blocks && launches == (n_blocks + per - 1) / per, "n_blocks %lld: %d launches end at %lld", (long long)n_blocks,
+              launches, (long long)next);
+    }
+    CHECK(blocks_of_launch(0, per) == per && blocks_of_launch(0, per + 1) == per && blocks_of_launch(per, per + 1) == 1,
+          "2^22 blocks and one more");
+}
+
 int main()
 {
     check_plans();
@@ -165,6 +188,7 @@ int main()
             check_fixed(len, w);
     for (const int w : {9, 11, 17, 18, 19})
         check_ragged(w);
+    check_lane_blocks();
     std::printf("kmer_plan ok\n");
     return 0;
 }

@@ -1,0 +1,108 @@
+// reads_args_check.cpp -- the host-side check of the argument checks the entry points over packed reads share
+// (covest_amd/csrc/reads_args.h), compiled and run by tests/test_reads_args_cpu.py with the host
+// compiler under -fsanitize=address,undefined.  No device: each check is walked at its boundary, and the status and the
+// exact text of the message are asserted.
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "reads_args.h"
+
+using namespace covest;
+
+static const int64_t kMax = std::numeric_limits<int64_t>::max();
+
+static void expect(const ArgCheck &got, int status, const std::string &message, int line)
+{
+    if (got.status != status || got.message != message) {
+        std::printf("FAILED %s:%d: status %d \"%s\", expected %d \"%s\"\n", __FILE__, line, got.status, got.message.c_str(), status,
+                    message.c_str());
+        std::exit(1);
+    }
+}
+#define OK(call) expect(call, COVEST_OK, "", __LINE__)
+#define INVALID(call, text) expect(call, COVEST_E_INVALID, std::string("who: ") + text, __LINE__)
+
+static const char *kNegative = "n_reads and first_read must not be negative";
+static const char *kReadLen = "without offsets read_len must not be negative";
+static const char *kReach = "more reads than 64-bit offsets reach";
+static const char *kOutOffsets = "reads of their own lengths need an array for the output offsets";
+
+// first_read + n_reads at INT64_MAX; n_reads * read_len either side of 2^63
+static void check_reach()
+{
+    OK(check_reads_reach("who", 0, 0, 0));
+    OK(check_reads_reach("who", kMax, 0, 1));
+    OK(check_reads_reach("who", 0, kMax, 1));
+    OK(check_reads_reach("who", kMax - 7, 7, 1));  // the sum is INT64_MAX
+    INVALID(check_reads_reach("who", kMax - 7, 8, 1), kReach);
+    INVALID(check_reads_reach("who", kMax, 1, 0), kReach);
+    INVALID(check_reads_reach("who", 1, kMax, 0), kReach);
+    // 2^63 = 2^31 * 2^32: one read fewer, or one base fewer a read, is within reach
+    const int64_t a = (int64_t)1 << 31, b = (int64_t)1 << 32;
+    INVALID(check_reads_reach("who", 0, a, b), kReach);
+    INVALID(check_reads_reach("who", 0, b, a), kReach);
+    OK(check_reads_reach("who", 0, a - 1, b));
+    OK(check_reads_reach("who", 0, a, b - 1));
+    OK(check_reads_reach("who", 0, kMax / 7, 7));  // 7 divides 2^63 - 1
+    INVALID(check_reads_reach("who", 0, kMax / 7 + 1, 7), kReach);
+    OK(check_reads_reach("who", 0, 1, kMax));
+    INVALID(check_reads_reach("who", 0, 2, kMax), kReach);
+    OK(check_reads_reach("who", 0, kMax, 0));      // reads with offsets of their own: no product
+}
+
+// the order of the four checks, and null and non-null output offsets
+static void check_args()
+{
+    OK(check_reads_args("who", false, 0, 0, 0, false));
+    OK(check_reads_args("who", false, 8, 100, 5, false));
+    OK(check_reads_args("who", true, 8, -1, 5, true));           // read_len is not looked at beside offsets
+    OK(check_reads_args("who", true, kMax, kMax, 0, true));       // ... nor multiplied
+    OK(check_reads_args("who", true, 0, 0, 0, false));            // no reads: no output offsets needed
+    OK(check_reads_args("who", false, 8, 100, 0, true));
+    INVALID(check_reads_args("who", true, 1, 0, 0, false), kOutOffsets);
+    INVALID(check_reads_args("who", true, 8, 100, 0, false), kOutOffsets);
+    INVALID(check_reads_args("who", false, -1, -1, kMax, false), kNegative);
+    INVALID(check_reads_args("who", true, 8, 0, -1, false), kNegative);
+    INVALID(check_reads_args("who", false, kMax, -1, kMax, false), kReadLen);
+    INVALID(check_reads_args("who", true, 8, 0, kMax - 7, false), kReach); // before the output offsets
+    OK(check_reads_args("who", true, 7, 0, kMax - 7, true));
+    INVALID(check_reads_args("who", false, (int64_t)1 << 62, 2, 0, true), kReach);
+    OK(check_reads_args("who", false, ((int64_t)1 << 62) - 1, 2, 0, true));
+    OK(check_reads_args("who", false, (int64_t)1 << 62, 0, 0, true)); // empty reads: no product to overflow
+}
+
+// offsets equal, descending at the first read and at the last, a negative first offset
+static void check_offsets()
+{
+    OK(check_ascending_offsets("who", nullptr, 5));
+    const std::vector<int64_t> equal(6, 7), rising = {0, 3, 3, 10, 11, 11}, one = {-1};
+    OK(check_ascending_offsets("who", equal.data(), 5));
+    OK(check_ascending_offsets("who", rising.data(), 5));
+    OK(check_ascending_offsets("who", rising.data(), 0));
+    std::vector<int64_t> bad = rising;
+    bad[1] = -1; // (after a first offset of 0: it descends, it is not "negative")
+    INVALID(check_ascending_offsets("who", bad.data(), 5), "offsets descend at read 0");
+    bad = rising;
+    bad[5] = 10;
+    INVALID(check_ascending_offsets("who", bad.data(), 5), "offsets descend at read 4");
+    OK(check_ascending_offsets("who", bad.data(), 4)); // (the last offset is not looked at)
+    bad = rising;
+    bad[0] = -1;
+    INVALID(check_ascending_offsets("who", bad.data(), 5), "negative offset");
+    INVALID(check_ascending_offsets("who", one.data(), 0), "negative offset"); // offsets[0] alone, with no read
+    bad = {kMax, kMax - 1};
+    INVALID(check_ascending_offsets("who", bad.data(), 1), "offsets descend at read 0");
+}
+
+int main()
+{
+    check_reach();
+    check_args();
+    check_offsets();
+    // a name is taken as it comes
+    expect(check_reads_reach("covest_sample_reads_device", kMax, 1, 0), COVEST_E_INVALID,
+           "covest_sample_reads_device: more reads than 64-bit offsets reach", __LINE__);
+    std::printf("reads_args ok\n");
+    return 0;
+}

@@ -215,6 +215,21 @@ torch.cuda.synchronize()
 assert d_counts.cpu().tolist() == [WPAT, 0, 0, WPAT] and d_o.cpu().tolist() == [WPAT, 0, WPAT], "n_reads == 0"
 print("variable ok")
 
+# the scan's carry from pass to pass: one pass of sample_scan holds 4096 workgroups' pairs, 1 048 576 reads -- exactly one
+# pass, one pair in the second, one more workgroup and a read; reads of length 1, then lengths of 0, 1 and 2, so that
+# the two halves of the pair carry different sums
+import time
+t0 = time.perf_counter()
+PASS = 4096 * 256
+for n in (PASS, PASS + 1, PASS + 257):
+    ones = rng.choice(ACGT, size=n)
+    for factor in (2, 16):
+        run(ones, None, 1, n, 3, factor, SEED, 1, 7, ("scan passes", n, factor))
+short = np.zeros(PASS + 2, dtype=np.int64); np.cumsum(rng.choice((0, 1, 2), size=PASS + 1), out=short[1:])
+nk, nb = run(rng.choice(ACGT, size=int(short[-1])), short, 0, PASS + 1, 3, 2, SEED, 7, 1, "scan passes, ragged")
+assert nk != nb, "the two halves of the pair carry the same sum"
+print("scan passes ok, %.2f s" % (time.perf_counter() - t0))
+
 # host form and device form agree
 got = sample.sample_reads((blob, offsets), 2, seed=SEED, first_read=5)
 want = ref.sample(blob, offsets, 5, 2, SEED)
@@ -274,8 +289,8 @@ print("device forms ok")
 
 def test_device_forms(hip_lib):
     """Raw device pointers (torch tensors): every fixed read length and read count at three factors and six pairs of
-    alignments, ragged reads with a long run of empty ones, nothing written outside the stated ranges, the sample into
-    the k-mer counter through add_device and count_reads_device, and a 4.4e9-base input at factor 64."""
+    alignments, ragged reads with a long run of empty ones, nothing written outside the stated ranges, read counts at
+    and just beyond one pass of the scan (its carry, bit for bit), the sample into the k-mer counter through add_device and count_reads_device, and a 4.4e9-base input at factor 64."""
     env = dict(os.environ, COVEST_REPO=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     proc = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", _DEVICE_SCRIPT], env=env, capture_output=True,
                           text=True)

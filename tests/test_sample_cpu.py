@@ -152,6 +152,48 @@ def test_c_entry_points_refuse_bad_arguments(hip_lib):
     assert not out.any() and (counts == -1).all()
 
 
+def test_the_shared_checks_word_their_messages_as_before(hip_lib):
+    """The texts of the checks covest_sample_reads*, covest_split_reads* and covest_simulate_reads* share
+    (csrc/reads_args.h), byte for byte as each entry point worded them on its own; the factor is looked at first."""
+    bases = np.full(64, 65, dtype=np.uint8)
+    out = np.zeros(64, dtype=np.uint8)
+    offsets = np.arange(9, dtype=np.int64) * 8
+    out_offsets = np.full(9, -1, dtype=np.int64)
+    counts = np.full(2, -1, dtype=np.int64)
+    n_kept, n_bases = ctypes.c_int64(-1), ctypes.c_int64(-1)
+
+    def host(n=8, L=8, first=0, factor=2.0, offs=None, out_offs=None):
+        return hip_lib.covest_sample_reads(-1, bases.ctypes.data, offs, n, L, first, factor, 1, out.ctypes.data, out_offs, None,
+                                           ctypes.byref(n_kept), ctypes.byref(n_bases))
+
+    def device(n=8, L=8, first=0, factor=2.0, offs=None, out_offs=None):
+        return hip_lib.covest_sample_reads_device(-1, bases.ctypes.data, offs, n, L, first, factor, 1, out.ctypes.data, out_offs,
+                                                  None, counts.ctypes.data, None)
+
+    def said(status):
+        assert status == -1
+        return hip_lib.covest_last_error().decode()
+
+    for fn, name in ((host, "covest_sample_reads"), (device, "covest_sample_reads_device")):
+        assert said(fn(n=-1, factor=0.5)) == name + ": factor must be a finite number, at least 1"
+        assert said(fn(n=-1, L=-1)) == name + ": n_reads and first_read must not be negative"
+        assert said(fn(first=-1)) == name + ": n_reads and first_read must not be negative"
+        assert said(fn(L=-1, first=(1 << 63) - 4)) == name + ": without offsets read_len must not be negative"
+        assert said(fn(first=(1 << 63) - 8)) == name + ": more reads than 64-bit offsets reach"
+        assert said(fn(n=1 << 62, L=100)) == name + ": more reads than 64-bit offsets reach"
+        assert said(fn(offs=offsets.ctypes.data)) == name + ": reads of their own lengths need an array for the output offsets"
+    bad = offsets.copy()
+    bad[3] = 5
+    assert said(host(offs=bad.ctypes.data, out_offs=out_offsets.ctypes.data)) == "covest_sample_reads: offsets descend at read 2"
+    bad = offsets - 1
+    assert said(host(offs=bad.ctypes.data, out_offs=out_offsets.ctypes.data)) == "covest_sample_reads: negative offset"
+    genome = np.full(64, ord("A"), dtype=np.uint8)
+    assert hip_lib.covest_simulate_reads(-1, genome.ctypes.data, 64, 8, (1 << 63) - 4, 8, 0.0, 1, 0, out.ctypes.data, None) == -1
+    assert hip_lib.covest_last_error().decode() == "covest_simulate_reads: more reads than 64-bit offsets reach"
+    assert hip_lib.covest_simulate_reads(-1, genome.ctypes.data, 64, 8, 0, 1 << 61, 0.0, 1, 0, out.ctypes.data, None) == -1
+    assert hip_lib.covest_last_error().decode() == "covest_simulate_reads: more reads than 64-bit offsets reach"
+
+
 def test_no_cpu_path(hip_lib, tmp_path):
     from covest_amd import _capi, sample
     if hip_lib.covest_device_count() > 0:

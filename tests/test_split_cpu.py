@@ -252,6 +252,44 @@ def test_argument_errors_come_before_the_library(monkeypatch):
         jackknife.read_jackknife(Model(), est[:1], reads)
 
 
+def test_the_shared_checks_word_their_messages_as_before(hip_lib):
+    """The texts of the checks the split shares with the sampler (csrc/reads_args.h), byte for byte as the split worded
+    them on its own, between its own two: the groups are looked at first, group_first last."""
+    import ctypes
+    bases = np.full(64, 65, dtype=np.uint8)
+    out = np.zeros(64, dtype=np.uint8)
+    offsets = np.arange(9, dtype=np.int64) * 8
+    out_offsets = np.full(9, -1, dtype=np.int64)
+    first_of = np.full(5, -1, dtype=np.int64)
+
+    def host(n=8, L=8, first=0, groups=4, offs=None, out_offs=None, gf=first_of.ctypes.data):
+        return hip_lib.covest_split_reads(-1, bases.ctypes.data, offs, n, L, first, groups, 1, out.ctypes.data, out_offs, None, gf)
+
+    def device(n=8, L=8, first=0, groups=4, offs=None, out_offs=None, gf=first_of.ctypes.data):
+        return hip_lib.covest_split_reads_device(-1, bases.ctypes.data, offs, n, L, first, groups, 1, out.ctypes.data, out_offs,
+                                                 None, gf, None)
+
+    def said(status):
+        assert status == -1
+        return hip_lib.covest_last_error().decode()
+
+    for fn, name in ((host, "covest_split_reads"), (device, "covest_split_reads_device")):
+        assert said(fn(n=-1, groups=257)) == name + ": groups must be within 1 .. 256"
+        assert said(fn(n=-1, L=-1, gf=None)) == name + ": n_reads and first_read must not be negative"
+        assert said(fn(first=-1)) == name + ": n_reads and first_read must not be negative"
+        assert said(fn(L=-1, first=(1 << 63) - 4)) == name + ": without offsets read_len must not be negative"
+        assert said(fn(first=(1 << 63) - 8)) == name + ": more reads than 64-bit offsets reach"
+        assert said(fn(n=1 << 62, L=100)) == name + ": more reads than 64-bit offsets reach"
+        assert said(fn(offs=offsets.ctypes.data, gf=None)) == name + ": reads of their own lengths need an array for the output offsets"
+        assert said(fn(gf=None)) == name + ": group_first is null"
+    bad = offsets.copy()
+    bad[8] = 50
+    assert said(host(offs=bad.ctypes.data, out_offs=out_offsets.ctypes.data)) == "covest_split_reads: offsets descend at read 7"
+    bad = offsets - 1
+    assert said(host(offs=bad.ctypes.data, out_offs=out_offsets.ctypes.data)) == "covest_split_reads: negative offset"
+    assert (first_of == -1).all() and not out.any()
+
+
 def test_the_header_states_the_rule_and_the_stream_table_has_its_row():
     import os
     from conftest import REPO

@@ -160,10 +160,11 @@ def rates(reps, lines):
     rate = {name: n_bases / (statistics.median(t) * 1e-3) / 1e9 for name, t in ms.items()}
     lines.append("# rates: GB/s of bases moved, median of %d; %d bases of %d-base reads; %s" % (reps, n_bases, READ_LEN,
                                                                                               torch.cuda.get_device_name(0)))
-    lines.append("# %-18s %10s %10s %16s" % ("route", "ms", "GB/s", "of the sampler's"))
+    lines.append("# %-18s %10s %10s %16s %10s %10s" % ("route", "ms", "GB/s", "of the sampler's", "least ms", "most ms"))
     for name, _ in routes:
-        lines.append("  %-18s %10.3f %10.1f %16.3f" % (name, statistics.median(ms[name]), rate[name],
-                                                       rate[name] / rate["sampler factor 1"]))
+        lines.append("  %-18s %10.3f %10.1f %16.3f %10.3f %10.3f" % (name, statistics.median(ms[name]), rate[name],
+                                                                     rate[name] / rate["sampler factor 1"], min(ms[name]),
+                                                                     max(ms[name])))
     del reads, out
     torch.cuda.empty_cache()
     # one whole leave_group_out_histograms: host reads in, histograms out

@@ -1,7 +1,8 @@
 """Rate of the read sampler (covest_sample_reads_device, sample_reads.hip) against a device-to-device hipMemcpyAsync
 of bases_kept bytes (the floor: the gather reads and writes that much) and against the torch route (bases2d[mask], the
 mask given), in one run: 100-bp reads, 10^8 and 10^9 input bases, factors 2 and 16.  HIP events on the stream after a
-spin-up; per case the median of N timed repetitions, the three routes taking turns.  Reported only: there is no bar.
+spin-up; per case the median of N timed repetitions (and, of the call's, the least and the most), the three routes
+taking turns.  Reported only: there is no bar.
 
 Run in a fresh process; torch is imported first (one HIP runtime a process).
 
@@ -47,8 +48,9 @@ def main():
     hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
 
     lines = ["# read sampler: GB/s of KEPT bytes, median of %d; 100-bp reads; %s" % (args.reps, torch.cuda.get_device_name(0)),
-             "# %-12s %6s %12s %12s %12s %12s %14s %14s" % ("input bases", "factor", "kept bytes", "call GB/s", "memcpy GB/s",
-                                                           "torch GB/s", "call / memcpy", "call / torch")]
+             "# %-12s %6s %12s %12s %12s %12s %14s %14s   %s" % ("input bases", "factor", "kept bytes", "call GB/s", "memcpy GB/s",
+                                                                "torch GB/s", "call / memcpy", "call / torch",
+                                                                "call ms: min median max")]
     for n_bases in (10 ** 8, 10 ** 9):
         n_reads = n_bases // READ_LEN
         reads = torch.randint(65, 85, (n_reads, READ_LEN), dtype=torch.uint8, device=dev)
@@ -83,9 +85,9 @@ def main():
                 for name, fn in routes:
                     ms[name].append(timed_ms(fn))
             rate = {name: kept_bytes / (statistics.median(t) * 1e-3) / 1e9 for name, t in ms.items()}
-            lines.append("  %-12d %6d %12d %12.1f %12.1f %12.1f %14.3f %14.1f" % (
+            lines.append("  %-12d %6d %12d %12.1f %12.1f %12.1f %14.3f %14.1f   %.4f %.4f %.4f" % (
                 n_bases, factor, kept_bytes, rate["call"], rate["memcpy"], rate["torch"], rate["call"] / rate["memcpy"],
-                rate["call"] / rate["torch"]))
+                rate["call"] / rate["torch"], min(ms["call"]), statistics.median(ms["call"]), max(ms["call"])))
         del reads, out
     text = "\n".join(lines) + "\n"
     print(text, end="")
