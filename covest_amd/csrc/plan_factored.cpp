@@ -6,7 +6,7 @@
 //   fill_plan                           the FactoredPlan fields every builder sets the same way
 //   part_columns                        per slot and per q-tile of a part: thresholds, (1-q)^4, step counts
 //   part_geometry                       columns of G, LDS stride, workgroup size, workgroups per (c, e)
-//   planner_charges                     the cost model's constants (and, in tuning builds, their overrides)
+//   planner_charges                     the cost model's constants (unit_deal.h; in tuning builds, their overrides)
 //   deal_qblock                         units to waves, pieces, slots -> UnitTables
 //   slot_weights, pair_halves           per-lane starting weights; the half-1 partner of every half-0 unit
 //   column_limit                        what the kernel's column limit cannot learn from the bands (band.h)
@@ -15,6 +15,7 @@
 //   build_list_plan                     the point lists of list mode, on the same UnitTables and PlanPack
 #include "band.h"
 #include "host.h"
+#include "unit_deal.h"
 
 #include <initializer_list>
 
@@ -145,6 +146,7 @@ struct PartGeometry {
     int pass_stride; // a pass begins on an MFMA step
     int n_columns, ld, n_buf;
     int n_threads, units_per_wave, n_qblocks;
+    bool one_block_a_pair = false; // a grid with enough (c, e) pairs to fill the chip with one workgroup each (part_geometry)
     int n_waves() const { return n_threads / 64; }
     size_t block_slots() const { return (size_t)n_waves() * kMaxUnits; } // unit slots of one workgroup
     size_t n_unit() const { return (size_t)n_qblocks * block_slots(); }
@@ -285,41 +287,28 @@ PartGeometry part_geometry(int t_loc_max, int n_pass, int32_t n_qtiles, int64_t 
     // cut into blocks, and the assignment of units to waves fixes the order of its sums)
     // (as many as FIT the chip in one round: 36 (c, e) pairs x 8 would be 288 workgroups for 256 CUs, a second round for the
     // last 32 -- round 5: 7, by the trace of an optimize_grid search whose K-factored launches took 25 us for 15 keys)
-    const int want_blocks = n_ce_grid >= 192 ? 1 : (int)std::min<int64_t>(n_qtiles, std::max<int64_t>(1, 256 / n_ce_grid));
+    geo.one_block_a_pair = n_ce_grid >= 192;
+    const int want_blocks = geo.one_block_a_pair ? 1 : (int)std::min<int64_t>(n_qtiles, std::max<int64_t>(1, 256 / n_ce_grid));
     geo.n_qblocks = std::max(std::max(1, (n_units + cap_block - 1) / cap_block), want_blocks);
     return geo;
 }
 
 // Cost model of the assignment, in MFMA steps: a unit costs its steps (in every pass) plus its share of the
-// logs; a builder wave starts with the cost of phase A (tuned on C3 with the in-kernel stamps).
-// (the assignment fixes the order of a point's sums: the shipped library takes the constants of tiles.h, only a
-// diagnostic build -- tiles.h -- or a TUNING build of this file alone, -DCOVEST_TUNE linked against the shipped
-// kernels (tools/build_tune.sh, profiles/r04_c3_factored_lpt_sweep_*.txt), lets the environment override them:
-// here, and nowhere else in this file)
-struct Charges {
-    int unit_overhead, build_cost, shared_div, last_builder_extra;
-    int min_shared; // fewer shared steps than this are left to the MFMA steps
-};
-
+// logs; a builder wave starts with the cost of phase A (tuned on C3 with the in-kernel stamps).  The charges, their
+// overrides in tuning builds and the deal itself: unit_deal.h.
 Charges planner_charges(const covest_model *m)
 {
-    Charges ch = {kUnitOverhead, kBuildCost, kSharedStepsPerMfma, kLastBuilderExtra, kMinSharedSteps};
+    Charges ch = {kUnitOverhead, kBuildCost, kSharedStepsPerMfma, kLastBuilderExtra, kMinSharedSteps, {}};
     // (with a tail an item may stand for up to 32 count-less tiles, tiles.h: the builders walk every one of them
     // while the contraction sees one item -- charge them for the tiles an item holds on average)
+    const bool low_keys = m->has_tiles && m->tv.n_items > 0 && m->low_tile_share >= 0.75;
     if (m->has_tiles && m->tv.n_items > 0)
-        ch.build_cost = (int)std::lround((double)(m->low_tile_share >= 0.75 ? kBuildCostLowKeys : kBuildCost) *
+        ch.build_cost = (int)std::lround((double)(low_keys ? kBuildCostLowKeys : kBuildCost) *
                                          (double)m->tv.n_tiles / (double)m->tv.n_items);
+    for (int w = 0; w < kBuildShareWaves; ++w)
+        ch.build_share[w] = wave_share(low_keys, w);
 #if defined(COVEST_DIAG) || defined(COVEST_TUNE)
-    if (const char *v = std::getenv("COVEST_FACTORED_UNIT_OVERHEAD"))
-        ch.unit_overhead = std::atoi(v);
-    if (const char *v = std::getenv("COVEST_FACTORED_BUILD_COST"))
-        ch.build_cost = std::atoi(v);
-    if (const char *v = std::getenv("COVEST_FACTORED_SHARED_DIV"))
-        ch.shared_div = std::max(1, std::atoi(v));
-    if (const char *v = std::getenv("COVEST_FACTORED_LAST_BUILDER_EXTRA"))
-        ch.last_builder_extra = std::atoi(v);
-    if (const char *v = std::getenv("COVEST_FACTORED_MIN_SHARED"))
-        ch.min_shared = std::atoi(v);
+    charges_from_env(ch);
 #endif
     return ch;
 }
@@ -343,36 +332,18 @@ int place_units(int blk, const PartSpec &ps, const PartColumns &pc, const PartGe
                                         (nsh ? 1 + (nsh + ch.shared_div - 1) / ch.shared_div : 0), 1});
         }
     std::stable_sort(units.begin(), units.end(), [](const Unit &a, const Unit &b) { return a.cost > b.cost; });
-    const int n_bins = std::min(4, nw);
-    std::vector<long> bin_load((size_t)n_bins, 0), wave_load((size_t)nw, 0);
-    if (geo.n_buf == 2) // builders contract less: they fill the next key tile in the same interval
-        for (int w = 0; w < nw && w * 64 < geo.n_columns; ++w) {
-            // (the builder of the TOP copy numbers is the wave every interval waits for -- the stamps of round 3:
-            // its streams stay live over the widest range of keys, and it shares its SIMD with another builder)
-            const int cost = ch.build_cost + (((w + 1) * 64 >= geo.n_columns && w >= n_bins) ? ch.last_builder_extra : 0);
-            bin_load[(size_t)(w % n_bins)] += cost;
-            wave_load[(size_t)w] += cost;
-        }
+    // (the upper builder waves of a plain part skip the items whose limit lies below their copy numbers, band.h: what
+    // they are charged for phase A falls with the wave -- unit_deal.h)
+    const bool shares = wave_shares_apply(geo.one_block_a_pair, ps.list_mode, ps.n_pass, ps.o_base);
+    std::vector<int> cost(units.size()), wave_of(units.size(), -1);
+    for (size_t i = 0; i < units.size(); ++i)
+        cost[i] = units[i].cost;
+    // (two buffers: builders contract less, they fill the next key tile in the same interval)
+    if (!deal_units(cost.data(), (int)units.size(), nw, geo.n_columns, geo.n_buf == 2, geo.units_per_wave, ch, shares, wave_of.data()))
+        return fail(COVEST_E_INVALID, "K-factored plan: no wave has room for a unit (internal)");
     held.assign((size_t)nw, {});
-    for (const Unit &u : units) {
-        int best_wave = -1;
-        for (int w = 0; w < nw; ++w) {
-            if ((int)held[(size_t)w].size() >= geo.units_per_wave)
-                continue;
-            if (best_wave < 0) {
-                best_wave = w;
-                continue;
-            }
-            const long lb = bin_load[(size_t)(w % n_bins)], bb = bin_load[(size_t)(best_wave % n_bins)];
-            if (lb < bb || (lb == bb && wave_load[(size_t)w] < wave_load[(size_t)best_wave]))
-                best_wave = w;
-        }
-        if (best_wave < 0)
-            return fail(COVEST_E_INVALID, "K-factored plan: no wave has room for a unit (internal)");
-        held[(size_t)best_wave].push_back(u);
-        bin_load[(size_t)(best_wave % n_bins)] += u.cost;
-        wave_load[(size_t)best_wave] += u.cost;
-    }
+    for (size_t i = 0; i < units.size(); ++i)
+        held[(size_t)wave_of[i]].push_back(units[i]);
     return COVEST_OK;
 }
 
