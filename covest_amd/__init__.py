@@ -28,3 +28,6 @@ from .posterior import posterior_classes, PosteriorClasses  # noqa: F401,E402
 from . import read_errors  # noqa: F401,E402
 from .read_errors import abundance_weights, read_error_scores, ReadErrorScores  # noqa: F401,E402
 from .read_errors import correct_reads, ReadCorrections  # noqa: F401,E402
+from . import influence  # noqa: F401,E402
+from .influence import (score_rows, read_influence, summarize_influence, rows_moments, rows_moments_device,  # noqa: F401,E402
+                        ReadInfluence)

@@ -35,6 +35,7 @@ EXPORTS = (
     "covest_kmer_count_reads_device", "covest_kmer_partition_info", "covest_kmer_partition_ms", "covest_kmer_memory_limit",
     "covest_kmer_scatter_rate", "covest_kmer_lookup_reads", "covest_kmer_lookup_reads_device",
     "covest_kmer_correct_reads", "covest_kmer_correct_reads_device",
+    "covest_kmer_read_influence", "covest_kmer_read_influence_device", "covest_rows_moments", "covest_rows_moments_device",
     "covest_reads_open", "covest_reads_close", "covest_reads_next", "covest_reads_bytes",
     "covest_thin_histogram", "covest_thin_histogram_timed",
     "covest_truncated_poisson", "covest_truncated_poisson_table",
@@ -218,6 +219,14 @@ def lib():
     L.covest_kmer_correct_reads_device.argtypes = [vp, vp, vp, i64, i64, ctypes.c_uint32, vp, vp, vp]
     L.covest_kmer_correct_reads.restype = ctypes.c_int
     L.covest_kmer_correct_reads.argtypes = [vp, vp, vp, i64, ctypes.c_uint32, vp, vp]
+    L.covest_kmer_read_influence_device.restype = ctypes.c_int
+    L.covest_kmer_read_influence_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, i32, vp, vp]
+    L.covest_kmer_read_influence.restype = ctypes.c_int
+    L.covest_kmer_read_influence.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp]
+    L.covest_rows_moments_device.restype = ctypes.c_int
+    L.covest_rows_moments_device.argtypes = [vp, i64, i32, vp, vp, vp, vp]
+    L.covest_rows_moments.restype = ctypes.c_int
+    L.covest_rows_moments.argtypes = [vp, i64, i32, vp, vp, vp]
     L.covest_reads_open.restype = ctypes.c_int
     L.covest_reads_open.argtypes = [ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.covest_reads_close.restype = None

@@ -1,5 +1,6 @@
 // call_scratch.h -- device memory of the entry points over packed reads that take no handle (abi_sample.cpp,
-// abi_split.cpp): the scratch of the device forms, and the staging of the host forms (ReadsStage, at the end).
+// abi_split.cpp; the block partials of covest_rows_moments_device, abi_influence.cpp): the scratch of the device forms,
+// and the staging of the host forms (ReadsStage, at the end).
 // A device form launches on the caller's stream and returns.  Such a call returns before its kernels have run, so what they work on cannot go with the call: a
 // block is handed to ONE call at a time and to the next only once the event recorded behind that call's last launch has
 // come to pass.  Blocks stay with the process (as the device cache's do); calls that overlap on several streams get a

@@ -117,6 +117,19 @@ def _packed_reads(reads):
     return blob, offsets
 
 
+MAX_INFLUENCE_COLUMNS = 8      # csrc/kmer_influence.h kInfluenceMaxCols
+MAX_INFLUENCE_WINDOWS = 4096   # ... kInfluenceMaxWindows
+
+
+def _influence_table(table):
+    """The (n_rows, n_cols) float64 table of KmerCounts.read_influence, C-contiguous; ValueError before the library is
+    asked."""
+    table = np.ascontiguousarray(np.asarray(table, dtype=np.float64))
+    if table.ndim != 2 or table.shape[0] < 1 or not 1 <= table.shape[1] <= MAX_INFLUENCE_COLUMNS:
+        raise ValueError("table must be (n_rows, n_cols) with at least one row and 1 .. %d columns" % MAX_INFLUENCE_COLUMNS)
+    return table
+
+
 def _or_minus_one(column):
     out = column.astype(np.int64)
     out[column == NO_WINDOW] = -1
@@ -366,6 +379,39 @@ class KmerCounts:
             self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0), int(n_reads), int(read_len),
             int(cutoff), ctypes.c_void_p(d_out_ptr or 0), ctypes.c_void_p(d_fix_ptr or 0), ctypes.c_void_p(stream or 0)),
             "covest_kmer_correct_reads_device")
+        return self
+
+    def read_influence(self, reads, table):
+        """What deleting each read alone does to a sum over the distinct k-mers (covest_kmer_read_influence; k <= 31,
+        read-only) -> float64 (n, n_cols + 1).  `reads`: what lookup takes.  `table`: (n_rows, n_cols) doubles, 1 <=
+        n_cols <= 8, row i the value at abundance i, abundances beyond the last row take the last row.  Column c of row
+        r is the sum over the DISTINCT keys x of read r of table[a_x - m_x][c] - table[a_x][c], a_x the table's count
+        and m_x the windows of r with key x; the last column is the number of windows.  A read shorter than k gives
+        zeros; a read with more than MAX_INFLUENCE_WINDOWS windows raises CovestHipError (the compare is quadratic).
+        The sums are made in a fixed order: the same bits on every run (covest_amd.influence)."""
+        blob, offsets = _packed_reads(reads)
+        table = _influence_table(table)
+        n = offsets.size - 1
+        rows = np.zeros((n, table.shape[1] + 1), dtype=np.float64)
+        if n:
+            _capi.check(_capi.lib().covest_kmer_read_influence(
+                self._handle, ctypes.c_void_p(blob.ctypes.data), ctypes.c_void_p(offsets.ctypes.data), n,
+                ctypes.c_void_p(table.ctypes.data), table.shape[0], table.shape[1], ctypes.c_void_p(rows.ctypes.data)),
+                "covest_kmer_read_influence")
+        return rows
+
+    def read_influence_device(self, d_bases_ptr, n_reads, read_len, d_table_ptr, n_rows, n_cols, d_rows_ptr,
+                              d_offsets_ptr=None, stream=None):
+        """The same for reads resident in HBM into a device array (raw pointers; covest_kmer_read_influence_device):
+        asynchronous on `stream`, which must be the stream of the adds it is to see (or ordered after them by the
+        caller).  `d_table_ptr`: double[n_rows][n_cols]; `d_rows_ptr`: double[n_reads][n_cols + 1], both aligned to 8
+        bytes.  With offsets a read of more than MAX_INFLUENCE_WINDOWS windows gets NaN in its value columns; reads of
+        one length that long are refused.  It does not look at the overflow flag."""
+        _capi.require_shared_runtime("KmerCounts.read_influence_device")
+        _capi.check(_capi.lib().covest_kmer_read_influence_device(
+            self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0), int(n_reads), int(read_len),
+            ctypes.c_void_p(d_table_ptr or 0), int(n_rows), int(n_cols), ctypes.c_void_p(d_rows_ptr or 0),
+            ctypes.c_void_p(stream or 0)), "covest_kmer_read_influence_device")
         return self
 
     def memory_limit(self, max_bytes):

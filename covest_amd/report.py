@@ -27,7 +27,7 @@ def _finite_int(x):
 def print_output(hist_orig, model, success, sample_factor, estimated=None, guess=None, orig=None,
                  reads_size=None, silent=False, orig_sample_factor=1, starting_points=1,
                  use_grid_search=False, intervals=None, information=None, bootstrap=None, jackknife=None,
-                 posterior=None, read_errors=None, corrections=None):
+                 posterior=None, read_errors=None, corrections=None, read_influence=None):
     """`intervals`: the dict covest_amd.profile.coverage_interval returns; the record then carries the likelihood-ratio
     interval of the coverage, of the genome size and its level.  Without it the record is the reference's, key for key.
     `information`: the dict covest_amd.information.observed_information returns (a key 'level' in it chooses the Wald
@@ -61,7 +61,13 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
     read_errors_mean_expected_erroneous_kmers.  Without it the record is unchanged.
     `corrections`: what covest_amd.read_errors.correct_reads (or KmerCounts.correct) returns; the record then carries
     corrections_cutoff, corrections_reads and the totals corrections_runs, corrections_corrected,
-    corrections_ambiguous and corrections_unfixable.  Without it the record is unchanged."""
+    corrections_ambiguous and corrections_unfixable.  Without it the record is unchanged.
+    `read_influence`: the ReadInfluence covest_amd.influence.read_influence returns, or its summary() (sample factor 1
+    by its own rule, so nothing is scaled); the record then carries read_influence_reads, read_influence_level and, per
+    free parameter and for genome_size, read_influence_se_<name> and read_influence_interval_<name>: the linearised
+    delete-ONE-read jackknife, the genome held fixed, first order in the inverse information.  Where it
+    has no covariance to start from the record carries read_influence_reason instead.  Without it the record is
+    unchanged."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -185,6 +191,19 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
         record['corrections_reads'] = int(corrections.runs.size)
         for name in ('runs', 'corrected', 'ambiguous', 'unfixable'):
             record['corrections_' + name] = int(getattr(corrections, name).sum())
+    if read_influence is not None:
+        summary = read_influence.summary() if hasattr(read_influence, 'summary') else read_influence
+        record['read_influence_reads'] = int(summary['reads'])
+        record['read_influence_level'] = float(summary['level'])
+        if summary.get('reason') is not None:
+            record['read_influence_reason'] = str(summary['reason'])
+        for name in list(model.params) + ['genome_size']:
+            value = summary['standard_errors'].get(name)
+            if value is not None:
+                record['read_influence_se_%s' % name] = float(value)
+            interval = summary['intervals'].get(name)
+            if interval is not None:
+                record['read_influence_interval_%s' % name] = [float(v) for v in interval]
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

@@ -457,6 +457,39 @@ int covest_kmer_correct_reads_device(covest_kmer *c, const uint8_t *d_bases, con
                                      int64_t read_len, uint32_t cutoff, uint8_t *d_out, uint32_t *d_fix, void *stream);
 int covest_kmer_correct_reads(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
                               uint32_t cutoff, uint8_t *out, uint32_t *fix);
+/* The influence of ONE read on a sum over the distinct k-mers (k <= 31; no reference counterpart; read-only on the
+ * table).  `table` is double[n_rows][n_cols] row-major, n_rows >= 1, 1 <= n_cols <= 8: row i is
+ * the value at abundance i, and the row of an abundance a is min(a, n_rows - 1).  With a_x the count the table holds
+ * for key x and m_x the number of windows of read r whose key is x, deleting r moves x from a_x to a_x - m_x, so
+ *   rows[r][c] = sum over the DISTINCT keys x of r of  table[row(max(a_x - m_x, 0))][c] - table[row(a_x)][c],  c < n_cols,
+ *   rows[r][n_cols] = the number of windows of r, as a double.
+ * `rows` is double[n_reads][n_cols + 1].  a_x < m_x can only happen when the table was not counted from these reads;
+ * it takes row 0.  A read shorter than k has every column +0.0: the key covest_kmer_add counts for it is NOT looked
+ * up, as in covest_kmer_lookup_reads.  The sums are made in a fixed order (csrc/kmer_influence.h): the same bits on
+ * every run.  The compare that finds m_x is quadratic in a read's windows: a read with more than 4096 windows gets
+ * NaN in its value columns from the device form with d_offsets (its window count is still written), and
+ * COVEST_E_UNSUPPORTED, before anything is launched, from the host form and from the device form with reads of one
+ * length.
+ * Device form: asynchronous on `stream`; d_bases at any alignment, d_table and d_rows aligned to 8 bytes; d_offsets
+ * NULL: every read is read_len bases.  It must be ORDERED AFTER the adds it is to see and never looks at the overflow
+ * flag.  Host form: copies, waits, and answers COVEST_E_NOMEM if an add overflowed.
+ * COVEST_E_UNSUPPORTED: k > 31.  COVEST_E_INVALID: a null counter, negative sizes, bad offsets, no offsets and
+ * read_len < 0, n_rows < 1, n_cols outside 1 .. 8, a null table or rows, or a counter that holds a
+ * covest_kmer_count_reads_device result.  n_reads == 0: COVEST_OK, nothing launched. */
+int covest_kmer_read_influence_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                                      int64_t read_len, const double *d_table, int64_t n_rows, int32_t n_cols,
+                                      double *d_rows, void *stream);
+int covest_kmer_read_influence(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
+                               const double *table, int64_t n_rows, int32_t n_cols, double *rows);
+/* The first two moments of n rows of q doubles about `centre` (1 <= q <= 9), with d_r = rows[r] - centre:
+ *   sum[k] = sum_r d_r[k];   cross[k q - k (k - 1) / 2 + (l - k)] = sum_r d_r[k] d_r[l] for k <= l
+ * (the packed upper triangle, row by row: q (q + 1) / 2 entries).  No floating-point atomic: the shape of the reduction
+ * is a function of n alone (csrc/kmer_influence.h), so the same rows give the same bits on every run.  n == 0: zeros.
+ * Device form: asynchronous on `stream`, on the calling thread's current device; every array aligned to 8 bytes.
+ * COVEST_E_INVALID: n < 0 or beyond 2^40, q outside 1 .. 9, a null array. */
+int covest_rows_moments_device(const double *d_rows, int64_t n, int32_t q, const double *d_centre, double *d_sum,
+                               double *d_cross, void *stream);
+int covest_rows_moments(const double *rows, int64_t n, int32_t q, const double *centre, double *sum, double *cross);
 
 /* ---- FASTA / FASTQ front-end of the k-mer histogram: bin/kmer_hist.py:44-54 preprocess, :67-74 load_reads ----
  * HOST code (the only HIP calls: a device count and the allocation of page-locked buffers): the mapped file
