@@ -5,24 +5,16 @@
 
 using namespace covest;
 
-extern "C" {
+namespace {
 
-int covest_kmer_correct_reads_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
-                                     int64_t read_len, uint32_t cutoff, uint8_t *d_out, uint32_t *d_fix, void *stream)
+int correct_locked(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads, int64_t read_len,
+                   uint32_t cutoff, uint8_t *d_out, uint32_t *d_fix, void *stream)
 {
     const std::string name("covest_kmer_correct_reads_device");
-    if (!c)
-        return fail(COVEST_E_INVALID, name + ": null counter");
-    std::lock_guard<std::mutex> guard(c->lock);
-    if (n_reads < 0 || (!d_offsets && (read_len < 0 || read_len >= ((int64_t)1 << 32))))
-        return fail(COVEST_E_INVALID, name + ": negative size, or no offsets and no read_len below 2^32");
+    COVEST_TRY(fail_if(check_table_reads_sizes(name, d_offsets != nullptr, n_reads, read_len)));
     if ((uintptr_t)d_fix % (4 * sizeof(uint32_t)))
         return fail(COVEST_E_INVALID, name + ": fix is not aligned to its rows of 16 bytes");
-    if (c->wide)
-        return fail(COVEST_E_UNSUPPORTED, name + ": k must be at most 31 (keys of one word)");
-    if (c->bulk)
-        return fail(COVEST_E_INVALID, name + ": the counter holds a covest_kmer_count_reads_device result "
-                                             "(its keys are not in the table); covest_kmer_clear first");
+    COVEST_TRY(fail_if(check_table_holds_keys(name, c->wide, c->bulk)));
     if (n_reads == 0)
         return COVEST_OK;
     if (!d_bases || !d_out)
@@ -33,11 +25,23 @@ int covest_kmer_correct_reads_device(covest_kmer *c, const uint8_t *d_bases, con
             return fail(COVEST_E_INVALID, name + ": out overlaps the bases without being the bases (in place: out == bases)");
     }
     DeviceGuard dev_guard(c->device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
+    COVEST_TRY(dev_guard.status());
     HIP_TRY(launch_kmer_correct(d_bases, d_offsets, n_reads, read_len, c->canonical, c->table, cutoff, d_out, d_fix,
                                 static_cast<hipStream_t>(stream)));
     return COVEST_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int covest_kmer_correct_reads_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                                     int64_t read_len, uint32_t cutoff, uint8_t *d_out, uint32_t *d_fix, void *stream)
+{
+    if (!c)
+        return fail(COVEST_E_INVALID, "covest_kmer_correct_reads_device: null counter");
+    std::lock_guard<std::mutex> guard(c->lock);
+    return correct_locked(c, d_bases, d_offsets, n_reads, read_len, cutoff, d_out, d_fix, stream);
 }
 
 int covest_kmer_correct_reads(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
@@ -45,26 +49,22 @@ int covest_kmer_correct_reads(covest_kmer *c, const uint8_t *bases, const int64_
 {
     if (!c || n_reads < 0 || (n_reads > 0 && !offsets))
         return fail(COVEST_E_INVALID, "covest_kmer_correct_reads: bad argument");
-    if (c->wide)
-        return fail(COVEST_E_UNSUPPORTED, "covest_kmer_correct_reads: k must be at most 31 (keys of one word)");
+    COVEST_TRY(fail_if(check_table_holds_keys("covest_kmer_correct_reads", c->wide, false))); // (bulk: the device form's)
     if (n_reads == 0)
         return COVEST_OK;
     const int64_t n_bytes = offsets[n_reads] - offsets[0];
     if (n_bytes < 0 || (n_bytes > 0 && !bases) || !out)
         return fail(COVEST_E_INVALID, "covest_kmer_correct_reads: bad offsets, or null bases or null out");
-    DeviceGuard dev_guard(c->device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
     const size_t n_pos = (size_t)n_bytes, n = (size_t)n_reads;
+    KmerHostCall call(c);
+    COVEST_TRY(call.open(bases, offsets, n_reads));
     DevBuf d_fix; // (goes with the call; the copies back have waited for the kernel)
-    COVEST_TRY(stage_reads_in_counter(c, bases, offsets, n_reads));
     if (fix)
         HIP_TRY(d_fix.reserve(n * 4 * sizeof(uint32_t)));
-    // in place on the staged copy of the bases: only the corrected bytes are stored
-    COVEST_TRY(covest_kmer_correct_reads_device(c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(), n_reads, 0, cutoff,
-                                                c->ws_bases.as<uint8_t>(), fix ? d_fix.as<uint32_t>() : nullptr, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    COVEST_TRY(kmer_check_partial(c, "covest_kmer_correct_reads"));
+    // in place on the staged copy of the bases: only the corrected bytes are stored (the copy back is under the lock too)
+    COVEST_TRY(correct_locked(c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(), n_reads, 0, cutoff,
+                              c->ws_bases.as<uint8_t>(), fix ? d_fix.as<uint32_t>() : nullptr, nullptr));
+    COVEST_TRY(call.close("covest_kmer_correct_reads"));
     if (n_pos)
         HIP_TRY(hipMemcpy(out, c->ws_bases.ptr, n_pos, hipMemcpyDeviceToHost));
     if (fix)

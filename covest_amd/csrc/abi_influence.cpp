@@ -9,35 +9,40 @@ using namespace covest;
 
 namespace {
 
-// The checks both influence forms share (after the null-counter check).
-int check_influence(const char *who, const covest_kmer *c, int64_t n_reads, int64_t read_len, bool has_offsets,
-                    const void *table, int64_t n_rows, int32_t n_cols, const void *rows)
-{
-    const std::string name(who);
-    if (n_reads < 0 || (!has_offsets && (read_len < 0 || read_len >= ((int64_t)1 << 32))))
-        return fail(COVEST_E_INVALID, name + ": negative size, or no offsets and no read_len below 2^32");
-    if (n_rows < 1 || n_cols < 1 || n_cols > kInfluenceMaxCols)
-        return fail(COVEST_E_INVALID, name + ": the table needs at least one row and 1 .. " +
-                                          std::to_string(kInfluenceMaxCols) + " columns");
-    if (n_rows > std::numeric_limits<int64_t>::max() / (int64_t)(n_cols * sizeof(double)))
-        return fail(COVEST_E_INVALID, name + ": a table beyond 64-bit sizes");
-    if (!table || (n_reads > 0 && !rows))
-        return fail(COVEST_E_INVALID, name + ": null table or rows");
-    if ((uintptr_t)table % alignof(double) || (uintptr_t)rows % alignof(double))
-        return fail(COVEST_E_INVALID, name + ": the table or the rows are not aligned to 8 bytes");
-    if (c->wide)
-        return fail(COVEST_E_UNSUPPORTED, name + ": k must be at most 31 (keys of one word)");
-    if (c->bulk)
-        return fail(COVEST_E_INVALID, name + ": the counter holds a covest_kmer_count_reads_device result "
-                                             "(its keys are not in the table); covest_kmer_clear first");
-    return COVEST_OK;
-}
-
 int too_many_windows(const char *who, int64_t read, int64_t windows)
 {
     return fail(COVEST_E_UNSUPPORTED, std::string(who) + ": read " + std::to_string(read) + " has " + std::to_string(windows) +
                                           " windows, more than " + std::to_string(kInfluenceMaxWindows) +
                                           " (the compare is quadratic in them)");
+}
+
+int influence_locked(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads, int64_t read_len,
+                     const double *d_table, int64_t n_rows, int32_t n_cols, double *d_rows, void *stream)
+{
+    const std::string name("covest_kmer_read_influence_device");
+    COVEST_TRY(fail_if(check_table_reads_sizes(name, d_offsets != nullptr, n_reads, read_len)));
+    if (n_rows < 1 || n_cols < 1 || n_cols > kInfluenceMaxCols)
+        return fail(COVEST_E_INVALID, name + ": the table needs at least one row and 1 .. " +
+                                          std::to_string(kInfluenceMaxCols) + " columns");
+    if (n_rows > std::numeric_limits<int64_t>::max() / (int64_t)(n_cols * sizeof(double)))
+        return fail(COVEST_E_INVALID, name + ": a table beyond 64-bit sizes");
+    if (!d_table || (n_reads > 0 && !d_rows))
+        return fail(COVEST_E_INVALID, name + ": null table or rows");
+    if ((uintptr_t)d_table % alignof(double) || (uintptr_t)d_rows % alignof(double))
+        return fail(COVEST_E_INVALID, name + ": the table or the rows are not aligned to 8 bytes");
+    COVEST_TRY(fail_if(check_table_holds_keys(name, c->wide, c->bulk)));
+    if (n_reads == 0)
+        return COVEST_OK;
+    if (!d_bases)
+        return fail(COVEST_E_INVALID, name + ": null bases");
+    // reads of one length: the host sees the windows (with offsets the kernel answers NaN for such a read)
+    if (!d_offsets && read_len - c->table.k + 1 > kInfluenceMaxWindows)
+        return too_many_windows(name.c_str(), 0, read_len - c->table.k + 1);
+    DeviceGuard dev_guard(c->device);
+    COVEST_TRY(dev_guard.status());
+    HIP_TRY(launch_kmer_read_influence(d_bases, d_offsets, n_reads, read_len, c->canonical, c->table, d_table, n_rows,
+                                       n_cols, d_rows, static_cast<hipStream_t>(stream)));
+    return COVEST_OK;
 }
 
 int check_moments(const char *who, const void *rows, int64_t n, int32_t q, const void *centre, const void *sum,
@@ -67,21 +72,7 @@ int covest_kmer_read_influence_device(covest_kmer *c, const uint8_t *d_bases, co
     if (!c)
         return fail(COVEST_E_INVALID, "covest_kmer_read_influence_device: null counter");
     std::lock_guard<std::mutex> guard(c->lock);
-    COVEST_TRY(check_influence("covest_kmer_read_influence_device", c, n_reads, read_len, d_offsets != nullptr, d_table,
-                               n_rows, n_cols, d_rows));
-    if (n_reads == 0)
-        return COVEST_OK;
-    if (!d_bases)
-        return fail(COVEST_E_INVALID, "covest_kmer_read_influence_device: null bases");
-    // reads of one length: the host sees the windows (with offsets the kernel answers NaN for such a read)
-    if (!d_offsets && read_len - c->table.k + 1 > kInfluenceMaxWindows)
-        return too_many_windows("covest_kmer_read_influence_device", 0, read_len - c->table.k + 1);
-    DeviceGuard dev_guard(c->device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
-    HIP_TRY(launch_kmer_read_influence(d_bases, d_offsets, n_reads, read_len, c->canonical, c->table, d_table, n_rows,
-                                       n_cols, d_rows, static_cast<hipStream_t>(stream)));
-    return COVEST_OK;
+    return influence_locked(c, d_bases, d_offsets, n_reads, read_len, d_table, n_rows, n_cols, d_rows, stream);
 }
 
 int covest_kmer_read_influence(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
@@ -94,8 +85,7 @@ int covest_kmer_read_influence(covest_kmer *c, const uint8_t *bases, const int64
                                           std::to_string(kInfluenceMaxCols) + " columns, and the rows a place");
     if (n_rows > std::numeric_limits<int64_t>::max() / (int64_t)(n_cols * sizeof(double)))
         return fail(COVEST_E_INVALID, "covest_kmer_read_influence: a table beyond 64-bit sizes");
-    if (c->wide)
-        return fail(COVEST_E_UNSUPPORTED, "covest_kmer_read_influence: k must be at most 31 (keys of one word)");
+    COVEST_TRY(fail_if(check_table_holds_keys("covest_kmer_read_influence", c->wide, false))); // (bulk: the device form's)
     if (n_reads == 0)
         return COVEST_OK;
     const int64_t n_bytes = offsets[n_reads] - offsets[0];
@@ -108,20 +98,17 @@ int covest_kmer_read_influence(covest_kmer *c, const uint8_t *bases, const int64
         if (windows > kInfluenceMaxWindows)
             return too_many_windows("covest_kmer_read_influence", i, windows);
     }
-    DeviceGuard dev_guard(c->device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
     const size_t table_bytes = (size_t)n_rows * (size_t)n_cols * sizeof(double);
     const size_t rows_bytes = (size_t)n_reads * (size_t)(n_cols + 1) * sizeof(double);
+    KmerHostCall call(c);
+    COVEST_TRY(call.open(bases, offsets, n_reads));
     DevBuf d_table, d_rows; // (go with the call; the copy back has waited for the kernel)
-    COVEST_TRY(stage_reads_in_counter(c, bases, offsets, n_reads));
     HIP_TRY(d_table.reserve(table_bytes));
     HIP_TRY(hipMemcpy(d_table.ptr, table, table_bytes, hipMemcpyHostToDevice));
     HIP_TRY(d_rows.reserve(rows_bytes));
-    COVEST_TRY(covest_kmer_read_influence_device(c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(), n_reads, 0,
-                                                 d_table.as<double>(), n_rows, n_cols, d_rows.as<double>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    COVEST_TRY(kmer_check_partial(c, "covest_kmer_read_influence"));
+    COVEST_TRY(influence_locked(c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(), n_reads, 0, d_table.as<double>(),
+                                n_rows, n_cols, d_rows.as<double>(), nullptr));
+    COVEST_TRY(call.close("covest_kmer_read_influence"));
     HIP_TRY(hipMemcpy(rows, d_rows.ptr, rows_bytes, hipMemcpyDeviceToHost));
     return COVEST_OK;
 }

@@ -400,13 +400,24 @@ double lgamma_of_factorial(int64_t j);
 
 int64_t launch_record_text(const LaunchRecord &r, char *buf, int64_t cap); // (kernels.h)
 
-// ---- kmer_host.cpp: what the host forms over the counter's table share (abi_lookup.cpp, abi_correct.cpp)
-// The reads of bases / offsets[n_reads + 1] (n_reads > 0, offsets[n_reads] >= offsets[0]) into c->ws_bases and, counted
-// from 0, c->ws_offsets.  Takes the counter's lock for the reserve and the copies, and lets it go.
-int stage_reads_in_counter(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads);
-// The sticky overflow flag (until covest_kmer_clear: an add overflowed, so the counts are partial), read after the
-// device has been waited for: COVEST_E_NOMEM in `who`'s name if it is set.
-int kmer_check_partial(covest_kmer *c, const char *who);
+// ---- kmer_host.cpp: a host form over the counter's table as a scope (covest_kmer_add, abi_lookup.cpp, abi_correct.cpp,
+// abi_influence.cpp), after the form's own checks: the counter's lock, then its device; open() stages the reads of bases
+// / offsets[n_reads + 1] (n_reads > 0, offsets[n_reads] >= offsets[0]) into c->ws_bases and, counted from 0,
+// c->ws_offsets; the caller reserves its outputs and launches (the *_locked body of its device form: the lock is not
+// recursive); close(), of the forms that only read the table, waits for the device and reads the sticky overflow flag
+// (set: COVEST_E_NOMEM, the counts `reader` saw are partial; the add words its own); the caller copies back.  The lock is
+// held until the object goes away: no other thread stages into ws_bases / ws_offsets under a kernel or that copy back.
+class KmerHostCall {
+  public:
+    explicit KmerHostCall(covest_kmer *c) : c(c), lock_(c->lock), dev_(c->device) {}
+    int open(const uint8_t *bases, const int64_t *offsets, int64_t n_reads);
+    int close(const char *reader);
+
+  private:
+    covest_kmer *c;
+    std::lock_guard<std::mutex> lock_;
+    DeviceGuard dev_;
+};
 
 // ---- tiles_host.cpp
 constexpr int64_t kListModeMaxPoints = 4096; // longer point lists are throughput work: K-direct

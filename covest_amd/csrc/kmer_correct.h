@@ -39,7 +39,7 @@
 
 namespace covest {
 
-// Asynchronous on `stream`; the launches are cut by kmer_plan::wave_reads_per_launch like the lookup's.
+// Asynchronous on `stream`; the launches are the visits of kmer_plan::for_each_wave_launch, `out` advanced as `bases` is.
 hipError_t launch_kmer_correct(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t fixed_len,
                                int canonical, const KmerTable &t, uint32_t cutoff, unsigned char *out, uint32_t *fix,
                                hipStream_t stream);

@@ -13,8 +13,7 @@
 // loads (the whole-read case of a short read: 3 n a position).  Measured beside the lookup: DESIGN.md section 6af.
 #include "kmer_correct.h"
 
-#include "kmer_table.h"
-#include "wave.h"
+#include "wave_read.h"
 
 namespace covest {
 
@@ -93,8 +92,10 @@ __global__ __launch_bounds__(256) void kmer_correct_kernel(const unsigned char *
                                                            const KmerTable t, uint32_t cutoff, unsigned char *out,
                                                            uint32_t *__restrict__ fix)
 {
+    // wave_read.h's opening with the wave index made scalar (readfirstlane): with the plain index the other four kernels
+    // share, this one takes 75 VGPRs for 44 and loses a wave of occupancy; with the scalar one the lookup is 7 % slower
     const int lane = threadIdx.x & (kWave - 1);
-    const int64_t r = (int64_t)blockIdx.x * (blockDim.x / kWave) + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    const int64_t r = (int64_t)blockIdx.x * kWaveReadsPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     if (r >= n_reads) // (the whole wave: a wave is a read)
         return;
     const int64_t p0 = offsets ? offsets[r] : r * fixed_len;
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(256) void kmer_correct_kernel(const unsigned char *
             bool weak = false;
             if (s < n_windows) {
                 unsigned long long h, rc;
-                window_codes(seq, s, len, k, h, rc);
+                window_codes(seq, s, len, k, h, rc); // (window_key in two steps: le_cur is rc before the canonical swap)
                 le_cur = ~rc & kmer_mask(k);
                 canonical_pair(h, rc, canonical);
                 weak = table_find(t, h, rc) < (unsigned long long)cutoff;
@@ -183,18 +184,11 @@ hipError_t launch_kmer_correct(const unsigned char *bases, const int64_t *offset
                                int canonical, const KmerTable &t, uint32_t cutoff, unsigned char *out, uint32_t *fix,
                                hipStream_t stream)
 {
-    if (n_reads <= 0)
-        return hipSuccess;
-    const int reads_per_block = 4;
-    const int64_t reads_per_launch = kmer_plan::wave_reads_per_launch(reads_per_block);
-    for (int64_t first = 0; first < n_reads; first += reads_per_launch) {
-        const int64_t n = kmer_plan::reads_of_launch(first, n_reads, reads_per_launch);
-        const int64_t at = offsets ? 0 : first * fixed_len; // (with offsets the reads say where they are themselves)
-        const dim3 grid((unsigned)((n + reads_per_block - 1) / reads_per_block));
-        hipLaunchKernelGGL(kmer_correct_kernel, grid, dim3(reads_per_block * kWave), 0, stream, bases + at,
-                           offsets ? offsets + first : nullptr, n, fixed_len, canonical, t, cutoff, out + at,
-                           fix ? fix + 4 * first : nullptr);
-    }
+    kmer_plan::for_each_wave_launch(n_reads, fixed_len, offsets != nullptr, kWaveReadsPerBlock, [&](const kmer_plan::WaveLaunch &l) {
+        hipLaunchKernelGGL(kmer_correct_kernel, dim3((unsigned)l.blocks), dim3(kWaveReadsPerBlock * kWave), 0, stream,
+                           bases + l.byte_at, offsets ? offsets + l.first : nullptr, l.n, fixed_len, canonical, t, cutoff,
+                           out + l.byte_at, fix ? fix + 4 * l.first : nullptr); // (out as bases: in place is out == bases)
+    });
     return hipGetLastError();
 }
 

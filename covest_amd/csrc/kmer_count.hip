@@ -19,8 +19,7 @@
 #include <algorithm>
 
 #include "kernels.h"
-#include "kmer_table.h"
-#include "wave.h"
+#include "wave_read.h"
 
 namespace covest {
 
@@ -34,8 +33,7 @@ __device__ __forceinline__ void count_window(const unsigned char *__restrict__ s
                                              int canonical, const KmerTable &t, int *overflow)
 {
     unsigned long long h, rc;
-    window_codes(seq, s, len, k, h, rc);
-    canonical_pair(h, rc, canonical);
+    window_key(seq, s, len, k, canonical, h, rc);
     table_add(t, h, rc, 1ull, overflow);
 }
 
@@ -44,20 +42,16 @@ __global__ __launch_bounds__(256) void kmer_count_kernel(const unsigned char *__
                                                          int64_t n_reads, int64_t fixed_len, int k,
                                                          int canonical, const KmerTable t, int *overflow)
 {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t r = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
-    if (r >= n_reads)
+    WaveRead w;
+    if (!wave_read(bases, offsets, n_reads, fixed_len, k, w))
         return;
-    const int64_t p0 = offsets ? offsets[r] : r * fixed_len;
-    const int64_t len = offsets ? offsets[r + 1] - p0 : fixed_len;
-    const unsigned char *seq = bases + p0;
-    if (len < k) {
+    if (w.len < k) {
         // hash_kmer(seq[:k]) of a read shorter than k: the hash of what there is, counted once;
         // an empty read counts k-mer 0 (bin/kmer_hist.py:36-37)
-        if (lane == 0) {
+        if (w.lane == 0) {
             unsigned long long h = 0, rc = 0;
-            for (int i = 0; i < (int)len; ++i) {
-                const unsigned long long c = base_code(seq[i]);
+            for (int i = 0; i < (int)w.len; ++i) {
+                const unsigned long long c = base_code(w.seq[i]);
                 h = (h << 2) | c;
             }
             rc = revcomp_code(h, k);
@@ -66,9 +60,8 @@ __global__ __launch_bounds__(256) void kmer_count_kernel(const unsigned char *__
         }
         return;
     }
-    const int64_t n_windows = len - k + 1;
-    for (int64_t s = lane; s < n_windows; s += kWave)
-        count_window(seq, s, len, k, canonical, t, overflow);
+    for (int64_t s = w.lane; s < w.len - k + 1; s += kWave) // (len >= k: w.n_windows without its clamp, which costs 0.5 %)
+        count_window(w.seq, s, w.len, k, canonical, t, overflow);
 }
 
 // Reads of ONE length (what a sequencing run's FASTQ holds, and config 5's synthetic reads): the windows of all reads
@@ -182,15 +175,10 @@ hipError_t launch_kmer_count(const unsigned char *bases, const int64_t *offsets,
         }
         return hipGetLastError();
     }
-    const int reads_per_block = 4;
-    const int64_t reads_per_launch = kmer_plan::wave_reads_per_launch(reads_per_block);
-    for (int64_t first = 0; first < n_reads; first += reads_per_launch) {
-        const int64_t n = kmer_plan::reads_of_launch(first, n_reads, reads_per_launch);
-        const dim3 grid((unsigned)((n + reads_per_block - 1) / reads_per_block));
-        hipLaunchKernelGGL(kmer_count_kernel, grid, dim3(reads_per_block * kWave), 0, stream,
-                           offsets ? bases : bases + first * fixed_len, offsets ? offsets + first : nullptr, n,
-                           fixed_len, k, canonical, t, overflow);
-    }
+    kmer_plan::for_each_wave_launch(n_reads, fixed_len, offsets != nullptr, kWaveReadsPerBlock, [&](const kmer_plan::WaveLaunch &l) {
+        hipLaunchKernelGGL(kmer_count_kernel, dim3((unsigned)l.blocks), dim3(kWaveReadsPerBlock * kWave), 0, stream,
+                           bases + l.byte_at, offsets ? offsets + l.first : nullptr, l.n, fixed_len, k, canonical, t, overflow);
+    });
     return hipGetLastError();
 }
 

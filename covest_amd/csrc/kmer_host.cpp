@@ -308,10 +308,10 @@ int finish(BulkCall &b)
 
 namespace covest {
 
-int stage_reads_in_counter(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads)
+int KmerHostCall::open(const uint8_t *bases, const int64_t *offsets, int64_t n_reads)
 {
+    COVEST_TRY(dev_.status());
     const size_t n_pos = (size_t)(offsets[n_reads] - offsets[0]), n = (size_t)n_reads;
-    std::lock_guard<std::mutex> guard(c->lock);
     HIP_TRY(c->ws_bases.reserve(std::max<size_t>(n_pos, 1)));
     HIP_TRY(c->ws_offsets.reserve((n + 1) * sizeof(int64_t)));
     if (n_pos)
@@ -323,14 +323,13 @@ int stage_reads_in_counter(covest_kmer *c, const uint8_t *bases, const int64_t *
     return COVEST_OK;
 }
 
-int kmer_check_partial(covest_kmer *c, const char *who)
+int KmerHostCall::close(const char *reader)
 {
+    HIP_TRY(hipDeviceSynchronize());
     int flag = 0;
     HIP_TRY(hipMemcpy(&flag, c->flag.ptr, sizeof(int), hipMemcpyDeviceToHost));
-    if (flag)
-        return fail(COVEST_E_NOMEM, std::string(who) + ": k-mer table overflow, the counts are partial: "
-                                                       "covest_kmer_clear and recount with more slots");
-    return COVEST_OK;
+    return !flag ? COVEST_OK : fail(COVEST_E_NOMEM, std::string(reader) + ": k-mer table overflow, the counts are partial: "
+                                                                          "covest_kmer_clear and recount with more slots");
 }
 
 } // namespace covest
@@ -468,20 +467,24 @@ int covest_kmer_reserve(covest_kmer *c, int64_t min_slots)
     return kmer_check_overflow(c);
 }
 
+// covest_kmer_add_device with the counter's lock held (covest_kmer_add holds it for its whole call: host.h KmerHostCall)
+static int add_device_locked(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                             int64_t read_len, void *stream)
+{
+    COVEST_TRY(fail_if(check_table_holds_keys("covest_kmer_add_device", 0, c->bulk))); // (keys of any width are added)
+    DeviceGuard dev_guard(c->device);
+    COVEST_TRY(dev_guard.status());
+    HIP_TRY(table_count(c, d_bases, d_offsets, n_reads, read_len, static_cast<hipStream_t>(stream)));
+    return COVEST_OK;
+}
+
 int covest_kmer_add_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets,
                            int64_t n_reads, int64_t read_len, void *stream)
 {
     if (!c || n_reads < 0 || (n_reads > 0 && !d_bases) || (!d_offsets && read_len < 0))
         return fail(COVEST_E_INVALID, "covest_kmer_add_device: bad argument");
     std::lock_guard<std::mutex> guard(c->lock);
-    if (c->bulk)
-        return fail(COVEST_E_INVALID, "covest_kmer_add_device: the counter holds a covest_kmer_count_reads_device result "
-                                      "(its keys are not in the table); covest_kmer_clear first");
-    DeviceGuard dev_guard(c->device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
-    HIP_TRY(table_count(c, d_bases, d_offsets, n_reads, read_len, static_cast<hipStream_t>(stream)));
-    return COVEST_OK;
+    return add_device_locked(c, d_bases, d_offsets, n_reads, read_len, stream);
 }
 
 int covest_kmer_add(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads)
@@ -493,15 +496,11 @@ int covest_kmer_add(covest_kmer *c, const uint8_t *bases, const int64_t *offsets
     const int64_t n_bytes = offsets[n_reads] - offsets[0];
     if (n_bytes < 0 || (n_bytes > 0 && !bases))
         return fail(COVEST_E_INVALID, "covest_kmer_add: bad offsets");
-    DeviceGuard dev_guard(c->device);
-    if (dev_guard.status() != COVEST_OK)
-        return dev_guard.status();
-    COVEST_TRY(stage_reads_in_counter(c, bases, offsets, n_reads));
-    int rc = covest_kmer_add_device(c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(), n_reads, 0, nullptr);
-    if (rc != COVEST_OK)
-        return rc;
+    KmerHostCall call(c);
+    COVEST_TRY(call.open(bases, offsets, n_reads));
+    COVEST_TRY(add_device_locked(c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(), n_reads, 0, nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    return kmer_check_overflow(c);
+    return kmer_check_overflow(c); // (the add's own words, not close()'s: the batch is partly counted, the table can grow)
 }
 
 int covest_kmer_histogram(covest_kmer *c, int64_t *out, int64_t out_len, int64_t *needed_len,

@@ -4,7 +4,7 @@
 //
 // ---- launch_kmer_read_influence ------------------------------------------------------------------------------------
 // One wave64 a read, four reads a workgroup of 256 threads, reads with offsets and reads of one length alike; the
-// launches are cut by kmer_plan::wave_reads_per_launch.  A window's key is window_codes + canonical_pair, so the same
+// launches are the visits of kmer_plan::for_each_wave_launch.  A window's key is window_key (wave_read.h), so the same
 // bytes make the same key as in counting; its abundance a is table_find (the table's 64-bit count).
 //
 //   table  double[n_rows][n_cols] row-major, n_rows >= 1, 1 <= n_cols <= kInfluenceMaxCols: row i is the value at

@@ -6,9 +6,7 @@
 // load, plus the stagings.
 #include "kmer_influence.h"
 
-#include "kmer_plan.h"
-#include "kmer_table.h"
-#include "wave.h"
+#include "wave_read.h"
 
 // the rows are held bit for bit against a restatement: no a * b + c may become an fma in this file
 #pragma clang fp contract(off)
@@ -19,7 +17,6 @@ namespace {
 
 using namespace kmer;
 
-constexpr int kReadsPerBlock = 4;
 constexpr unsigned long long kAbsentKey = ~0ull; // (a key of k <= 31 has at most 62 bits)
 
 // What a wave has written to its own LDS row is read by its other lanes, and the other way round: LDS operations of one
@@ -36,18 +33,14 @@ __global__ __launch_bounds__(256) void kmer_read_influence_kernel(const unsigned
                                                                   const double *__restrict__ table, int64_t n_rows,
                                                                   int n_cols, double *__restrict__ rows)
 {
-    __shared__ unsigned long long staged[kReadsPerBlock][kWave];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x / kWave;
-    const int64_t r = (int64_t)blockIdx.x * kReadsPerBlock + wave;
-    if (r >= n_reads) // (the whole wave: a wave is a read; no workgroup barrier below)
-        return;
-    const int64_t p0 = offsets ? offsets[r] : r * fixed_len;
-    const int64_t len = offsets ? offsets[r + 1] - p0 : fixed_len;
-    const unsigned char *seq = bases + p0;
+    __shared__ unsigned long long staged[kWaveReadsPerBlock][kWave];
     const int k = t.k;
-    const int64_t n_windows = len >= k ? len - k + 1 : 0;
-    double *out = rows + r * (n_cols + 1);
+    WaveRead w;
+    if (!wave_read(bases, offsets, n_reads, fixed_len, k, w)) // (no workgroup barrier below)
+        return;
+    const int lane = w.lane;
+    const int64_t n_windows = w.n_windows;
+    double *out = rows + w.r * (n_cols + 1);
     if (n_windows > kInfluenceMaxWindows) {
         if (lane == 0) {
             for (int col = 0; col < n_cols; ++col)
@@ -57,7 +50,7 @@ __global__ __launch_bounds__(256) void kmer_read_influence_kernel(const unsigned
         return;
     }
 
-    unsigned long long *keys = staged[wave];
+    unsigned long long *keys = staged[threadIdx.x / kWave];
     const unsigned long long top = (unsigned long long)(n_rows - 1);
     const int n_chunks = (int)((n_windows + kWave - 1) / kWave);
     double partial[kInfluenceMaxCols];
@@ -68,10 +61,8 @@ __global__ __launch_bounds__(256) void kmer_read_influence_kernel(const unsigned
         const int64_t s = (int64_t)c * kWave + lane;
         const bool own = s < n_windows;
         unsigned long long h = kAbsentKey, rc = 0;
-        if (own) {
-            window_codes(seq, s, len, k, h, rc);
-            canonical_pair(h, rc, canonical);
-        }
+        if (own)
+            window_key(w.seq, s, w.len, k, canonical, h, rc);
         unsigned m = 0;
         bool earlier = false;
         for (int d = 0; d < n_chunks; ++d) { // against the 64 windows of chunk d
@@ -81,8 +72,7 @@ __global__ __launch_bounds__(256) void kmer_read_influence_kernel(const unsigned
                 other = kAbsentKey;
                 if (s2 < n_windows) {
                     unsigned long long rc2;
-                    window_codes(seq, s2, len, k, other, rc2);
-                    canonical_pair(other, rc2, canonical);
+                    window_key(w.seq, s2, w.len, k, canonical, other, rc2);
                 }
             }
             wave_lds_sync(); // (the compares of the chunk before are done)
@@ -225,17 +215,11 @@ hipError_t launch_kmer_read_influence(const unsigned char *bases, const int64_t 
                                       int canonical, const KmerTable &t, const double *table, int64_t n_rows, int n_cols,
                                       double *rows, hipStream_t stream)
 {
-    if (n_reads <= 0)
-        return hipSuccess;
-    const int64_t reads_per_launch = kmer_plan::wave_reads_per_launch(kReadsPerBlock);
-    for (int64_t first = 0; first < n_reads; first += reads_per_launch) {
-        const int64_t n = kmer_plan::reads_of_launch(first, n_reads, reads_per_launch);
-        const int64_t at = offsets ? 0 : first * fixed_len; // (with offsets the reads say where they are themselves)
-        const dim3 grid((unsigned)((n + kReadsPerBlock - 1) / kReadsPerBlock));
-        hipLaunchKernelGGL(kmer_read_influence_kernel, grid, dim3(kReadsPerBlock * kWave), 0, stream, bases + at,
-                           offsets ? offsets + first : nullptr, n, fixed_len, canonical, t, table, n_rows, n_cols,
-                           rows + first * (n_cols + 1));
-    }
+    kmer_plan::for_each_wave_launch(n_reads, fixed_len, offsets != nullptr, kWaveReadsPerBlock, [&](const kmer_plan::WaveLaunch &l) {
+        hipLaunchKernelGGL(kmer_read_influence_kernel, dim3((unsigned)l.blocks), dim3(kWaveReadsPerBlock * kWave), 0, stream,
+                           bases + l.byte_at, offsets ? offsets + l.first : nullptr, l.n, fixed_len, canonical, t, table, n_rows,
+                           n_cols, rows + l.first * (n_cols + 1));
+    });
     return hipGetLastError();
 }
 

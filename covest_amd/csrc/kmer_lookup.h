@@ -33,7 +33,7 @@ namespace covest {
 
 constexpr uint32_t kNoWindow = 0xFFFFFFFFu;
 
-// Asynchronous on `stream`; the launches are cut by kmer_plan::wave_reads_per_launch like the counter's.
+// Asynchronous on `stream`; the launches are the visits of kmer_plan::for_each_wave_launch (a wave a read: wave_read.h).
 hipError_t launch_kmer_lookup(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t fixed_len,
                               int canonical, const KmerTable &t, uint32_t cutoff, const double *weights, int n_weights,
                               uint32_t *abundance, uint32_t *summary, double *score, hipStream_t stream);

@@ -5,8 +5,7 @@
 // kmer_table.h), against the add's load, sometimes a CAS, and an atomic add to the same line.
 #include "kmer_lookup.h"
 
-#include "kmer_table.h"
-#include "wave.h"
+#include "wave_read.h"
 
 namespace covest {
 
@@ -21,24 +20,18 @@ __global__ __launch_bounds__(256) void kmer_lookup_kernel(const unsigned char *_
                                                           int n_weights, uint32_t *__restrict__ abundance,
                                                           uint32_t *__restrict__ summary, double *__restrict__ score)
 {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t r = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
-    if (r >= n_reads) // (the whole wave: a wave is a read)
-        return;
-    const int64_t p0 = offsets ? offsets[r] : r * fixed_len;
-    const int64_t len = offsets ? offsets[r + 1] - p0 : fixed_len;
-    const unsigned char *seq = bases + p0;
     const int k = t.k;
-    const int64_t n_windows = len >= k ? len - k + 1 : 0;
+    WaveRead w;
+    if (!wave_read(bases, offsets, n_reads, fixed_len, k, w))
+        return;
 
     uint32_t lowest = kNoWindow, weak = 0, first_weak = kNoWindow, last_weak_1 = 0; // (last weak window + 1; 0: none)
     double partial = 0.0;
-    for (int64_t s = lane; s < len; s += kWave) {
+    for (int64_t s = w.lane; s < w.len; s += kWave) {
         uint32_t a = kNoWindow;
-        if (s < n_windows) {
+        if (s < w.n_windows) {
             unsigned long long h, rc;
-            window_codes(seq, s, len, k, h, rc);
-            canonical_pair(h, rc, canonical);
+            window_key(w.seq, s, w.len, k, canonical, h, rc);
             const unsigned long long count = table_find(t, h, rc);
             a = count < (unsigned long long)(kNoWindow - 1) ? (uint32_t)count : kNoWindow - 1;
             lowest = a < lowest ? a : lowest;
@@ -53,7 +46,7 @@ __global__ __launch_bounds__(256) void kmer_lookup_kernel(const unsigned char *_
             }
         }
         if (abundance)
-            abundance[p0 + s] = a;
+            abundance[w.p0 + s] = a;
     }
     if (!summary && !score)
         return;
@@ -67,11 +60,11 @@ __global__ __launch_bounds__(256) void kmer_lookup_kernel(const unsigned char *_
         weak += __shfl_xor(weak, off, kWave);
         partial = partial + __shfl_xor(partial, off, kWave);
     }
-    if (lane == 0) {
+    if (w.lane == 0) {
         if (summary)
-            reinterpret_cast<uint4 *>(summary)[r] = make_uint4(lowest, weak, first_weak, last_weak_1 - 1u); // (0 - 1: none)
+            reinterpret_cast<uint4 *>(summary)[w.r] = make_uint4(lowest, weak, first_weak, last_weak_1 - 1u); // (0 - 1: none)
         if (score)
-            score[r] = partial;
+            score[w.r] = partial;
     }
 }
 
@@ -81,19 +74,12 @@ hipError_t launch_kmer_lookup(const unsigned char *bases, const int64_t *offsets
                               int canonical, const KmerTable &t, uint32_t cutoff, const double *weights, int n_weights,
                               uint32_t *abundance, uint32_t *summary, double *score, hipStream_t stream)
 {
-    if (n_reads <= 0)
-        return hipSuccess;
-    const int reads_per_block = 4;
-    const int64_t reads_per_launch = kmer_plan::wave_reads_per_launch(reads_per_block);
-    for (int64_t first = 0; first < n_reads; first += reads_per_launch) {
-        const int64_t n = kmer_plan::reads_of_launch(first, n_reads, reads_per_launch);
-        const int64_t at = offsets ? 0 : first * fixed_len; // (with offsets the reads say where they are themselves)
-        const dim3 grid((unsigned)((n + reads_per_block - 1) / reads_per_block));
-        hipLaunchKernelGGL(kmer_lookup_kernel, grid, dim3(reads_per_block * kWave), 0, stream, bases + at,
-                           offsets ? offsets + first : nullptr, n, fixed_len, canonical, t, cutoff, weights, n_weights,
-                           abundance ? abundance + at : nullptr, summary ? summary + 4 * first : nullptr,
-                           score ? score + first : nullptr);
-    }
+    kmer_plan::for_each_wave_launch(n_reads, fixed_len, offsets != nullptr, kWaveReadsPerBlock, [&](const kmer_plan::WaveLaunch &l) {
+        hipLaunchKernelGGL(kmer_lookup_kernel, dim3((unsigned)l.blocks), dim3(kWaveReadsPerBlock * kWave), 0, stream,
+                           bases + l.byte_at, offsets ? offsets + l.first : nullptr, l.n, fixed_len, canonical, t, cutoff, weights,
+                           n_weights, abundance ? abundance + l.byte_at : nullptr, summary ? summary + 4 * l.first : nullptr,
+                           score ? score + l.first : nullptr);
+    });
     return hipGetLastError();
 }
 

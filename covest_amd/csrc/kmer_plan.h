@@ -1,6 +1,7 @@
 // kmer_plan.h -- the arithmetic of the partitioned k-mer counter (kmer_host.cpp, kmer_bulk.hip) in plain C++: table
-// sizes, the tile geometry and the launch cuts the host and the kernels must agree on, the plan of a call, the sizes
-// that follow from pass 0.  No HIP in it: tests/kmer_plan_check.cpp runs it under the host compiler's sanitizers.
+// sizes, the tile geometry, the launch cuts (and the walk over the launches of a wave a read, for_each_wave_launch), the
+// plan of a call, the sizes that follow from pass 0.  No HIP in it: tests/kmer_plan_check.cpp and, for the launch cuts
+// and the walk, tests/kmer_stages_check.cpp run it under the host compiler's sanitizers.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -35,7 +36,7 @@ inline int kmer_wide_words(int k)
 
 // ---- the table paths' launches (kmer_count.hip, kmer_wide.hip): whole reads, `per` of them a launch ---------------------
 // A wave a read, reads_per_block reads a workgroup: HIP wraps a grid of more than 2^32 threads silently, so at most
-// 2^23 workgroups of 256 threads a launch.
+// 2^23 workgroups of 256 threads a launch (called by for_each_wave_launch below alone).
 inline int64_t wave_reads_per_launch(int reads_per_block)
 {
     return (int64_t)reads_per_block << 23;
@@ -51,6 +52,21 @@ inline int64_t window_reads_per_launch(int64_t n_windows)
 inline int64_t reads_of_launch(int64_t first, int64_t n_reads, int64_t per) // reads of the launch that starts at `first`
 {
     return std::min(n_reads - first, per);
+}
+
+// One launch of a wave a read (wave_read.h): what its launcher hands the kernel follows from `first` and `byte_at` alone.
+struct WaveLaunch {
+    int64_t first, n; // reads first .. first + n - 1
+    int64_t byte_at; // with offsets 0 (the reads say where they are themselves), else first * fixed_len
+    int64_t blocks;  // ceil(n / reads_per_block) workgroups, at most 2^23
+};
+template <class F> void for_each_wave_launch(int64_t n_reads, int64_t fixed_len, bool has_offsets, int reads_per_block, F &&f)
+{
+    const int64_t per = wave_reads_per_launch(reads_per_block);
+    for (int64_t first = 0; first < n_reads; first += per) {
+        const int64_t n = reads_of_launch(first, n_reads, per);
+        f(WaveLaunch{first, n, has_offsets ? 0 : first * fixed_len, (n + reads_per_block - 1) / reads_per_block});
+    }
 }
 
 // A lane a read (or a few), workgroups of 256 threads (sample_reads.hip, split_reads.hip): 2^22 workgroups, 2^30 threads,

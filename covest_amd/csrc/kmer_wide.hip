@@ -24,8 +24,7 @@
 #include <algorithm>
 
 #include "kernels.h"
-#include "kmer_table.h"
-#include "wave.h"
+#include "wave_read.h"
 
 namespace covest {
 
@@ -168,22 +167,18 @@ __global__ __launch_bounds__(256) void kmer_wide_count_kernel(const unsigned cha
                                                               int64_t fixed_len, int canonical, const KmerWideTable t,
                                                               int *overflow)
 {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t r = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
-    if (r >= n_reads)
-        return;
     const int k = t.k;
-    const int64_t p0 = offsets ? offsets[r] : r * fixed_len;
-    const int64_t len = offsets ? offsets[r + 1] - p0 : fixed_len;
-    const unsigned char *seq = bases + p0;
-    if (len < k) {
+    kmer::WaveRead w;
+    if (!kmer::wave_read(bases, offsets, n_reads, fixed_len, k, w))
+        return;
+    if (w.len < k) {
         // hash_kmer(seq[:k]) of a read shorter than k: the hash of what there is, counted once; an empty read
         // counts k-mer 0 (bin/kmer_hist.py:36-37)
-        if (lane == 0) {
+        if (w.lane == 0) {
             WideKey<W> h;
             h.clear();
-            for (int i = 0; i < (int)len; ++i)
-                h.push(base_code(seq[i]));
+            for (int i = 0; i < (int)w.len; ++i)
+                h.push(base_code(w.seq[i]));
             if (canonical) {
                 const WideKey<W> rc = wide_revcomp(h, k);
                 if (rc.less_than(h))
@@ -193,13 +188,12 @@ __global__ __launch_bounds__(256) void kmer_wide_count_kernel(const unsigned cha
         }
         return;
     }
-    const int64_t n_windows = len - k + 1;
-    for (int64_t s = lane; s < n_windows; s += kWave) {
+    for (int64_t s = w.lane; s < w.n_windows; s += kWave) {
         WideKey<W> h, rc;
         h.clear();
         rc.clear();
         for (int i = 0; i < k; ++i) {
-            const u64 c = base_code(seq[s + i]);
+            const u64 c = base_code(w.seq[s + i]);
             h.push(c);              // hash_kmer, :18-23 (rehash :26-31 yields the same window code)
             rc.set(i, 3ull - c);    // reverse complement, built back to front
         }
@@ -268,15 +262,10 @@ template <int W>
 hipError_t count_w(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t fixed_len, int canonical,
                    const KmerWideTable &t, int *overflow, hipStream_t stream)
 {
-    const int reads_per_block = 4;
-    const int64_t reads_per_launch = kmer_plan::wave_reads_per_launch(reads_per_block);
-    for (int64_t first = 0; first < n_reads; first += reads_per_launch) {
-        const int64_t n = kmer_plan::reads_of_launch(first, n_reads, reads_per_launch);
-        const dim3 grid((unsigned)((n + reads_per_block - 1) / reads_per_block));
-        hipLaunchKernelGGL((kmer_wide_count_kernel<W>), grid, dim3(reads_per_block * kWave), 0, stream,
-                           offsets ? bases : bases + first * fixed_len, offsets ? offsets + first : nullptr, n, fixed_len,
-                           canonical, t, overflow);
-    }
+    kmer_plan::for_each_wave_launch(n_reads, fixed_len, offsets != nullptr, kmer::kWaveReadsPerBlock, [&](const kmer_plan::WaveLaunch &l) {
+        hipLaunchKernelGGL((kmer_wide_count_kernel<W>), dim3((unsigned)l.blocks), dim3(kmer::kWaveReadsPerBlock * kWave), 0, stream,
+                           bases + l.byte_at, offsets ? offsets + l.first : nullptr, l.n, fixed_len, canonical, t, overflow);
+    });
     return hipGetLastError();
 }
 

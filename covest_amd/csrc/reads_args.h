@@ -1,5 +1,5 @@
-// reads_args.h -- the argument checks the entry points over packed reads that take no handle share (abi_sample.cpp,
-// abi_split.cpp; the reach check: abi_sim.cpp too), in plain C++.  No HIP in it:
+// reads_args.h -- the argument checks that entry points over packed reads share (abi_sample.cpp, abi_split.cpp; the reach
+// check: abi_sim.cpp too; the forms over a counter's table), in plain C++ (DESIGN.md sections 6ag, 6aj).  No HIP in it:
 // tests/reads_args_check.cpp runs it under the host compiler's sanitizers.  A check returns the status and the text of
 // the message; the caller passes them to `fail` (host.h fail_if).
 #pragma once
@@ -44,6 +44,22 @@ inline ArgCheck check_reads_args(const std::string &name, bool has_offsets, int6
     if (n_reads > 0 && has_offsets && !has_out_offsets)
         return arg_invalid(name, "reads of their own lengths need an array for the output offsets");
     return ArgCheck{};
+}
+
+// The device forms that walk reads against a counter's table (abi_lookup.cpp, abi_correct.cpp, abi_influence.cpp): their
+// first check, the sizes, and their last, that the table holds the keys -- one word a key (`wide`: covest_kmer::wide, the
+// words of a longer key) and not the partitioned path's result (`bulk`).  Each form keeps its own checks between the two.
+inline ArgCheck check_table_reads_sizes(const std::string &name, bool has_offsets, int64_t n_reads, int64_t read_len)
+{
+    const bool bad = n_reads < 0 || (!has_offsets && (read_len < 0 || read_len >= ((int64_t)1 << 32)));
+    return bad ? arg_invalid(name, "negative size, or no offsets and no read_len below 2^32") : ArgCheck{};
+}
+inline ArgCheck check_table_holds_keys(const std::string &name, int wide, bool bulk)
+{
+    if (wide)
+        return ArgCheck{COVEST_E_UNSUPPORTED, name + ": k must be at most 31 (keys of one word)"};
+    return bulk ? arg_invalid(name, "the counter holds a covest_kmer_count_reads_device result (its keys are not in the "
+                                    "table); covest_kmer_clear first") : ArgCheck{};
 }
 
 // Of the host form: offsets[0 .. n_reads] (or nullptr) start at no negative byte and never descend.

@@ -1,5 +1,6 @@
 // kmer_stages_check.cpp -- the integer logic of the partitioned k-mer counter's kernels that the host compiler can build
-// (covest_amd/csrc/kmer_codes.h, kmer_runs.h, and the table paths' launch cuts of kmer_plan.h),
+// (covest_amd/csrc/kmer_codes.h, kmer_runs.h, and the table paths' launch cuts and launch walk of kmer_plan.h; DESIGN.md
+// sections 6ad, 6aj),
 // compiled and run by tests/test_kmer_plan_cpu.py under -fsanitize=address,undefined.  On the device a mistake in any of
 // it shows only as a wrong histogram.
 #include <cstdint>
@@ -209,12 +210,42 @@ static void check_cut(int64_t per, const char *what)
     }
 }
 
+// 5. The walk the launchers of a wave a read make (for_each_wave_launch): the visits tile n_reads exactly once, a
+// launch's bytes begin where its reads do (0 with offsets), its workgroups hold its reads and are at most 2^23.
+static void check_wave_walk(int reads_per_block)
+{
+    const int64_t per = kmer_plan::wave_reads_per_launch(reads_per_block), fixed_len = 100;
+    const int64_t totals[] = {0, 1, reads_per_block, reads_per_block + 1, per - 1, per, per + 1, 2 * per - 1, 2 * per, 2 * per + 1,
+                              3 * per - 1, 3 * per};
+    for (const int64_t n_reads : totals)
+        for (const bool has_offsets : {false, true}) {
+            int64_t next = 0;
+            int launches = 0;
+            kmer_plan::for_each_wave_launch(n_reads, fixed_len, has_offsets, reads_per_block, [&](const kmer_plan::WaveLaunch &l) {
+                CHECK(l.first == next && l.n >= 1, "walk(%d) n_reads %lld offsets %d: first %lld, %lld reads", reads_per_block,
+                      (long long)n_reads, (int)has_offsets, (long long)l.first, (long long)l.n);
+                CHECK(l.byte_at == (has_offsets ? 0 : l.first * fixed_len), "walk(%d) n_reads %lld offsets %d first %lld: byte_at %lld",
+                      reads_per_block, (long long)n_reads, (int)has_offsets, (long long)l.first, (long long)l.byte_at);
+                CHECK(l.blocks * reads_per_block >= l.n && l.blocks * reads_per_block < l.n + reads_per_block &&
+                          l.blocks <= (int64_t)1 << 23,
+                      "walk(%d) n_reads %lld first %lld: %lld workgroups for %lld reads", reads_per_block, (long long)n_reads,
+                      (long long)l.first, (long long)l.blocks, (long long)l.n);
+                next = l.first + l.n;
+                ++launches;
+            });
+            CHECK(next == n_reads && launches == (n_reads + per - 1) / per && launches <= 3,
+                  "walk(%d) n_reads %lld offsets %d: %d launches end at %lld", reads_per_block, (long long)n_reads, (int)has_offsets,
+                  launches, (long long)next);
+        }
+}
+
 static void check_cuts()
 {
     for (const int reads_per_block : {1, 4}) {
         const int64_t per = kmer_plan::wave_reads_per_launch(reads_per_block);
         CHECK(per / reads_per_block == (int64_t)1 << 23, "wave_reads_per_launch(%d): workgroups", reads_per_block); // threads < 2^32
         check_cut(per, "a wave a read");
+        check_wave_walk(reads_per_block);
     }
     for (const int64_t n_windows : {(int64_t)1, (int64_t)70, (int64_t)80, (int64_t)4096, ((int64_t)1 << 31) - 256, (int64_t)1 << 31}) {
         const int64_t per = kmer_plan::window_reads_per_launch(n_windows);

@@ -95,11 +95,39 @@ static void check_offsets()
     INVALID(check_ascending_offsets("who", bad.data(), 1), "offsets descend at read 0");
 }
 
+// The device forms over a counter's table: the sizes at 0 and either side of 2^32, and what the table must hold -- the
+// wide keys win over the partitioned result, as they did in each form.
+static void check_table_forms()
+{
+    static const char *kSizes = "negative size, or no offsets and no read_len below 2^32";
+    static const char *kWide = "who: k must be at most 31 (keys of one word)";
+    static const char *kBulk = "the counter holds a covest_kmer_count_reads_device result (its keys are not in the table); "
+                               "covest_kmer_clear first";
+    const int64_t two32 = (int64_t)1 << 32;
+    OK(check_table_reads_sizes("who", false, 0, 0));
+    OK(check_table_reads_sizes("who", false, kMax, two32 - 1));
+    OK(check_table_reads_sizes("who", true, 0, -1));      // read_len is not looked at beside offsets
+    OK(check_table_reads_sizes("who", true, kMax, two32));
+    OK(check_table_reads_sizes("who", true, 5, kMax));
+    INVALID(check_table_reads_sizes("who", false, 0, two32), kSizes);
+    INVALID(check_table_reads_sizes("who", false, 5, kMax), kSizes);
+    INVALID(check_table_reads_sizes("who", false, 0, -1), kSizes);
+    INVALID(check_table_reads_sizes("who", false, -1, 0), kSizes);
+    INVALID(check_table_reads_sizes("who", true, -1, 0), kSizes);  // no reads below none, with offsets too
+    OK(check_table_holds_keys("who", 0, false));
+    INVALID(check_table_holds_keys("who", 0, true), kBulk);
+    for (const int wide : {2, 4, 8}) {
+        expect(check_table_holds_keys("who", wide, false), COVEST_E_UNSUPPORTED, kWide, __LINE__);
+        expect(check_table_holds_keys("who", wide, true), COVEST_E_UNSUPPORTED, kWide, __LINE__);
+    }
+}
+
 int main()
 {
     check_reach();
     check_args();
     check_offsets();
+    check_table_forms();
     // a name is taken as it comes
     expect(check_reads_reach("covest_sample_reads_device", kMax, 1, 0), COVEST_E_INVALID,
            "covest_sample_reads_device: more reads than 64-bit offsets reach", __LINE__);

@@ -5,7 +5,8 @@ that follow from pass 0, the tables' sizes against the comparison in double they
 the totals around each multiple of a launch: at small sizes a mistake there loses or double-counts windows silently.
 tests/kmer_stages_check.cpp, over kmer_codes.h and kmer_runs.h, checks what the kernels compute in integers: the length of
 a run from the waves' masks against a walk over the tile's 256 threads, the pieces of a run, the pair reversals against
-the base-by-base loops, the LDS tables' slot, and the table paths' launch cuts."""
+the base-by-base loops, the LDS tables' slot, the table paths' launch cuts, and the walk over the launches of a wave a read
+(for_each_wave_launch: first read, first byte and workgroups of every launch)."""
 import os
 import shutil
 import subprocess
