@@ -31,3 +31,7 @@ from .read_errors import correct_reads, ReadCorrections  # noqa: F401,E402
 from . import influence  # noqa: F401,E402
 from .influence import (score_rows, read_influence, summarize_influence, rows_moments, rows_moments_device,  # noqa: F401,E402
                         ReadInfluence)
+# (covest_amd.read_bootstrap is the FUNCTION, as covest_amd.read_jackknife is; the module of the same name is reached by
+# `from covest_amd.read_bootstrap import ...`)
+from .read_bootstrap import (bootstrap_weights, bootstrap_weights_device, bootstrap_histograms,  # noqa: F401,E402
+                             summarize_read_bootstrap, read_bootstrap)

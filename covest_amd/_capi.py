@@ -31,7 +31,7 @@ EXPORTS = (
     "covest_grid_work", "covest_grid_profile", "covest_grid_kernel_ms", "covest_grid_diag",
     "covest_grid_launch_record", "covest_model_launch_record", "covest_compiled_variants",
     "covest_kmer_create", "covest_kmer_destroy", "covest_kmer_reserve", "covest_kmer_add",
-    "covest_kmer_add_device", "covest_kmer_histogram", "covest_kmer_slots", "covest_kmer_clear",
+    "covest_kmer_add_device", "covest_kmer_add_weighted", "covest_kmer_add_weighted_device", "covest_kmer_histogram", "covest_kmer_slots", "covest_kmer_clear",
     "covest_kmer_count_reads_device", "covest_kmer_partition_info", "covest_kmer_partition_ms", "covest_kmer_memory_limit",
     "covest_kmer_scatter_rate", "covest_kmer_lookup_reads", "covest_kmer_lookup_reads_device",
     "covest_kmer_correct_reads", "covest_kmer_correct_reads_device",
@@ -42,6 +42,7 @@ EXPORTS = (
     "covest_random_genome", "covest_random_genome_device", "covest_simulate_reads", "covest_simulate_reads_device",
     "covest_sample_reads", "covest_sample_reads_device",
     "covest_split_reads", "covest_split_reads_device",
+    "covest_bootstrap_weights", "covest_bootstrap_weights_device",
     "covest_repeat_plan", "covest_repeat_genome", "covest_repeat_genome_device",
     "covest_draw_thresholds", "covest_draw_histograms", "covest_draw_histograms_device",
     "covest_batch_create", "covest_batch_draw", "covest_batch_counts", "covest_batch_eval_cross", "covest_batch_eval_pairs",
@@ -195,6 +196,10 @@ def lib():
     L.covest_kmer_add.argtypes = [vp, u8p, i64p, i64]
     L.covest_kmer_add_device.restype = ctypes.c_int
     L.covest_kmer_add_device.argtypes = [vp, vp, vp, i64, i64, vp]
+    L.covest_kmer_add_weighted.restype = ctypes.c_int
+    L.covest_kmer_add_weighted.argtypes = [vp, vp, vp, i64, vp]
+    L.covest_kmer_add_weighted_device.restype = ctypes.c_int
+    L.covest_kmer_add_weighted_device.argtypes = [vp, vp, vp, i64, i64, vp, vp]
     L.covest_kmer_count_reads_device.restype = ctypes.c_int
     L.covest_kmer_count_reads_device.argtypes = [vp, vp, vp, i64, i64, i64, vp]
     L.covest_kmer_partition_info.restype = ctypes.c_int
@@ -261,6 +266,10 @@ def lib():
     L.covest_split_reads.argtypes = [i32, vp, vp, i64, i64, i64, i32, u64, vp, vp, vp, vp]
     L.covest_split_reads_device.restype = ctypes.c_int
     L.covest_split_reads_device.argtypes = [i32, vp, vp, i64, i64, i64, i32, u64, vp, vp, vp, vp, vp]
+    L.covest_bootstrap_weights.restype = ctypes.c_int
+    L.covest_bootstrap_weights.argtypes = [i32, i64, i64, u64, ctypes.c_uint32, vp]
+    L.covest_bootstrap_weights_device.restype = ctypes.c_int
+    L.covest_bootstrap_weights_device.argtypes = [i32, i64, i64, u64, ctypes.c_uint32, vp, vp]
     L.covest_repeat_plan.restype = ctypes.c_int
     L.covest_repeat_plan.argtypes = [i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, u64, i32, vp, i64p]
     L.covest_repeat_genome.restype = ctypes.c_int

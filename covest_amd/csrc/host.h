@@ -11,6 +11,7 @@
 //   abi_sim.cpp       covest_random_genome*, covest_simulate_reads*
 //   abi_repeat.cpp    covest_repeat_plan, covest_repeat_genome*
 //   abi_draw.cpp      covest_draw_thresholds, covest_draw_histograms*
+//   abi_bootstrap.cpp covest_bootstrap_weights*
 //   abi_batch.cpp     covest_batch_*
 //   abi_posterior.cpp covest_posterior_classes
 // ).  Nothing here is part of the C ABI (include/covest_amd.h).
@@ -375,7 +376,7 @@ struct covest_kmer {
     int wide = 0;          // 0: k <= 31, `table`; else the words per key of `wtable` (kmer_wide.hip)
     KmerWideTable wtable{};
     KmerTable table{};
-    DevBuf slots, flag, stats, hist, ws_bases, ws_offsets;
+    DevBuf slots, flag, stats, hist, ws_bases, ws_offsets, ws_weights; // (ws_weights: covest_kmer_add_weighted's)
     bool bulk = false; // the counter holds the result of covest_kmer_count_reads_device (until covest_kmer_clear)
     BulkState part;
     std::mutex lock;

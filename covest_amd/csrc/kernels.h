@@ -215,10 +215,11 @@ struct KmerTable {
     int k; // bases per key (a key's first slot is a function of its minimizer: kmer_count.hip)
 };
 hipError_t launch_kmer_fill_empty(const KmerTable &t, hipStream_t stream);
-// bases: ASCII acgt/ACGT; offsets[n_reads + 1] or nullptr with every read `fixed_len` long.
+// bases: ASCII acgt/ACGT; offsets[n_reads + 1] or nullptr with every read `fixed_len` long.  weights (device, a uint32
+// a read) or nullptr: every occurrence of read r is added weights[r] times, and a read of weight 0 adds nothing.
 hipError_t launch_kmer_count(const unsigned char *bases, const int64_t *offsets, int64_t n_reads,
                              int64_t fixed_len, int k, int canonical, const KmerTable &t, int *overflow,
-                             hipStream_t stream);
+                             hipStream_t stream, const uint32_t *weights = nullptr);
 hipError_t launch_kmer_rehash(const KmerTable &src, const KmerTable &dst, int *overflow, hipStream_t stream);
 hipError_t launch_kmer_stats(const KmerTable &t, unsigned long long *stats, hipStream_t stream);
 hipError_t launch_kmer_histogram(const KmerTable &t, unsigned long long *hist, unsigned long long hist_len,
@@ -304,7 +305,8 @@ struct KmerWideTable {
 };
 hipError_t launch_kmer_wide_clear(const KmerWideTable &t, hipStream_t stream);
 hipError_t launch_kmer_wide_count(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t fixed_len,
-                                  int canonical, const KmerWideTable &t, int *overflow, hipStream_t stream);
+                                  int canonical, const KmerWideTable &t, int *overflow, hipStream_t stream,
+                                  const uint32_t *weights = nullptr); // (weights: as launch_kmer_count's)
 hipError_t launch_kmer_wide_rehash(const KmerWideTable &src, const KmerWideTable &dst, int *overflow, hipStream_t stream);
 hipError_t launch_kmer_wide_stats(const KmerWideTable &t, unsigned long long *stats, hipStream_t stream);
 hipError_t launch_kmer_wide_histogram(const KmerWideTable &t, unsigned long long *hist, unsigned long long hist_len,

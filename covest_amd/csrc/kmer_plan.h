@@ -69,6 +69,19 @@ template <class F> void for_each_wave_launch(int64_t n_reads, int64_t fixed_len,
     }
 }
 
+// A weighted add (covest_kmer_add_weighted*) has a weight a READ, indexed like the call's reads: the entry a launch's
+// kernel starts from.  A wave-a-read launch indexes its reads from l.first on -- whatever byte_at says: with offsets the
+// bytes do not advance, the reads still do --, the windows-numbered-through loop from its own `first`.
+inline int64_t weights_at(const WaveLaunch &l)
+{
+    return l.first;
+}
+
+inline int64_t window_weights_at(int64_t first) // `first`: the read a launch of the windows numbered through starts at
+{
+    return first;
+}
+
 // A lane a read (or a few), workgroups of 256 threads (sample_reads.hip, split_reads.hip): 2^22 workgroups, 2^30 threads,
 // a launch, for the same wrap.
 inline int64_t lane_blocks_per_launch()

@@ -160,17 +160,24 @@ __device__ __forceinline__ void wide_add(const KmerWideTable t, const WideKey<W>
     *overflow = 1;
 }
 
-// One wave per read, lane = window start (then + 64, ...): compute_counts, bin/kmer_hist.py:34-41.
-template <int W>
-__global__ __launch_bounds__(256) void kmer_wide_count_kernel(const unsigned char *__restrict__ bases,
-                                                              const int64_t *__restrict__ offsets, int64_t n_reads,
-                                                              int64_t fixed_len, int canonical, const KmerWideTable t,
-                                                              int *overflow)
+// One wave per read, lane = window start (then + 64, ...): compute_counts, bin/kmer_hist.py:34-41.  kWeighted: every
+// occurrence is added weights[read] times in its one atomic add; a wave whose read has weight 0 leaves before it
+// touches the bases.  The unweighted instantiation is the kernel as it was.
+template <int W, bool kWeighted>
+__device__ __forceinline__ void wide_count_read(const unsigned char *__restrict__ bases, const int64_t *__restrict__ offsets,
+                                                int64_t n_reads, int64_t fixed_len, int canonical, const KmerWideTable t,
+                                                int *overflow, const uint32_t *__restrict__ weights)
 {
     const int k = t.k;
     kmer::WaveRead w;
     if (!kmer::wave_read(bases, offsets, n_reads, fixed_len, k, w))
         return;
+    u64 add = 1ull;
+    if (kWeighted) {
+        add = weights[w.r];
+        if (add == 0)
+            return;
+    }
     if (w.len < k) {
         // hash_kmer(seq[:k]) of a read shorter than k: the hash of what there is, counted once; an empty read
         // counts k-mer 0 (bin/kmer_hist.py:36-37)
@@ -184,7 +191,7 @@ __global__ __launch_bounds__(256) void kmer_wide_count_kernel(const unsigned cha
                 if (rc.less_than(h))
                     h = rc;
             }
-            wide_add(t, h, 1ull, overflow);
+            wide_add(t, h, add, overflow);
         }
         return;
     }
@@ -200,8 +207,27 @@ __global__ __launch_bounds__(256) void kmer_wide_count_kernel(const unsigned cha
         h.mask_to(k);
         if (canonical && rc.less_than(h))
             h = rc;
-        wide_add(t, h, 1ull, overflow);
+        wide_add(t, h, add, overflow);
     }
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void kmer_wide_count_kernel(const unsigned char *__restrict__ bases,
+                                                              const int64_t *__restrict__ offsets, int64_t n_reads,
+                                                              int64_t fixed_len, int canonical, const KmerWideTable t,
+                                                              int *overflow)
+{
+    wide_count_read<W, false>(bases, offsets, n_reads, fixed_len, canonical, t, overflow, nullptr);
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void kmer_wide_count_weighted_kernel(const unsigned char *__restrict__ bases,
+                                                                       const int64_t *__restrict__ offsets, int64_t n_reads,
+                                                                       int64_t fixed_len, int canonical,
+                                                                       const KmerWideTable t, int *overflow,
+                                                                       const uint32_t *__restrict__ weights)
+{
+    wide_count_read<W, true>(bases, offsets, n_reads, fixed_len, canonical, t, overflow, weights);
 }
 
 template <int W>
@@ -260,11 +286,17 @@ __global__ __launch_bounds__(256) void kmer_wide_histogram_kernel(const KmerWide
 
 template <int W>
 hipError_t count_w(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t fixed_len, int canonical,
-                   const KmerWideTable &t, int *overflow, hipStream_t stream)
+                   const KmerWideTable &t, int *overflow, hipStream_t stream, const uint32_t *weights)
 {
     kmer_plan::for_each_wave_launch(n_reads, fixed_len, offsets != nullptr, kmer::kWaveReadsPerBlock, [&](const kmer_plan::WaveLaunch &l) {
-        hipLaunchKernelGGL((kmer_wide_count_kernel<W>), dim3((unsigned)l.blocks), dim3(kmer::kWaveReadsPerBlock * kWave), 0, stream,
-                           bases + l.byte_at, offsets ? offsets + l.first : nullptr, l.n, fixed_len, canonical, t, overflow);
+        const dim3 grid((unsigned)l.blocks), block(kmer::kWaveReadsPerBlock * kWave);
+        const int64_t *offs = offsets ? offsets + l.first : nullptr;
+        if (weights) // a weight a read: it goes with the launch's first read (kmer_plan.h weights_at)
+            hipLaunchKernelGGL((kmer_wide_count_weighted_kernel<W>), grid, block, 0, stream, bases + l.byte_at, offs, l.n,
+                               fixed_len, canonical, t, overflow, weights + kmer_plan::weights_at(l));
+        else
+            hipLaunchKernelGGL((kmer_wide_count_kernel<W>), grid, block, 0, stream, bases + l.byte_at, offs, l.n, fixed_len,
+                               canonical, t, overflow);
     });
     return hipGetLastError();
 }
@@ -279,16 +311,17 @@ hipError_t launch_kmer_wide_clear(const KmerWideTable &t, hipStream_t stream)
 }
 
 hipError_t launch_kmer_wide_count(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t fixed_len,
-                                  int canonical, const KmerWideTable &t, int *overflow, hipStream_t stream)
+                                  int canonical, const KmerWideTable &t, int *overflow, hipStream_t stream,
+                                  const uint32_t *weights)
 {
     if (n_reads <= 0)
         return hipSuccess;
     if (t.w == 2)
-        return count_w<2>(bases, offsets, n_reads, fixed_len, canonical, t, overflow, stream);
+        return count_w<2>(bases, offsets, n_reads, fixed_len, canonical, t, overflow, stream, weights);
     if (t.w == 4)
-        return count_w<4>(bases, offsets, n_reads, fixed_len, canonical, t, overflow, stream);
+        return count_w<4>(bases, offsets, n_reads, fixed_len, canonical, t, overflow, stream, weights);
     if (t.w == 8)
-        return count_w<8>(bases, offsets, n_reads, fixed_len, canonical, t, overflow, stream);
+        return count_w<8>(bases, offsets, n_reads, fixed_len, canonical, t, overflow, stream, weights);
     return hipErrorInvalidValue;
 }
 

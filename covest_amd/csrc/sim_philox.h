@@ -58,15 +58,42 @@ COVEST_HD uint32_t mod3(uint32_t w)
 //   divergence  genome base i>>2  0                             one a base: substituted()
 //   draw        draw d >> 1       replicate b                   (w0 | w1 << 32) >> 1 an even d, (w2 | w3 << 32) >> 1 an odd
 //   group       read r            0                             (w0 * G) >> 32: the read's group of G (split_reads.hip)
-// A new generator takes the next free number (and a row here and in the header); c2 is free in all but `read` and `draw`.
+//   bootstrap   read r            replicate b                   w0 against kPoisson1Cdf: the read's multiplicity
+// A new generator takes the next free number (and a row here and in the header); c2 is free in all but `read`, `draw` and
+// `bootstrap`.
 constexpr uint32_t kStreamRead = 0, kStreamGenome = 1, kStreamKeep = 2, kStreamFamily = 3, kStreamCopies = 4,
-                   kStreamShuffle = 5, kStreamDivergence = 6, kStreamDraw = 7, kStreamGroup = 8;
+                   kStreamShuffle = 5, kStreamDivergence = 6, kStreamDraw = 7, kStreamGroup = 8, kStreamBootstrap = 9;
 
 struct PhiloxKey { uint32_t k0, k1; };
 COVEST_HD PhiloxKey philox_key(uint64_t seed) { return PhiloxKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
 COVEST_HD void philox_block(uint64_t index, uint32_t c2, uint32_t stream, PhiloxKey key, uint32_t out[4])
 {
     philox4x32_10((uint32_t)index, (uint32_t)(index >> 32), c2, stream, key.k0, key.k1, out);
+}
+
+// THE READ BOOTSTRAP'S MULTIPLICITY (bootstrap_weights.hip): Poisson(1) by inversion on one word,
+// m = #{i : w >= T_i}, T_i = floor(2^32 P(Poisson(1) <= i)), i = 0 .. 12.  The mass beyond 12 is 0.27 * 2^-32: the table is
+// complete at 32 bits, and the largest m is 13.  The compares are a fixed thirteen: no lane takes a branch of its own.
+constexpr int kPoisson1Steps = 13;
+COVEST_HD uint32_t poisson1_multiplicity(uint32_t w)
+{
+    constexpr uint32_t kPoisson1Cdf[kPoisson1Steps] = {1580030168u, 3160060337u, 3950075421u, 4213413783u, 4279248373u,
+                                                       4292415291u, 4294609777u, 4294923276u, 4294962463u, 4294966817u,
+                                                       4294967252u, 4294967292u, 4294967295u};
+    uint32_t m = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < kPoisson1Steps; ++i)
+        m += w >= kPoisson1Cdf[i] ? 1u : 0u;
+    return m;
+}
+// the multiplicity of read r in replicate b under `key`
+COVEST_HD uint32_t bootstrap_weight(uint64_t r, uint32_t b, PhiloxKey key)
+{
+    uint32_t w[4];
+    philox_block(r, b, kStreamBootstrap, key, w);
+    return poisson1_multiplicity(w[0]);
 }
 
 // THE BASE CODE.  A, C, G, T = 0, 1, 2, 3, the complement of c is 3 - c.  ASCII a/c/g/t in either case: (byte >> 1) & 3

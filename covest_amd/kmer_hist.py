@@ -117,6 +117,19 @@ def _packed_reads(reads):
     return blob, offsets
 
 
+def _read_weights(weights, n_reads):
+    """The uint32 array of KmerCounts.add_weighted: one weight a read, whole numbers in 0 .. 2^32 - 1; ValueError before
+    the library is asked."""
+    w = np.asarray(weights)
+    if w.ndim != 1 or w.size != n_reads:
+        raise ValueError("weights must be a one-dimensional array of one entry per read")
+    if w.size and w.dtype.kind not in "iu":
+        raise ValueError("weights must be integers")
+    if w.size and (int(w.min()) < 0 or int(w.max()) > 0xFFFFFFFF):
+        raise ValueError("weights must be within 0 .. 2^32 - 1")
+    return np.ascontiguousarray(w, dtype=np.uint32)
+
+
 MAX_INFLUENCE_COLUMNS = 8      # csrc/kmer_influence.h kInfluenceMaxCols
 MAX_INFLUENCE_WINDOWS = 4096   # ... kInfluenceMaxWindows
 
@@ -277,6 +290,38 @@ class KmerCounts:
         _capi.check(_capi.lib().covest_kmer_add_device(
             self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0),
             int(n_reads), int(read_len), ctypes.c_void_p(stream or 0)), "covest_kmer_add_device")
+        return self
+
+    def add_weighted(self, reads, weights):
+        """Count the k-mers of `reads` -- what lookup takes: a list of preprocessed strings, a pair (bases, offsets), an
+        (n, L) uint8 array -- with every occurrence of read r added weights[r] times (covest_kmer_add_weighted): a weight
+        of 0 adds nothing and creates no key, all weights 1 is add_reads.  `weights`: n integers in 0 .. 2^32 - 1.  The
+        table is sized as for the unweighted add: weights never add distinct keys."""
+        blob, offsets = _packed_reads(reads)
+        n = offsets.size - 1
+        weights = _read_weights(weights, n)
+        if not n:
+            return self
+        self._reserve_for(int(np.maximum(np.diff(offsets) - self.k + 1, 1).sum()))
+        _capi.check(_capi.lib().covest_kmer_add_weighted(
+            self._handle, ctypes.c_void_p(blob.ctypes.data), ctypes.c_void_p(offsets.ctypes.data), n,
+            ctypes.c_void_p(weights.ctypes.data)), "covest_kmer_add_weighted")
+        return self
+
+    def add_weighted_device(self, d_bases_ptr, n_reads, read_len, d_weights_ptr, d_offsets_ptr=None, stream=None,
+                            reserve=True):
+        """add_device with a weight per read resident in HBM (`d_weights_ptr`: n_reads uint32, aligned to 4 bytes;
+        covest_kmer_add_weighted_device): asynchronous on `stream`, where the weights are read -- a
+        bootstrap_weights_device on the same stream needs no synchronisation before it.  `reserve` as add_device's."""
+        n_new = int(n_reads) * max(int(read_len) - self.k + 1, 1)
+        if reserve:
+            self._reserve_for(n_new)
+        else:
+            self._added += n_new
+        _capi.require_shared_runtime("KmerCounts.add_weighted_device")
+        _capi.check(_capi.lib().covest_kmer_add_weighted_device(
+            self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0), int(n_reads), int(read_len),
+            ctypes.c_void_p(d_weights_ptr or 0), ctypes.c_void_p(stream or 0)), "covest_kmer_add_weighted_device")
         return self
 
     def count_reads_device(self, d_bases_ptr, n_reads, read_len, d_offsets_ptr=None, n_bases=None, stream=None):

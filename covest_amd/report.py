@@ -27,7 +27,7 @@ def _finite_int(x):
 def print_output(hist_orig, model, success, sample_factor, estimated=None, guess=None, orig=None,
                  reads_size=None, silent=False, orig_sample_factor=1, starting_points=1,
                  use_grid_search=False, intervals=None, information=None, bootstrap=None, jackknife=None,
-                 posterior=None, read_errors=None, corrections=None, read_influence=None):
+                 posterior=None, read_errors=None, corrections=None, read_influence=None, read_bootstrap=None):
     """`intervals`: the dict covest_amd.profile.coverage_interval returns; the record then carries the likelihood-ratio
     interval of the coverage, of the genome size and its level.  Without it the record is the reference's, key for key.
     `information`: the dict covest_amd.information.observed_information returns (a key 'level' in it chooses the Wald
@@ -67,7 +67,13 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
     free parameter and for genome_size, read_influence_se_<name> and read_influence_interval_<name>: the linearised
     delete-ONE-read jackknife, the genome held fixed, first order in the inverse information.  Where it
     has no covariance to start from the record carries read_influence_reason instead.  Without it the record is
-    unchanged."""
+    unchanged.
+    `read_bootstrap`: the dict covest_amd.read_bootstrap.read_bootstrap returns (sample factor 1 by its own rule, so
+    nothing is scaled); the record then carries read_bootstrap_replicates, read_bootstrap_used, read_bootstrap_failed,
+    read_bootstrap_level and, per free parameter and for genome_size, read_bootstrap_se_<name>,
+    read_bootstrap_bias_<name> and read_bootstrap_interval_<name> (the percentile interval): the Poisson bootstrap over
+    READS, the genome held fixed -- measured to be biased by the duplicated reads, the jackknife's fields are the ones
+    to rely on.  Without it the record is unchanged."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -204,6 +210,19 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
             interval = summary['intervals'].get(name)
             if interval is not None:
                 record['read_influence_interval_%s' % name] = [float(v) for v in interval]
+    if read_bootstrap is not None:
+        record['read_bootstrap_replicates'] = int(read_bootstrap['replicates'])
+        record['read_bootstrap_used'] = int(read_bootstrap['used'])
+        record['read_bootstrap_failed'] = int(read_bootstrap['failed'])
+        record['read_bootstrap_level'] = float(read_bootstrap['level'])
+        for name in list(model.params) + ['genome_size']:
+            for key, source in (('se', 'standard_errors'), ('bias', 'bias')):
+                value = read_bootstrap[source].get(name)
+                if value is not None:
+                    record['read_bootstrap_%s_%s' % (key, name)] = float(value)
+            interval = read_bootstrap['intervals'].get(name)
+            if interval is not None:
+                record['read_bootstrap_interval_%s' % name] = [float(v) for v in interval]
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

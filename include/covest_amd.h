@@ -361,6 +361,19 @@ int covest_kmer_add(covest_kmer *c, const uint8_t *bases, const int64_t *offsets
  * read_len bases long. */
 int covest_kmer_add_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets,
                            int64_t n_reads, int64_t read_len, void *stream);
+/* The same with a WEIGHT PER READ (uint32, weights[n_reads], aligned to 4 bytes): every k-mer
+ * occurrence of read r is added weights[r] times, in one atomic add.  A read of weight 0 adds nothing and creates no
+ * key; a read shorter than k adds its one key weights[r] times.  All weights 1 is covest_kmer_add*.  Everything else --
+ * the table, every key width (k = 1 .. 255), the overflow flag and its contract, the reserve rule (weights never add
+ * DISTINCT keys: the caller sizes the table as for the unweighted add), the refusal on a counter that holds a
+ * covest_kmer_count_reads_device result -- is covest_kmer_add_device's and covest_kmer_add's.  The _device form is
+ * asynchronous on `stream` and reads d_weights there: weights written on the same stream (covest_bootstrap_weights_device)
+ * need no synchronisation in between.  COVEST_E_INVALID also for NULL weights with n_reads > 0 and for a weights
+ * pointer that is not aligned to 4 bytes.  The partitioned path takes no weights. */
+int covest_kmer_add_weighted_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                                    int64_t read_len, const uint32_t *d_weights, void *stream);
+int covest_kmer_add_weighted(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
+                             const uint32_t *weights);
 /* compute_histogram(counts) (bin/kmer_hist.py:57-64): out[i] = number of distinct k-mers seen i
  * times, i = 0 .. max count.  Call with out == NULL to learn needed_len (= max count + 1) and the
  * number of distinct k-mers; fails with COVEST_E_NOMEM-like status if the table overflowed. */
@@ -649,6 +662,28 @@ int covest_split_reads(int32_t device, const uint8_t *bases, const int64_t *offs
                        int64_t read_len, int64_t first_read, int32_t groups, uint64_t seed,
                        uint8_t *out_bases, int64_t *out_offsets, int64_t *read_index, int64_t *group_first);
 
+/* ---- read bootstrap: how often each read is drawn in a replicate ----
+ * The bootstrap over reads resamples whole reads with replacement.  Here it is the POISSON bootstrap: the multiplicity
+ * of every read is Poisson(1), drawn on its own, so a replicate holds n reads on average (relative spread 1 / sqrt(n))
+ * rather than exactly n, and the multiplicity is a function of (seed, replicate, read index) alone:
+ *   read r = index within the call + first_read (64-bit); replicate b (uint32);
+ *   w = word 0 of Philox4x32-10 (as above; key = seed's low and high word) on the counter (lo32(r), hi32(r), b, 9)
+ *   (stream 9, `bootstrap`: the next row of the table of streams below);
+ *   m(r, b) = #{ i in 0 .. 12 : w >= T_i },  T_i = floor(2^32 P(Poisson(1) <= i)):
+ *   T = 1580030168, 3160060337, 3950075421, 4213413783, 4279248373, 4292415291, 4294609777, 4294923276, 4294962463,
+ *       4294966817, 4294967252, 4294967292, 4294967295.
+ * The largest m is 13; the mass beyond 12 is 0.27 * 2^-32, so the table is complete at 32 bits.  Rows [a, a + m) drawn
+ * with first_read = a equal the same rows of the whole run.  out[n_reads] (uint32, aligned to 4 bytes) is what
+ * covest_kmer_add_weighted* takes for its weights; nothing is written outside out[0 .. n_reads).
+ * COVEST_E_INVALID: n_reads < 0 or first_read < 0, first_read + n_reads beyond 64-bit reach, a NULL or misaligned out
+ * with n_reads > 0.  n_reads == 0: COVEST_OK, nothing launched.  device < 0 = the calling thread's current device.
+ * The _device form takes a DEVICE buffer and is asynchronous on `stream`; the other takes a HOST buffer, copies and
+ * waits (COVEST_E_NOMEM where its device buffer does not fit). */
+int covest_bootstrap_weights_device(int32_t device, int64_t n_reads, int64_t first_read, uint64_t seed, uint32_t replicate,
+                                    uint32_t *d_out, void *stream);
+int covest_bootstrap_weights(int32_t device, int64_t n_reads, int64_t first_read, uint64_t seed, uint32_t replicate,
+                             uint32_t *out);
+
 /* ---- replicate histograms drawn from a weight vector: the parametric bootstrap's generator ----
  * INPUT: m >= 1 weights w_0 .. w_{m-1} (doubles, finite, >= 0, sum > 0) and a number of draws n >= 0.  A call covers
  * the replicates first_rep .. first_rep + n_rep - 1, every replicate index < 2^32, under a 64-bit seed.
@@ -662,8 +697,8 @@ int covest_split_reads(int32_t device, const uint8_t *bases, const int64_t *offs
  *   cell after it, is never reached from above; a cell of weight 0 (t_i == t_{i-1}) never counts.
  * The streams of the generators, by the counter's last word (the key is always the seed's two words):
  *   0 read (c2: 0 the header, 1 + j the bases 4j .. 4j + 3)   1 genome   2 keep (the sampler)   3 family   4 copies
- *   5 shuffle   6 divergence   7 draw (c2: the replicate)   8 group (covest_split_reads) -- c2 is 0 in all but `read`
- *   and `draw`.
+ *   5 shuffle   6 divergence   7 draw (c2: the replicate)   8 group (covest_split_reads)
+ *   9 bootstrap (c2: the replicate; covest_bootstrap_weights) -- c2 is 0 in all but `read`, `draw` and `bootstrap`.
  * OUTPUT: counts[b - first_rep][i] (int64, row-major n_rep x m) = the number of draws d < n of replicate b in cell i.
  * The call OVERWRITES the output: the caller does not zero it.  A run of replicates [a, a + k) equals the same rows
  * of a larger run, and the row for n equals the row for n' > n restricted to its first n draws.  All arithmetic on the
