@@ -35,3 +35,5 @@ from .influence import (score_rows, read_influence, summarize_influence, rows_mo
 # `from covest_amd.read_bootstrap import ...`)
 from .read_bootstrap import (bootstrap_weights, bootstrap_weights_device, bootstrap_histograms,  # noqa: F401,E402
                              summarize_read_bootstrap, read_bootstrap)
+from . import dedup  # noqa: F401,E402
+from .dedup import dedup_reads, dedup_reads_device, DedupReads  # noqa: F401,E402

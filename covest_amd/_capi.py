@@ -42,6 +42,7 @@ EXPORTS = (
     "covest_random_genome", "covest_random_genome_device", "covest_simulate_reads", "covest_simulate_reads_device",
     "covest_sample_reads", "covest_sample_reads_device",
     "covest_split_reads", "covest_split_reads_device",
+    "covest_dedup_reads", "covest_dedup_reads_device",
     "covest_bootstrap_weights", "covest_bootstrap_weights_device",
     "covest_repeat_plan", "covest_repeat_genome", "covest_repeat_genome_device",
     "covest_draw_thresholds", "covest_draw_histograms", "covest_draw_histograms_device",
@@ -262,6 +263,10 @@ def lib():
     L.covest_sample_reads.argtypes = [i32, vp, vp, i64, i64, i64, ctypes.c_double, u64, vp, vp, vp, i64p, i64p]
     L.covest_sample_reads_device.restype = ctypes.c_int
     L.covest_sample_reads_device.argtypes = [i32, vp, vp, i64, i64, i64, ctypes.c_double, u64, vp, vp, vp, vp, vp]
+    L.covest_dedup_reads.restype = ctypes.c_int
+    L.covest_dedup_reads.argtypes = [i32, vp, vp, i64, i64, i64, i32, i32, u64, vp, vp, vp, vp, i64p, i64p, i64p]
+    L.covest_dedup_reads_device.restype = ctypes.c_int
+    L.covest_dedup_reads_device.argtypes = [i32, vp, vp, i64, i64, i64, i32, i32, u64, vp, vp, vp, vp, vp, vp]
     L.covest_split_reads.restype = ctypes.c_int
     L.covest_split_reads.argtypes = [i32, vp, vp, i64, i64, i64, i32, u64, vp, vp, vp, vp]
     L.covest_split_reads_device.restype = ctypes.c_int

@@ -28,6 +28,7 @@ SOURCES = [("host_common.cpp", (), "host_common"), ("tiles_host.cpp", (), "tiles
            ("abi_sample.cpp", (), "abi_sample"), ("sample_reads.hip", (), "sample_reads"),
            ("abi_split.cpp", (), "abi_split"), ("split_reads.hip", (), "split_reads"),
            ("gather_reads.hip", (), "gather_reads"),
+           ("abi_dedup.cpp", (), "abi_dedup"), ("dedup_reads.hip", (), "dedup_reads"),
            ("abi_repeat.cpp", (), "abi_repeat"), ("sim_repeats.hip", (), "sim_repeats"),
            ("abi_draw.cpp", (), "abi_draw"), ("draw_hist.hip", (), "draw_hist"),
            ("abi_batch.cpp", (), "abi_batch"), ("ll_batch.hip", (), "ll_batch"),

@@ -27,7 +27,8 @@ def _finite_int(x):
 def print_output(hist_orig, model, success, sample_factor, estimated=None, guess=None, orig=None,
                  reads_size=None, silent=False, orig_sample_factor=1, starting_points=1,
                  use_grid_search=False, intervals=None, information=None, bootstrap=None, jackknife=None,
-                 posterior=None, read_errors=None, corrections=None, read_influence=None, read_bootstrap=None):
+                 posterior=None, read_errors=None, corrections=None, read_influence=None, read_bootstrap=None,
+                 duplicates=None):
     """`intervals`: the dict covest_amd.profile.coverage_interval returns; the record then carries the likelihood-ratio
     interval of the coverage, of the genome size and its level.  Without it the record is the reference's, key for key.
     `information`: the dict covest_amd.information.observed_information returns (a key 'level' in it chooses the Wald
@@ -73,7 +74,10 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
     read_bootstrap_level and, per free parameter and for genome_size, read_bootstrap_se_<name>,
     read_bootstrap_bias_<name> and read_bootstrap_interval_<name> (the percentile interval): the Poisson bootstrap over
     READS, the genome held fixed -- measured to be biased by the duplicated reads, the jackknife's fields are the ones
-    to rely on.  Without it the record is unchanged."""
+    to rely on.  Without it the record is unchanged.
+    `duplicates`: the DedupReads covest_amd.dedup.dedup_reads returns; the record then carries duplicates_reads (the
+    reads that went in), duplicates_kept, duplicates_share (the share that was dropped) and duplicates_max_copies
+    (DESIGN.md 6al).  Without it the record is unchanged."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -223,6 +227,11 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
             interval = read_bootstrap['intervals'].get(name)
             if interval is not None:
                 record['read_bootstrap_interval_%s' % name] = [float(v) for v in interval]
+    if duplicates is not None:
+        record['duplicates_reads'] = int(duplicates.n_input)
+        record['duplicates_kept'] = int(duplicates.n_reads)
+        record['duplicates_share'] = float(duplicates.duplicate_share)
+        record['duplicates_max_copies'] = int(duplicates.copies.max()) if duplicates.n_reads else 0
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

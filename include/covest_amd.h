@@ -628,6 +628,46 @@ int covest_sample_reads(int32_t device, const uint8_t *bases, const int64_t *off
                         uint8_t *out_bases, int64_t *out_offsets, int64_t *kept_index,
                         int64_t *n_kept, int64_t *bases_kept);
 
+/* ---- duplicate reads removed: the first copy kept, input order ----
+ * Takes the copies out of a read set in the packed layout above (PCR and optical duplicates double the variance of the
+ * k-mer abundances and make repeated misreads look like k-mers of abundance 2) and writes the kept reads, IN INPUT
+ * ORDER, in the layout they came in.  The result is a function of the input; scheduling does not change it.
+ *   Equality: reads x and y are equal if they have the same length and the same bytes; with reverse_complement != 0 also
+ *   if x is the reverse complement of y (a <-> t, c <-> g in either case, the case kept; every other byte is its own
+ *   complement).  Case is not folded.  Two empty reads are equal.
+ *   Fingerprint: mix64(z) is the finaliser of SplitMix64 (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *   z *= 0x94D049BB133111EB; z ^= z >> 31); salt = mix64(seed + 0x9E3779B97F4A7C15); S(x) = the sum mod 2^64 over the
+ *   positions j of mix64(salt + 256 * j + x[j]); F(x) = mix64(mix64(S(x) + seed) + len(x)).  A read's fingerprint is
+ *   F(x), with reverse_complement min(F(x), F(rc(x))); its KEY the low fp_bits bits of that, fp_bits in 1 .. 63 (so the
+ *   table's empty sentinel, ~0, is no key).  fp_bits below 63 only makes more reads collide: it is there for tests of
+ *   the collision route.  Pass 63.
+ *   rep(r) = the lowest read index among the call's reads that have r's key.  Read r is KEPT iff rep(r) == r, or read r
+ *   is not equal to read rep(r) (a fingerprint collision: kept and counted as collided), or its insert into the table
+ *   ran out of probes (2^16; counted alike).  Otherwise it is DROPPED and is one more copy of rep(r).
+ * So every dropped read is equal to an earlier read that is kept, a read without an equal is never dropped, and a
+ * duplicate survives only beside a collision: where counts[2] > 0, the call run again on its own output with another
+ * seed removes the remainder.
+ * Output: out_bases (any alignment), out_offsets[n_kept + 1] (may be NULL where offsets is), kept_index[n_kept] (may be
+ * NULL): first_read + the index within the call; copies[n_kept] (may be NULL): 1 + the reads dropped onto that read;
+ * counts[3] = (reads kept, bases kept, reads kept as collided).  The caller sizes the outputs for the input; nothing is
+ * written outside out_bases[0 .. bases_kept), out_offsets[0 .. n_kept], kept_index[0 .. n_kept), copies[0 .. n_kept)
+ * and counts[0 .. 3).  Scratch is the library's own: 16 bytes a slot of a table of the power of two of slots that is
+ * at least 2 * n_reads, and 20 bytes a read.  The compared read must be resident: one call, one resident set.
+ * COVEST_E_INVALID: fp_bits outside 1 .. 63; n_reads < 0 or first_read < 0; offsets == NULL with read_len < 0; offsets
+ * without out_offsets; a NULL counts.  n_reads == 0: COVEST_OK, no kernel launched, counts (0, 0, 0) and out_offsets[0]
+ * = 0 (the device form sets them by a memset on the stream).  COVEST_E_NOMEM where the device buffers of the call do not
+ * fit.  device < 0 = the calling thread's current device.
+ * The _device form takes DEVICE buffers, is asynchronous on `stream` and does not look at the offsets; the other takes
+ * HOST buffers, copies and waits, and answers COVEST_E_INVALID for offsets that are negative or descend. */
+int covest_dedup_reads_device(int32_t device, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                              int64_t read_len, int64_t first_read, int32_t reverse_complement, int32_t fp_bits,
+                              uint64_t seed, uint8_t *d_out_bases, int64_t *d_out_offsets, int64_t *d_kept_index,
+                              int32_t *d_copies, int64_t *d_counts /* 3 */, void *stream);
+int covest_dedup_reads(int32_t device, const uint8_t *bases, const int64_t *offsets, int64_t n_reads, int64_t read_len,
+                       int64_t first_read, int32_t reverse_complement, int32_t fp_bits, uint64_t seed,
+                       uint8_t *out_bases, int64_t *out_offsets, int64_t *kept_index, int32_t *copies,
+                       int64_t *n_kept, int64_t *bases_kept, int64_t *n_collided);
+
 /* ---- read groups: a stable G-way split of the packed reads ----
  * Deals every read into one of `groups` = G groups (1 <= G <= 256) and writes the reads group by group -- group 0's
  * first, then group 1's, ... --, IN INPUT ORDER WITHIN A GROUP (a stable partition), in the layout they came in: the
