@@ -31,6 +31,7 @@ import math
 import numpy as np
 
 from . import _capi
+from .read_sets import check_refit_request
 
 # the kernel's constants (csrc/kernels.h; tests/test_draw_cpu.py compares): the cap on m, the two LDS layouts' limits,
 # the guide table's size and the draws a workgroup takes
@@ -287,16 +288,8 @@ def parametric_bootstrap(model, estimate, replicates=100, seed=0, fix=None, leve
     genome_size['t_interval'], the coverage interval's endpoints through the monotone map c -> genome size.
     See the module's docstring for what these numbers do and do not say."""
     replicates, seed = int(replicates), int(seed)
-    estimate = [float(v) for v in estimate]
-    names = list(model.params)
-    if len(estimate) != len(names):
-        raise ValueError("parametric_bootstrap: %d parameters expected, %d given" % (len(names), len(estimate)))
-    if refit not in ("sequential", "lockstep", "lockstep-gradient"):
-        raise ValueError('refit must be "sequential", "lockstep" or "lockstep-gradient"')
-    if refit == "lockstep" and estimator_options.get('gradient', 'fd') != 'fd':
-        raise ValueError('refit="lockstep" goes with gradient="fd" only: the analytic gradient is refit="lockstep-gradient"')
-    if refit == "lockstep-gradient" and estimator_options.get('gradient', 'analytic') != 'analytic':
-        raise ValueError('refit="lockstep-gradient" goes with gradient="analytic" only: finite differences are refit="lockstep"')
+    estimate, names = check_refit_request("parametric_bootstrap", model, estimate, refit, estimator_options, level,
+                                          refits=("sequential", "lockstep", "lockstep-gradient"))
     n_draws = int(round(float(sum(model.hist.values())) + float(model.tail)))
     estimates = np.full((replicates, len(names)), np.nan)
     success = np.zeros(replicates, dtype=bool)

@@ -22,7 +22,7 @@ import numpy as np
 from . import _capi
 from .kmer_hist import NS_IGNORE, ReadBatches
 from .sample import _packed, _write_records
-from .simulate import _check_seed
+from .simulate import _check_first_read, _check_seed
 
 FP_BITS = 63       # the fingerprint's bits; fewer only make more reads collide (the tests' way into that route)
 MAX_ROUNDS = 4     # of dedup_reads: a round more for as long as reads were kept as collided
@@ -31,11 +31,10 @@ MAX_ROUNDS = 4     # of dedup_reads: a round more for as long as reads were kept
 def _check(seed, first_read, fp_bits=FP_BITS):
     """The argument rules of covest_dedup_reads, before the library is asked (ValueError, as sample.py's)."""
     _check_seed(seed, whole=True)
-    if int(first_read) != first_read or first_read < 0:
-        raise ValueError("first_read must not be negative")
+    first_read = _check_first_read(first_read)
     if isinstance(fp_bits, bool) or int(fp_bits) != fp_bits or not 1 <= fp_bits <= 63:
         raise ValueError("fp_bits must be within 1 .. 63")
-    return int(seed), int(first_read), int(fp_bits)
+    return int(seed), first_read, int(fp_bits)
 
 
 class DedupReads:

@@ -29,6 +29,7 @@ import numpy as np
 
 from . import _capi
 from .batch import pair_index
+from .read_sets import check_refit_request
 
 MAX_MOMENT_COLUMNS = 9  # csrc/kmer_influence.h kMomentsMaxQ
 
@@ -251,17 +252,9 @@ def read_influence(model, estimate, counts, reads, fix=None, level=0.95):
 
     A sample factor other than 1 raises ValueError: sample_histogram rounds at random, so the histogram would not be a
     function of the reads."""
-    estimate = [float(v) for v in estimate]
-    names = list(model.params)
-    if len(estimate) != len(names):
-        raise ValueError("read_influence: %d parameters expected, %d given" % (len(names), len(estimate)))
-    if not (isinstance(level, (int, float)) and 0.0 < level < 1.0):
-        raise ValueError("level must be in (0, 1)")
-    if getattr(model, 'sample_factor', 1) != 1:
-        raise ValueError("read_influence needs a model built with sample factor 1: a down-sampled histogram is rounded at "
-                         "random and is not a function of the reads")
-    if fix is not None and len(fix) != len(names):
-        raise ValueError("read_influence: fix needs one entry per parameter")
+    # (a level that is no int or float is refused here as NaN is: the jackknife's rule takes any number)
+    estimate, names = check_refit_request("read_influence", model, estimate, fix=fix, sample_factor=1,
+                                          level=level if isinstance(level, (int, float)) else math.nan)
     if int(counts.k) != int(model.k):
         raise ValueError("read_influence: the counter's k (%d) is not the model's (%d)" % (counts.k, model.k))
     from .batch import HistogramBatch

@@ -18,29 +18,9 @@ import math
 
 import numpy as np
 
-from . import _capi
-from .sample import MAX_GROUPS, _DeviceArena, _check_split, _packed, split_reads_device
-
-REFITS = ("lockstep", "lockstep-gradient")
-
-
-def _hist_dict(counts):
-    """KmerCounts.histogram()'s list as {abundance: k-mers}, the abundances that occur."""
-    return {i: int(v) for i, v in enumerate(counts.histogram()) if i > 0 and v > 0}
-
-
-def _occurrences(hist):
-    return int(sum(i * n for i, n in hist.items()))
-
-
-def _check_groups(groups):
-    if isinstance(groups, bool) or not isinstance(groups, (int, np.integer)):
-        raise ValueError("groups must be an integer")
-    if groups < 2:
-        raise ValueError("a jackknife needs at least two groups")
-    if groups > MAX_GROUPS:
-        raise ValueError("groups must be within 2 .. %d" % MAX_GROUPS)
-    return int(groups)
+from .read_sets import (REFITS, ResidentReads, _cut, _hist_dict, _occurrences, check_refit_request, check_sets,  # noqa: F401
+                        jackknife_batch, quantity_rows, refit_histogram_set)
+from .sample import MAX_GROUPS, _check_split, split_reads_device
 
 
 def leave_group_out_histograms(reads, k, groups, seed=0, canonical=False, device=-1):
@@ -58,64 +38,31 @@ def leave_group_out_histograms(reads, k, groups, seed=0, canonical=False, device
 
 def _leave_group_out(reads, k, groups, seed, canonical, device):
     """leave_group_out_histograms, and the split's group_first behind its three results."""
-    groups = _check_groups(groups)
+    groups = check_sets("groups", groups, "jackknife", MAX_GROUPS, MAX_GROUPS)
     groups, seed, _ = _check_split(groups, seed, 0)
-    if int(k) != k or k < 1:
-        raise ValueError("k must be a positive integer")
-    blob, offsets, n, read_len, source = _packed(reads)
-    first_read = int(source.first_read) if source is not None else 0
-    from .kmer_hist import KmerCounts
-    n_bases = int(offsets[-1]) if offsets is not None else n * read_len
-    arena = counts = None
-    try:
-        arena = _DeviceArena("leave_group_out_histograms")
-        if device >= 0:
-            import ctypes
-            current = ctypes.c_int(-1)
-            arena.hip.hipGetDevice(ctypes.byref(current))
-            if current.value != int(device):
-                raise _capi.CovestHipError("leave_group_out_histograms: the reads are staged on the calling thread's current "
-                                           "device (%d), not device %d" % (current.value, device))
-        try:
-            d_in = arena.upload("in", blob.ctypes.data, n_bases)
-            d_off = arena.upload("offsets", offsets.ctypes.data, 8 * (n + 1)) if offsets is not None else None
-            d_out = arena.reserve("out", n_bases)
-            d_out_off = arena.reserve("out_offsets", 8 * (n + 1)) if offsets is not None else None
-            d_first = arena.reserve("group_first", 8 * (groups + 1))
-        except _capi.CovestHipError as e:
-            raise _capi.CovestHipError("leave_group_out_histograms: %d bases of reads do not fit the device together with "
-                                       "their copy in group order (%s)" % (n_bases, e))
-        split_reads_device(d_in, n, d_out, d_first, groups, seed=seed, first_read=first_read, read_len=read_len,
-                           offsets_ptr=d_off, out_offsets_ptr=d_out_off, device=device)
+    with ResidentReads(reads, k, canonical, device, "leave_group_out_histograms", "their copy in group order") as rs:
+        d_out = rs.reserve("out", rs.n_bases)
+        d_out_off = rs.reserve("out_offsets", 8 * (rs.n + 1)) if rs.offsets is not None else None
+        d_first = rs.reserve("group_first", 8 * (groups + 1))
+        split_reads_device(rs.d_in, rs.n, d_out, d_first, groups, seed=seed, first_read=rs.first_read, read_len=rs.read_len,
+                           offsets_ptr=rs.d_offsets, out_offsets_ptr=d_out_off, device=device)
         first = np.empty(groups + 1, dtype=np.int64)
-        arena.download("group_first", first)  # (the null stream: waits for the split)
-
-        counts = KmerCounts(k, canonical=canonical, device=device)
-        # k-mers the whole set can add: sum(max(len - k + 1, 1)), bounded as add_packed bounds it
-        counts._reserve_for(n_bases + n if offsets is not None else n * max(read_len - int(k) + 1, 1))
+        rs.download("group_first", first)  # (waits for the split)
+        rs.open_counter()
 
         def add(lo, hi):  # ranks [lo, hi) of the split buffer
-            if hi <= lo:
-                return
-            if offsets is not None:
-                counts.add_device(d_out, hi - lo, 0, d_offsets_ptr=d_out_off + 8 * lo, reserve=False)
-            else:
-                counts.add_device(d_out + lo * read_len, hi - lo, read_len, reserve=False)
+            if hi > lo:
+                rs.count(d_out, d_out_off, lo, hi)
 
-        add(0, n)
-        hist_full = _hist_dict(counts)  # (waits for the counter)
+        add(0, rs.n)
+        hist_full = rs.histogram()
         hists = []
         for g in range(groups):
-            counts.clear()
+            rs.clear()
             add(0, int(first[g]))
-            add(int(first[g + 1]), n)
-            hists.append(_hist_dict(counts))
+            add(int(first[g + 1]), rs.n)
+            hists.append(rs.histogram())
         return hist_full, hists, [_occurrences(h) for h in hists], first
-    finally:
-        if counts is not None:
-            counts.close()
-        if arena is not None:
-            arena.close()
 
 
 def summarize_jackknife(estimates, success, full, occurrences, occurrences_full, names, fix, level, correct_c):
@@ -132,32 +79,15 @@ def summarize_jackknife(estimates, success, full, occurrences, occurrences_full,
     - mean)^2); bias = (G' - 1) (mean - theta_full); bias_corrected = theta_full - bias; intervals = theta_full -+
     t_{G' - 1, (1 + level) / 2} * standard error.  None for a fixed parameter (the genome size goes with the coverage),
     and for everything where G' < 2.  Also `failed` = G - G' and `used` = G'."""
-    if not (0.0 < level < 1.0):
-        raise ValueError("level must be in (0, 1)")
-    names = list(names)
-    est = np.asarray(estimates, dtype=np.float64).reshape(-1, len(names))
-    ok = np.asarray(success, dtype=bool).reshape(-1)
-    occ = np.asarray(occurrences, dtype=np.float64).reshape(-1)
-    full = np.asarray(full, dtype=np.float64).reshape(-1)
-    if not (len(est) == len(ok) == len(occ)) or len(full) != len(names):
-        raise ValueError("summarize_jackknife: one estimate, success flag and occurrence count per group")
-    fix = [None] * len(names) if fix is None else list(fix)
-    used = int(ok.sum())
-    good, good_occ = est[ok], occ[ok]
-    # (quantity, its G' leave-out values, its value on the full set, free)
-    rows = []
-    for d, name in enumerate(names):
-        values = good[:, d] * (float(occurrences_full) / good_occ) if d == 0 else good[:, d]
-        rows.append((name, values, float(full[d]), fix[d] is None))
-    rows.append(('genome_size', np.array([o / correct_c(c) for o, c in zip(good_occ, good[:, 0])], dtype=np.float64),
-                 float(occurrences_full) / correct_c(float(full[0])), fix[0] is None))
+    used, ok, rows = quantity_rows("summarize_jackknife", estimates, success, full, occurrences, occurrences_full, names, fix,
+                                   level, correct_c, "group")
     out = {'mean': {}, 'standard_errors': {}, 'bias': {}, 'bias_corrected': {}, 'intervals': {},
            'failed': int(len(ok) - used), 'used': used}
     quantile = None
     if used >= 2:
         from scipy.stats import t as student_t
         quantile = float(student_t.ppf(0.5 * (1.0 + level), used - 1))
-    for name, values, theta_full, free in rows:
+    for name, values, theta_full, free, _ in rows:
         if not free or used < 2:
             for key in ('mean', 'standard_errors', 'bias', 'bias_corrected', 'intervals'):
                 out[key][name] = None
@@ -171,37 +101,6 @@ def summarize_jackknife(estimates, success, full, occurrences, occurrences_full,
         out['bias_corrected'][name] = theta_full - bias
         out['intervals'][name] = [theta_full - quantile * se, theta_full + quantile * se]
     return out
-
-
-def _cut(hist, trim):
-    """(kept, tail) of one histogram under the model's cut (hist_steps.trim_hist); trim None: no cut."""
-    if trim is None or not hist:
-        return dict(hist), 0
-    from .hist_steps import trim_hist
-    return trim_hist(hist, trim)
-
-
-def jackknife_batch(model, hists, hist_full, trim=None):
-    """(twin, batch, keys_added): the leave-out histograms (rows 0 .. G - 1) and the full one (row G) as ONE
-    HistogramBatch on a twin of `model` whose key set is the model's keys and behind them, ascending, the keys any of
-    the histograms keeps beyond those, zero counts kept.  Each histogram is cut as read_jackknife states.  Both are the
-    caller's to close (batch first)."""
-    from .batch import HistogramBatch
-    from .bootstrap import _replicate_model
-    if trim is None and model.tail != 0:
-        trim = max(model.hist) + 1
-    cut = [_cut(h, trim) for h in list(hists) + [hist_full]]
-    own = list(model.hist.keys())
-    added = sorted(set().union(*(kept.keys() for kept, _ in cut)) - set(own))
-    keys = own + added
-    counts = np.array([[kept.get(j, 0) for j in keys] for kept, _ in cut], dtype=np.float64)
-    tails = np.array([tail for _, tail in cut], dtype=np.float64)
-    twin = _replicate_model(model, keys, counts[-1], float(tails[-1]))
-    try:
-        return twin, HistogramBatch(twin, counts, tails), len(added)
-    except Exception:
-        twin.close()
-        raise
 
 
 def read_jackknife(model, estimate, reads, groups=32, seed=0, fix=None, level=0.95, trim=None, refit="lockstep-gradient",
@@ -233,46 +132,14 @@ def read_jackknife(model, estimate, reads, groups=32, seed=0, fix=None, level=0.
     (G x P), group_sizes (reads a group), occurrences (G), occurrences_full, full_estimate (row G's refit),
     full_success, full_minus_given (its distance from `estimate`), keys_added (keys of the union the model did not
     have), params, estimate, level, groups, seed, refit."""
-    groups = _check_groups(groups)
+    groups = check_sets("groups", groups, "jackknife", MAX_GROUPS, MAX_GROUPS)
     _check_split(groups, seed, 0)
-    estimate = [float(v) for v in estimate]
-    names = list(model.params)
-    if len(estimate) != len(names):
-        raise ValueError("read_jackknife: %d parameters expected, %d given" % (len(names), len(estimate)))
-    if refit not in REFITS:
-        raise ValueError('refit must be "lockstep" or "lockstep-gradient"')
-    if refit == "lockstep" and estimator_options.get('gradient', 'fd') != 'fd':
-        raise ValueError('refit="lockstep" goes with gradient="fd" only: the analytic gradient is refit="lockstep-gradient"')
-    if refit == "lockstep-gradient" and estimator_options.get('gradient', 'analytic') != 'analytic':
-        raise ValueError('refit="lockstep-gradient" goes with gradient="analytic" only: finite differences are refit="lockstep"')
-    if not (0.0 < level < 1.0):
-        raise ValueError("level must be in (0, 1)")
-    if sample_factor != 1 or getattr(model, 'sample_factor', 1) != 1:
-        raise ValueError("read_jackknife needs a model built with sample factor 1: a down-sampled histogram is rounded at "
-                         "random and is not a function of the reads")
-    if fix is not None and len(fix) != len(names):
-        raise ValueError("read_jackknife: fix needs one entry per parameter")
-    if trim is not None and (int(trim) != trim or trim < 1):
-        raise ValueError("trim must be a positive integer")
-    from .bootstrap import _on_bound, _refit_lockstep
-
-    hist_full, hists, occurrences, group_first = _leave_group_out(reads, model.k, groups, seed, canonical, model.device)
-    occurrences_full = _occurrences(hist_full)
-    twin, batch, added = jackknife_batch(model, hists, hist_full, trim)
-    try:
-        estimates, success, _ = _refit_lockstep(twin, estimate, groups + 1, seed, 0, fix, estimator_options,
-                                                analytic=refit == "lockstep-gradient", batch=batch)
-    finally:
-        batch.close()
-        twin.close()
-    full = [float(v) for v in estimates[groups]]
-    out = {'groups': groups, 'seed': int(seed), 'refit': refit, 'level': float(level), 'params': names, 'estimate': estimate,
-           'estimates': estimates[:groups].copy(), 'success': success[:groups].copy(),
-           'at_bound': np.array([_on_bound(row, model.bounds) for row in estimates[:groups]], dtype=bool),
-           'occurrences': list(occurrences), 'occurrences_full': occurrences_full,
-           'full_estimate': full, 'full_success': bool(success[groups]),
-           'full_minus_given': [a - b for a, b in zip(full, estimate)], 'keys_added': added,
-           'group_sizes': np.diff(group_first).tolist()}
-    out.update(summarize_jackknife(out['estimates'], out['success'], full, occurrences, occurrences_full, names, fix, level,
-                                   model.correct_c))
+    estimate, names = check_refit_request("read_jackknife", model, estimate, refit, estimator_options, level, fix, trim,
+                                          sample_factor, REFITS)
+    hist_full, hists, _, group_first = _leave_group_out(reads, model.k, groups, seed, canonical, model.device)
+    out = {'groups': groups}
+    out.update(refit_histogram_set(model, estimate, hists, hist_full, seed, fix, level, trim, refit, estimator_options))
+    out['group_sizes'] = np.diff(group_first).tolist()
+    out.update(summarize_jackknife(out['estimates'], out['success'], out['full_estimate'], out['occurrences'],
+                                   out['occurrences_full'], names, fix, level, model.correct_c))
     return out

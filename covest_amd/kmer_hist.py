@@ -80,6 +80,23 @@ def scatter_rate(slots, ops=1 << 28, device=0):
 NO_WINDOW = 0xFFFFFFFF  # in the flat abundance array: no window starts at this base
 
 
+def _bases_and_offsets(bases, offsets):
+    """The rule of a pair (bases, offsets) in the packed layout, and the pair as contiguous uint8 and int64 arrays: the
+    bases one-dimensional uint8, the offsets n_reads + 1 integers that ascend from a non-negative start and do not reach
+    beyond the bases (ValueError)."""
+    bases, offsets = np.asarray(bases), np.asarray(offsets)
+    if bases.dtype != np.uint8 or bases.ndim != 1:
+        raise ValueError("bases must be a one-dimensional uint8 array")
+    if offsets.ndim != 1 or offsets.size < 1 or offsets.dtype.kind not in "iu":
+        raise ValueError("offsets must be a one-dimensional integer array of n_reads + 1 entries")
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offsets[0] < 0 or (np.diff(offsets) < 0).any():
+        raise ValueError("offsets must ascend from a non-negative start")
+    if offsets[-1] > bases.size:
+        raise ValueError("offsets reach beyond the bases")
+    return np.ascontiguousarray(bases), offsets
+
+
 def _packed_reads(reads):
     """(bases uint8[...], offsets int64[n + 1]) of what KmerCounts.lookup takes: a list of strings, a pair (bases,
     offsets), an (n, L) uint8 array or an object that carries one as `.bases` (SimulatedReads).  ValueError for
@@ -92,16 +109,7 @@ def _packed_reads(reads):
         blob = np.ascontiguousarray(reads).reshape(-1)
         offsets = np.arange(reads.shape[0] + 1, dtype=np.int64) * reads.shape[1]
     elif isinstance(reads, tuple) and len(reads) == 2 and not isinstance(reads[0], str):
-        blob, offsets = np.asarray(reads[0]), np.asarray(reads[1])
-        if blob.dtype != np.uint8 or blob.ndim != 1:
-            raise ValueError("bases must be a one-dimensional uint8 array")
-        if offsets.ndim != 1 or offsets.size < 1 or offsets.dtype.kind not in "iu":
-            raise ValueError("offsets must be a one-dimensional integer array of n_reads + 1 entries")
-        blob, offsets = np.ascontiguousarray(blob), np.ascontiguousarray(offsets, dtype=np.int64)
-        if offsets[0] < 0 or (np.diff(offsets) < 0).any():
-            raise ValueError("offsets must ascend from a non-negative start")
-        if offsets[-1] > blob.size:
-            raise ValueError("offsets reach beyond the bases")
+        blob, offsets = _bases_and_offsets(*reads)
     else:
         reads = [r if isinstance(r, str) else str(r) for r in reads]
         lens = np.fromiter((len(r) for r in reads), dtype=np.int64, count=len(reads))

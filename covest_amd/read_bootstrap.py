@@ -21,9 +21,10 @@ import ctypes
 import numpy as np
 
 from . import _capi
-from .jackknife import REFITS, _hist_dict, _occurrences, jackknife_batch
-from .sample import _DeviceArena, _packed
-from .simulate import _check_seed
+from .read_sets import (REFITS, ResidentReads, _occurrences, check_refit_request, check_sets, quantity_rows,
+                        refit_histogram_set)
+from .simulate import _check_first_read, _check_seed
+
 
 def _check_weights_args(n_reads, replicate, seed, first_read):
     """The argument rules of covest_bootstrap_weights, before the library is asked (ValueError)."""
@@ -32,9 +33,7 @@ def _check_weights_args(n_reads, replicate, seed, first_read):
     if isinstance(replicate, bool) or int(replicate) != replicate or not 0 <= replicate < 1 << 32:
         raise ValueError("replicate must fit 32 bits, not negative")
     _check_seed(seed, whole=True)
-    if int(first_read) != first_read or first_read < 0:
-        raise ValueError("first_read must not be negative")
-    return int(n_reads), int(replicate), int(seed), int(first_read)
+    return int(n_reads), int(replicate), int(seed), _check_first_read(first_read)
 
 
 def bootstrap_weights(n_reads, replicate, seed=0, first_read=0, device=-1):
@@ -60,16 +59,6 @@ def bootstrap_weights_device(out_ptr, n_reads, replicate, seed=0, first_read=0, 
         "covest_bootstrap_weights_device")
 
 
-def _check_replicates(replicates):
-    if isinstance(replicates, bool) or not isinstance(replicates, (int, np.integer)):
-        raise ValueError("replicates must be an integer")
-    if replicates < 2:
-        raise ValueError("a bootstrap needs at least two replicates")
-    if replicates > 1 << 20:
-        raise ValueError("replicates must be within 2 .. 2^20")
-    return int(replicates)
-
-
 def bootstrap_histograms(reads, k, replicates, seed=0, canonical=False, device=-1):
     """(hist_full, [hist_b for b in range(replicates)], occurrences, reads_drawn) of `reads` -- a SimulatedReads, an (n,
     L) uint8 array or a pair (bases, offsets) in the packed layout --: hist_b the k-mer histogram {abundance: k-mers} of
@@ -81,51 +70,23 @@ def bootstrap_histograms(reads, k, replicates, seed=0, canonical=False, device=-
     replicate: draw the weights, clear, add_weighted_device, histogram, all on the null stream.  The buffers live on the
     calling thread's current device, which `device` has to name (or -1).  Reads that do not fit the device raise
     CovestHipError; streaming a file in passes is not built."""
-    replicates = _check_replicates(replicates)
+    replicates = check_sets("replicates", replicates, "bootstrap", 1 << 20, "2^20")
     _check_seed(seed, whole=True)
-    if int(k) != k or k < 1:
-        raise ValueError("k must be a positive integer")
-    blob, offsets, n, read_len, source = _packed(reads)
-    first_read = int(source.first_read) if source is not None else 0
-    from .kmer_hist import KmerCounts
-    n_bases = int(offsets[-1]) if offsets is not None else n * read_len
-    arena = counts = None
-    try:
-        arena = _DeviceArena("bootstrap_histograms")
-        if device >= 0:
-            current = ctypes.c_int(-1)
-            arena.hip.hipGetDevice(ctypes.byref(current))
-            if current.value != int(device):
-                raise _capi.CovestHipError("bootstrap_histograms: the reads are staged on the calling thread's current "
-                                           "device (%d), not device %d" % (current.value, device))
-        try:
-            d_in = arena.upload("in", blob.ctypes.data, n_bases)
-            d_off = arena.upload("offsets", offsets.ctypes.data, 8 * (n + 1)) if offsets is not None else None
-            d_weights = arena.reserve("weights", 4 * n)
-        except _capi.CovestHipError as e:
-            raise _capi.CovestHipError("bootstrap_histograms: %d bases of reads do not fit the device together with a "
-                                       "weight a read (%s)" % (n_bases, e))
-        counts = KmerCounts(k, canonical=canonical, device=device)
-        # k-mers the whole set can add: sum(max(len - k + 1, 1)), bounded as add_packed bounds it
-        counts._reserve_for(n_bases + n if offsets is not None else n * max(read_len - int(k) + 1, 1))
-        counts.add_device(d_in, n, 0 if offsets is not None else read_len, d_offsets_ptr=d_off, reserve=False)
-        hist_full = _hist_dict(counts)  # (waits for the counter)
+    with ResidentReads(reads, k, canonical, device, "bootstrap_histograms", "a weight a read") as rs:
+        d_weights = rs.reserve("weights", 4 * rs.n)
+        rs.open_counter()
+        rs.count(rs.d_in, rs.d_offsets, 0, rs.n)
+        hist_full = rs.histogram()
         hists, drawn = [], []
-        weights = np.empty(n, dtype=np.uint32)
+        weights = np.empty(rs.n, dtype=np.uint32)
         for b in range(replicates):
-            bootstrap_weights_device(d_weights, n, b, seed=seed, first_read=first_read, device=device)
-            counts.clear()
-            counts.add_weighted_device(d_in, n, 0 if offsets is not None else read_len, d_weights, d_offsets_ptr=d_off,
-                                       reserve=False)
-            hists.append(_hist_dict(counts))
-            arena.download("weights", weights)
+            bootstrap_weights_device(d_weights, rs.n, b, seed=seed, first_read=rs.first_read, device=device)
+            rs.clear()
+            rs.count(rs.d_in, rs.d_offsets, 0, rs.n, d_weights)
+            hists.append(rs.histogram())
+            rs.download("weights", weights)
             drawn.append(int(weights.sum(dtype=np.int64)))
         return hist_full, hists, [_occurrences(h) for h in hists], drawn
-    finally:
-        if counts is not None:
-            counts.close()
-        if arena is not None:
-            arena.close()
 
 
 def summarize_read_bootstrap(estimates, success, full, occurrences, occurrences_full, names, fix, level, correct_c,
@@ -144,28 +105,11 @@ def summarize_read_bootstrap(estimates, success, full, occurrences, occurrences_
     size goes with the coverage; None without `at_bound`).  None for a fixed parameter, and for everything where B' < 2.
     Also `failed` = B - B' and `used` = B'."""
     from .bootstrap import _percentiles
-    if not (0.0 < level < 1.0):
-        raise ValueError("level must be in (0, 1)")
-    names = list(names)
-    est = np.asarray(estimates, dtype=np.float64).reshape(-1, len(names))
-    ok = np.asarray(success, dtype=bool).reshape(-1)
-    occ = np.asarray(occurrences, dtype=np.float64).reshape(-1)
-    full = np.asarray(full, dtype=np.float64).reshape(-1)
-    if not (len(est) == len(ok) == len(occ)) or len(full) != len(names):
-        raise ValueError("summarize_read_bootstrap: one estimate, success flag and occurrence count per replicate")
-    bound = None if at_bound is None else np.asarray(at_bound, dtype=bool).reshape(-1, len(names))
-    if bound is not None and len(bound) != len(est):
+    used, ok, rows = quantity_rows("summarize_read_bootstrap", estimates, success, full, occurrences, occurrences_full,
+                                   names, fix, level, correct_c, "replicate")
+    bound = None if at_bound is None else np.asarray(at_bound, dtype=bool).reshape(-1, len(rows) - 1)
+    if bound is not None and len(bound) != len(ok):
         raise ValueError("summarize_read_bootstrap: one row of at_bound per replicate")
-    fix = [None] * len(names) if fix is None else list(fix)
-    used = int(ok.sum())
-    good, good_occ = est[ok], occ[ok]
-    # (quantity, its B' values, its value on the full set, free, the parameter whose bounds it ends on)
-    rows = []
-    for d, name in enumerate(names):
-        values = good[:, d] * (float(occurrences_full) / good_occ) if d == 0 else good[:, d]
-        rows.append((name, values, float(full[d]), fix[d] is None, d))
-    rows.append(('genome_size', np.array([o / correct_c(c) for o, c in zip(good_occ, good[:, 0])], dtype=np.float64),
-                 float(occurrences_full) / correct_c(float(full[0])), fix[0] is None, 0))
     keys = ('mean', 'standard_errors', 'bias', 'intervals', 'bound_share')
     out = {key: {} for key in keys}
     out.update(failed=int(len(ok) - used), used=used)
@@ -214,45 +158,17 @@ def read_bootstrap(model, estimate, reads, replicates=64, seed=0, fix=None, leve
     (B x P), occurrences (B), occurrences_full, reads_drawn (B), full_estimate (row B's refit), full_success,
     full_minus_given (its distance from `estimate`), keys_added (keys of the union the model did not have), params,
     estimate, level, replicates, seed, refit."""
-    replicates = _check_replicates(replicates)
+    replicates = check_sets("replicates", replicates, "bootstrap", 1 << 20, "2^20")
     _check_seed(seed, whole=True)
-    estimate = [float(v) for v in estimate]
-    names = list(model.params)
-    if len(estimate) != len(names):
-        raise ValueError("read_bootstrap: %d parameters expected, %d given" % (len(names), len(estimate)))
-    if refit not in REFITS:
-        raise ValueError('refit must be "lockstep" or "lockstep-gradient"')
-    if refit == "lockstep" and estimator_options.get('gradient', 'fd') != 'fd':
-        raise ValueError('refit="lockstep" goes with gradient="fd" only: the analytic gradient is refit="lockstep-gradient"')
-    if refit == "lockstep-gradient" and estimator_options.get('gradient', 'analytic') != 'analytic':
-        raise ValueError('refit="lockstep-gradient" goes with gradient="analytic" only: finite differences are refit="lockstep"')
-    if not (0.0 < level < 1.0):
-        raise ValueError("level must be in (0, 1)")
-    if sample_factor != 1 or getattr(model, 'sample_factor', 1) != 1:
-        raise ValueError("read_bootstrap needs a model built with sample factor 1: a down-sampled histogram is rounded at "
-                         "random and is not a function of the reads")
-    if fix is not None and len(fix) != len(names):
-        raise ValueError("read_bootstrap: fix needs one entry per parameter")
-    if trim is not None and (int(trim) != trim or trim < 1):
-        raise ValueError("trim must be a positive integer")
-    from .bootstrap import _on_bound, _refit_lockstep
-
-    hist_full, hists, occurrences, drawn = bootstrap_histograms(reads, model.k, replicates, seed, canonical, model.device)
-    occurrences_full = _occurrences(hist_full)
-    twin, batch, added = jackknife_batch(model, hists, hist_full, trim)
-    try:
-        estimates, success, _ = _refit_lockstep(twin, estimate, replicates + 1, seed, 0, fix, estimator_options,
-                                                analytic=refit == "lockstep-gradient", batch=batch)
-    finally:
-        batch.close()
-        twin.close()
-    full = [float(v) for v in estimates[replicates]]
-    out = {'replicates': replicates, 'seed': int(seed), 'refit': refit, 'level': float(level), 'params': names,
-           'estimate': estimate, 'estimates': estimates[:replicates].copy(), 'success': success[:replicates].copy(),
-           'at_bound': np.array([_on_bound(row, model.bounds) for row in estimates[:replicates]], dtype=bool),
-           'occurrences': list(occurrences), 'occurrences_full': occurrences_full, 'reads_drawn': list(drawn),
-           'full_estimate': full, 'full_success': bool(success[replicates]),
-           'full_minus_given': [a - b for a, b in zip(full, estimate)], 'keys_added': added}
-    out.update(summarize_read_bootstrap(out['estimates'], out['success'], full, occurrences, occurrences_full, names, fix,
-                                        level, model.correct_c, at_bound=out['at_bound']))
+    estimate, names = check_refit_request("read_bootstrap", model, estimate, refit, estimator_options, level, fix, trim,
+                                          sample_factor, REFITS)
+    hist_full, hists, _, drawn = bootstrap_histograms(reads, model.k, replicates, seed, canonical, model.device)
+    out = {'replicates': replicates}
+    for key, value in refit_histogram_set(model, estimate, hists, hist_full, seed, fix, level, trim, refit,
+                                          estimator_options).items():
+        out[key] = value
+        if key == 'occurrences_full':  # (the replicates' sizes stand beside their occurrences)
+            out['reads_drawn'] = list(drawn)
+    out.update(summarize_read_bootstrap(out['estimates'], out['success'], out['full_estimate'], out['occurrences'],
+                                        out['occurrences_full'], names, fix, level, model.correct_c, at_bound=out['at_bound']))
     return out

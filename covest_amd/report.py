@@ -88,6 +88,22 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
             row[0] *= sample_factor
         return {name: v for name, v in zip(names, row) if v is not None}
 
+    def resampled(prefix, result, count=None, kinds=(('se', 'standard_errors'), ('bias', 'bias'))):
+        """The fields of a statistic over resampled reads under `prefix`: with `count` (the key of its groups or
+        replicates) that number, used, failed and level; then, per parameter and for the genome size, the `kinds` and the
+        interval where it has them."""
+        if count is not None:
+            for key, kind in ((count, int), ('used', int), ('failed', int), ('level', float)):
+                record['%s_%s' % (prefix, key)] = kind(result[key])
+        for name in list(model.params) + ['genome_size']:
+            for key, source in kinds:
+                value = result[source].get(name)
+                if value is not None:
+                    record['%s_%s_%s' % (prefix, key, name)] = float(value)
+            interval = result['intervals'].get(name)
+            if interval is not None:
+                record['%s_interval_%s' % (prefix, name)] = [float(v) for v in interval]
+
     record = {
         'model': model.short_name(),
         'hist_size': max(model.hist),
@@ -169,18 +185,7 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
         if size is not None and size.get('t_interval') is not None:
             record['bootstrap_t_interval_genome_size'] = [float(v) for v in size['t_interval']]
     if jackknife is not None:
-        record['jackknife_groups'] = int(jackknife['groups'])
-        record['jackknife_used'] = int(jackknife['used'])
-        record['jackknife_failed'] = int(jackknife['failed'])
-        record['jackknife_level'] = float(jackknife['level'])
-        for name in list(model.params) + ['genome_size']:
-            for key, source in (('se', 'standard_errors'), ('bias', 'bias')):
-                value = jackknife[source].get(name)
-                if value is not None:
-                    record['jackknife_%s_%s' % (key, name)] = float(value)
-            interval = jackknife['intervals'].get(name)
-            if interval is not None:
-                record['jackknife_interval_%s' % name] = [float(v) for v in interval]
+        resampled('jackknife', jackknife, 'groups')
     if posterior is not None:
         cutoff = posterior.error_cutoff()
         record['posterior_error_cutoff'] = None if cutoff is None else int(cutoff)
@@ -207,26 +212,9 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
         record['read_influence_level'] = float(summary['level'])
         if summary.get('reason') is not None:
             record['read_influence_reason'] = str(summary['reason'])
-        for name in list(model.params) + ['genome_size']:
-            value = summary['standard_errors'].get(name)
-            if value is not None:
-                record['read_influence_se_%s' % name] = float(value)
-            interval = summary['intervals'].get(name)
-            if interval is not None:
-                record['read_influence_interval_%s' % name] = [float(v) for v in interval]
+        resampled('read_influence', summary, kinds=(('se', 'standard_errors'),))
     if read_bootstrap is not None:
-        record['read_bootstrap_replicates'] = int(read_bootstrap['replicates'])
-        record['read_bootstrap_used'] = int(read_bootstrap['used'])
-        record['read_bootstrap_failed'] = int(read_bootstrap['failed'])
-        record['read_bootstrap_level'] = float(read_bootstrap['level'])
-        for name in list(model.params) + ['genome_size']:
-            for key, source in (('se', 'standard_errors'), ('bias', 'bias')):
-                value = read_bootstrap[source].get(name)
-                if value is not None:
-                    record['read_bootstrap_%s_%s' % (key, name)] = float(value)
-            interval = read_bootstrap['intervals'].get(name)
-            if interval is not None:
-                record['read_bootstrap_interval_%s' % name] = [float(v) for v in interval]
+        resampled('read_bootstrap', read_bootstrap, 'replicates')
     if duplicates is not None:
         record['duplicates_reads'] = int(duplicates.n_input)
         record['duplicates_kept'] = int(duplicates.n_reads)

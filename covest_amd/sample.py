@@ -20,8 +20,8 @@ import math
 import numpy as np
 
 from . import _capi
-from .kmer_hist import NS_IGNORE, KmerCounts, ReadBatches
-from .simulate import SimulatedReads, _check_seed
+from .kmer_hist import NS_IGNORE, KmerCounts, ReadBatches, _bases_and_offsets
+from .simulate import SimulatedReads, _check_first_read, _check_seed
 
 
 def _check(factor, seed, first_read):
@@ -33,9 +33,7 @@ def _check(factor, seed, first_read):
     if not (factor >= 1.0) or not math.isfinite(factor):  # (NaN fails the first)
         raise ValueError("factor must be a finite number, at least 1")
     _check_seed(seed, whole=True)
-    if int(first_read) != first_read or first_read < 0:
-        raise ValueError("first_read must not be negative")
-    return factor, int(seed), int(first_read)
+    return factor, int(seed), _check_first_read(first_read)
 
 
 def threshold(factor):
@@ -49,17 +47,8 @@ def _packed(reads):
         n, L = reads.bases.shape
         return np.ascontiguousarray(reads.bases).reshape(-1), None, n, L, reads
     if isinstance(reads, tuple) and len(reads) == 2:
-        bases, offsets = np.asarray(reads[0]), np.asarray(reads[1])
-        if bases.dtype != np.uint8 or bases.ndim != 1:
-            raise ValueError("bases must be a one-dimensional uint8 array")
-        if offsets.ndim != 1 or offsets.size < 1 or offsets.dtype.kind not in "iu":
-            raise ValueError("offsets must be a one-dimensional integer array of n_reads + 1 entries")
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        if offsets[0] < 0 or (np.diff(offsets) < 0).any():
-            raise ValueError("offsets must ascend from a non-negative start")
-        if offsets[-1] > bases.size:
-            raise ValueError("offsets reach beyond the bases")
-        return np.ascontiguousarray(bases), offsets, offsets.size - 1, 0, None
+        bases, offsets = _bases_and_offsets(*reads)
+        return bases, offsets, offsets.size - 1, 0, None
     a = np.asarray(reads)
     if a.dtype != np.uint8 or a.ndim != 2:
         raise ValueError("reads must be a SimulatedReads, an (n, L) uint8 array or a pair (bases, offsets)")
@@ -190,9 +179,7 @@ def _check_split(groups, seed, first_read):
     if not 1 <= groups <= MAX_GROUPS:
         raise ValueError("groups must be within 1 .. %d" % MAX_GROUPS)
     _check_seed(seed, whole=True)
-    if int(first_read) != first_read or first_read < 0:
-        raise ValueError("first_read must not be negative")
-    return int(groups), int(seed), int(first_read)
+    return int(groups), int(seed), _check_first_read(first_read)
 
 
 class SplitReads:

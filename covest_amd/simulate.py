@@ -52,6 +52,13 @@ def _check_seed(seed, whole=False):
         raise ValueError("seed must fit 64 bits")
 
 
+def _check_first_read(first_read):
+    """The index of a call's first read, as an int: a whole number, not negative."""
+    if int(first_read) != first_read or first_read < 0:
+        raise ValueError("first_read must not be negative")
+    return int(first_read)
+
+
 def _check(read_length, genome_len, n_reads, first_read, error_rate, seed):
     """The argument rules of covest_simulate_reads, before the library is asked (ValueError, as the models' arguments)."""
     if int(read_length) != read_length or read_length < 1:

@@ -82,6 +82,31 @@ def test_two_groups_are_each_others_complement(hip_lib):
         jackknife.leave_group_out_histograms(reads, 9, 1)
 
 
+def test_a_read_index_that_crosses_a_word_inside_the_set(hip_lib):
+    """A SimulatedReads carries its own first_read into the split and into the bootstrap's weights: reads 2^32 - 200 ..
+    2^32 + 199."""
+    import bootstrap_weights_reference as bw
+    from covest_amd import jackknife, sample, simulate as sim
+    from covest_amd.read_bootstrap import bootstrap_histograms
+    first_read = (1 << 32) - 200
+    reads = sim.simulate_reads(sim.random_genome(2000, 5), 50, n_reads=400, error_rate=0.02, seed=5, first_read=first_read)
+    strings = texts(reads.bases)
+    want_full = as_dict(kr.histogram(strings, 9)[0])
+    full, hists, occ = jackknife.leave_group_out_histograms(reads, 9, 4, seed=SEED)
+    group = sample.read_groups(400, 4, SEED, first_read=first_read)
+    assert not np.array_equal(group, sample.read_groups(400, 4, SEED))      # (the groups do depend on the numbering)
+    assert full == want_full and len(hists) == len(occ) == 4
+    for g in range(4):
+        assert hists[g] == as_dict(kr.histogram([t for t, of in zip(strings, group) if of != g], 9)[0]), g
+        assert occ[g] == int((group != g).sum()) * (50 - 9 + 1), g
+    full, hists, occ, drawn = bootstrap_histograms(reads, 9, 3, seed=SEED)
+    assert full == want_full and len(hists) == len(occ) == len(drawn) == 3
+    for b in range(3):
+        w = bw.weights(400, b, SEED, first_read=first_read)
+        assert hists[b] == as_dict(kr.histogram(bw.expand(strings, w), 9)[0]), b
+        assert drawn[b] == int(w.sum()) and occ[b] == drawn[b] * (50 - 9 + 1), b
+
+
 @functools.lru_cache(maxsize=None)
 def fitted():
     """(reads, model, estimate) of the basic model on simulated reads: 50 000-base genome, coverage 10, e = 0.02, k = 15."""

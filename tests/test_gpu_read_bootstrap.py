@@ -317,6 +317,25 @@ def test_bootstrap_histograms_are_the_weighted_truths(hip_lib):
     assert len(set(drawn)) > 1
 
 
+def test_bootstrap_histograms_of_ragged_reads(hip_lib):
+    """Reads of their own lengths (the offsets go up beside the bases), cut as tests/test_gpu_jackknife.py cuts them."""
+    from covest_amd.read_bootstrap import bootstrap_histograms
+    reads = small_reads()
+    lens = np.random.default_rng(8).choice((0, 5, 8, 9, 10, 30, 50), size=400)  # empty reads and reads shorter than k
+    offsets = np.zeros(401, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    bases = np.concatenate([reads.bases[i, :lens[i]] for i in range(400)])
+    blob = bases.tobytes().decode()
+    strings = [blob[offsets[i]:offsets[i + 1]] for i in range(400)]
+    full, hists, occ, drawn = bootstrap_histograms((bases, offsets), 9, 3, seed=E2E_SEED)
+    assert full == as_dict(kr.histogram(strings, 9)[0])
+    assert len(hists) == len(occ) == len(drawn) == 3
+    for b in range(3):
+        w = bw.weights(400, b, E2E_SEED)
+        assert hists[b] == as_dict(kr.histogram(bw.expand(strings, w), 9)[0]), b
+        assert drawn[b] == int(w.sum()) and occ[b] == sum(i * n for i, n in hists[b].items()), b
+
+
 def test_read_bootstrap_end_to_end(hip_lib):
     from covest_amd import print_output
     from covest_amd.read_bootstrap import read_bootstrap
