@@ -37,3 +37,6 @@ from .read_bootstrap import (bootstrap_weights, bootstrap_weights_device, bootst
                              summarize_read_bootstrap, read_bootstrap)
 from . import dedup  # noqa: F401,E402
 from .dedup import dedup_reads, dedup_reads_device, DedupReads  # noqa: F401,E402
+from .simulate import genome_counts  # noqa: F401,E402
+# (covest_amd.copy_spectrum is the FUNCTION too; the module: `from covest_amd.copy_spectrum import ...`)
+from .copy_spectrum import copy_spectrum, CopySpectrum  # noqa: F401,E402

@@ -35,6 +35,7 @@ EXPORTS = (
     "covest_kmer_count_reads_device", "covest_kmer_partition_info", "covest_kmer_partition_ms", "covest_kmer_memory_limit",
     "covest_kmer_scatter_rate", "covest_kmer_lookup_reads", "covest_kmer_lookup_reads_device",
     "covest_kmer_correct_reads", "covest_kmer_correct_reads_device",
+    "covest_kmer_join_histogram", "covest_kmer_join_histogram_device",
     "covest_kmer_read_influence", "covest_kmer_read_influence_device", "covest_rows_moments", "covest_rows_moments_device",
     "covest_reads_open", "covest_reads_close", "covest_reads_next", "covest_reads_bytes",
     "covest_thin_histogram", "covest_thin_histogram_timed",
@@ -221,6 +222,10 @@ def lib():
     L.covest_kmer_lookup_reads_device.argtypes = [vp, vp, vp, i64, i64, ctypes.c_uint32, vp, i32, vp, vp, vp, vp]
     L.covest_kmer_lookup_reads.restype = ctypes.c_int
     L.covest_kmer_lookup_reads.argtypes = [vp, vp, vp, i64, ctypes.c_uint32, vp, i32, vp, vp, vp]
+    L.covest_kmer_join_histogram_device.restype = ctypes.c_int
+    L.covest_kmer_join_histogram_device.argtypes = [vp, vp, i64, i64, vp, vp]
+    L.covest_kmer_join_histogram.restype = ctypes.c_int
+    L.covest_kmer_join_histogram.argtypes = [vp, vp, i64, i64, vp]
     L.covest_kmer_correct_reads_device.restype = ctypes.c_int
     L.covest_kmer_correct_reads_device.argtypes = [vp, vp, vp, i64, i64, ctypes.c_uint32, vp, vp, vp]
     L.covest_kmer_correct_reads.restype = ctypes.c_int

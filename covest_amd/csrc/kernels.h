@@ -224,6 +224,10 @@ hipError_t launch_kmer_rehash(const KmerTable &src, const KmerTable &dst, int *o
 hipError_t launch_kmer_stats(const KmerTable &t, unsigned long long *stats, hipStream_t stream);
 hipError_t launch_kmer_histogram(const KmerTable &t, unsigned long long *hist, unsigned long long hist_len,
                                  hipStream_t stream);
+// kmer_join.hip: out[n_rows][n_cols] (device, zeroed by the call on `stream`) = the keys of a or b by their clipped
+// counts in the two (kmer_join.h, whose cells_ok(n_rows, n_cols) the caller has checked); the tables share their k
+hipError_t launch_kmer_join(const KmerTable &a, const KmerTable &b, int64_t n_rows, int64_t n_cols, int64_t *out,
+                            hipStream_t stream);
 
 // ---- K-kmer, partitioned (kmer_bulk.hip): minimizer buckets of super-k-mer records in HBM, counted in LDS ----
 struct KmerBulk {

@@ -1,6 +1,7 @@
 // kmer_table.h -- the open-addressing k-mer table of K-kmer (k <= 31) as device functions: shared by
 // kmer_count.hip (every occurrence goes to the table), kmer_bulk.hip (only what its LDS path hands back does), and
-// kmer_lookup.hip, kmer_correct.hip and kmer_influence.hip (which only read it: table_find; a wave a read: wave_read.h).
+// kmer_lookup.hip, kmer_correct.hip and kmer_influence.hip (which only read it: table_find; a wave a read: wave_read.h),
+// and kmer_join.hip (which reads two: every key of one table looked up in the other).
 // See kmer_count.hip for the reference it restates and for why a key's first slot is a function of its minimizer.
 // The arithmetic on the codes themselves: kmer_codes.h.
 #pragma once

@@ -467,6 +467,33 @@ class KmerCounts:
             ctypes.c_void_p(stream or 0)), "covest_kmer_read_influence_device")
         return self
 
+    def join_histogram(self, other, rows, cols):
+        """This counter joined with `other` (a KmerCounts of the same k, canonical flag and device; k <= 31) on their
+        keys (covest_kmer_join_histogram; read-only on both) -> int64 (rows, cols): entry [i][j] is the number of keys
+        held by at least one of the two whose count here, clipped to rows - 1, is i and whose count in `other`, clipped
+        to cols - 1, is j.  Row 0: the keys of `other` alone; column 0: the keys of this counter alone.  rows * cols is
+        at most 2^22.  Integer counts: the same result on every run (covest_amd.copy_spectrum)."""
+        rows, cols = int(rows), int(cols)
+        if not isinstance(other, KmerCounts):
+            raise TypeError("join_histogram joins two KmerCounts")
+        out = np.zeros((rows, cols) if rows >= 1 and cols >= 1 and rows * cols <= 1 << 22 else (1, 1), dtype=np.int64)
+        _capi.check(_capi.lib().covest_kmer_join_histogram(
+            self._handle, other._handle, rows, cols, ctypes.c_void_p(out.ctypes.data)), "covest_kmer_join_histogram")
+        return out
+
+    def join_histogram_device(self, other, rows, cols, d_out_ptr, stream=None):
+        """The same into a device array (raw pointer; covest_kmer_join_histogram_device): asynchronous on `stream`,
+        which must be the stream of the adds into BOTH counters that it is to see (or ordered after them by the
+        caller).  `d_out_ptr`: int64[rows][cols], aligned to 8 bytes; the call zeroes it on `stream` first.  It does
+        not look at an overflow flag."""
+        if not isinstance(other, KmerCounts):
+            raise TypeError("join_histogram_device joins two KmerCounts")
+        _capi.require_shared_runtime("KmerCounts.join_histogram_device")
+        _capi.check(_capi.lib().covest_kmer_join_histogram_device(
+            self._handle, other._handle, int(rows), int(cols), ctypes.c_void_p(d_out_ptr or 0),
+            ctypes.c_void_p(stream or 0)), "covest_kmer_join_histogram_device")
+        return self
+
     def memory_limit(self, max_bytes):
         """Bytes the partitioned path may allocate for its buckets' records (0: no cap but the free device memory); a
         count_reads_device that would pass it takes the table path instead (covest_kmer_memory_limit)."""

@@ -28,7 +28,7 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
                  reads_size=None, silent=False, orig_sample_factor=1, starting_points=1,
                  use_grid_search=False, intervals=None, information=None, bootstrap=None, jackknife=None,
                  posterior=None, read_errors=None, corrections=None, read_influence=None, read_bootstrap=None,
-                 duplicates=None):
+                 duplicates=None, copy_spectrum=None):
     """`intervals`: the dict covest_amd.profile.coverage_interval returns; the record then carries the likelihood-ratio
     interval of the coverage, of the genome size and its level.  Without it the record is the reference's, key for key.
     `information`: the dict covest_amd.information.observed_information returns (a key 'level' in it chooses the Wald
@@ -77,7 +77,13 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
     to rely on.  Without it the record is unchanged.
     `duplicates`: the DedupReads covest_amd.dedup.dedup_reads returns; the record then carries duplicates_reads (the
     reads that went in), duplicates_kept, duplicates_share (the share that was dropped) and duplicates_max_copies
-    (DESIGN.md 6al).  Without it the record is unchanged."""
+    (DESIGN.md 6al).  Without it the record is unchanged.
+    `copy_spectrum`: the CopySpectrum covest_amd.copy_spectrum.copy_spectrum returns -- the truth, where the genome is
+    known; the record then carries one copy_spectrum_* per entry of its observed_kmers() (the columns of `posterior`
+    where that is given, four otherwise), named like their posterior_* counterparts, copy_spectrum_error_cutoff (the
+    measured cutoff at level 0.5; the model's is posterior_error_cutoff) and copy_spectrum_q1, _q2, _q
+    (spectrum_to_q of its genome_spectrum()).  They compare with the posterior_* fields only where the model was fitted
+    to the histogram of the joined counts with no sample factor.  Without it the record is unchanged."""
     def named(names, values):
         """{name: value} without the None entries; the coverage (first entry) is reported for the
         un-sampled data, i.e. times sample_factor."""
@@ -220,6 +226,15 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
         record['duplicates_kept'] = int(duplicates.n_reads)
         record['duplicates_share'] = float(duplicates.duplicate_share)
         record['duplicates_max_copies'] = int(duplicates.copies.max()) if duplicates.n_reads else 0
+    if copy_spectrum is not None:
+        from .simulate import spectrum_to_q
+        columns = 4 if posterior is None else posterior.copy_share.shape[1]
+        for name, value in copy_spectrum.observed_kmers(columns).items():
+            record['copy_spectrum_%s%s' % (name, '' if name.startswith('copies_') else '_kmers')] = int(value)
+        cutoff = copy_spectrum.error_cutoff()
+        record['copy_spectrum_error_cutoff'] = None if cutoff is None else int(cutoff)
+        for name, value in zip(('q1', 'q2', 'q'), spectrum_to_q(copy_spectrum.genome_spectrum())):
+            record['copy_spectrum_' + name] = None if value is None else float(value)
     if not silent:
         print(yaml.dump(record, indent=4, default_flow_style=False))
     return record

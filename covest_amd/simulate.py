@@ -318,29 +318,50 @@ def genome_spectrum(genome, k, canonical=False, device=-1):
     taken together if `canonical`), counted on the device with KmerCounts.  The genome (a RepeatGenome, str, bytes or
     uint8 array of a/c/g/t) is handed over as overlapping windows of up to 65 536 + k - 1 bases, a window a read, so
     every k-mer start falls in exactly one window."""
-    from .kmer_hist import KmerCounts
+    g, k = _spectrum_genome(genome, k)
+    if g.size - k + 1 <= 0:
+        return {}
+    counts = genome_counts(g, k, canonical=canonical, device=device)
+    try:
+        hist = counts.histogram()
+    finally:
+        counts.close()
+    return {o: int(v) for o, v in enumerate(hist) if o > 0 and v > 0}
+
+
+def _spectrum_genome(genome, k):
     g = genome.bases if isinstance(genome, RepeatGenome) else _genome_bytes(genome)
     k = int(k)
     if k < 1:
         raise ValueError("k must be at least 1")
     if g.size and not _VALID[g].all():
         raise ValueError("genome byte outside acgtACGT")
+    return g, k
+
+
+def genome_counts(genome, k, canonical=False, device=-1):
+    """The table genome_spectrum counts and closes, left open: a KmerCounts that holds every k-mer of the genome with
+    the number of its copies -- the other side of KmerCounts.join_histogram and of covest_amd.copy_spectrum.  The same
+    overlapping windows of up to 65 536 + k - 1 bases, a window a read; a genome shorter than k gives an empty counter.
+    The caller closes it."""
+    from .kmer_hist import KmerCounts
+    g, k = _spectrum_genome(genome, k)
+    counts = KmerCounts(k, canonical=canonical, device=device)
     n_starts = g.size - k + 1
     if n_starts <= 0:
-        return {}
+        return counts
     starts = np.arange(0, n_starts, _SPECTRUM_WINDOW, dtype=np.int64)
     lens = np.minimum(_SPECTRUM_WINDOW, n_starts - starts) + (k - 1)  # every window holds a k-mer
     offsets = np.zeros(starts.size + 1, dtype=np.int64)
     np.cumsum(lens, out=offsets[1:])
     blob = np.concatenate([g[a:a + m] for a, m in zip(starts.tolist(), lens.tolist())])
-    counts = KmerCounts(k, canonical=canonical, device=device)
     try:
         counts.add_packed(blob.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                           offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), starts.size, blob.size)
-        hist = counts.histogram()
-    finally:
+    except Exception:
         counts.close()
-    return {o: int(v) for o, v in enumerate(hist) if o > 0 and v > 0}
+        raise
+    return counts
 
 
 def spectrum_to_q(spectrum):

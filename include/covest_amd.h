@@ -494,6 +494,30 @@ int covest_kmer_read_influence_device(covest_kmer *c, const uint8_t *d_bases, co
                                       double *d_rows, void *stream);
 int covest_kmer_read_influence(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
                                const double *table, int64_t n_rows, int32_t n_cols, double *rows);
+/* Two counters joined on their keys (k <= 31 on both sides, the same k, canonical flag and device; no reference
+ * counterpart; read-only on both tables).  With a(x) the count counter `a` holds for key x (0:
+ * it holds none), b(x) the same for `b`, and U the keys held by at least one of the two,
+ *   out[i][j] = #{ x in U : min(a(x), n_rows - 1) == i  and  min(b(x), n_cols - 1) == j },
+ * int64, row-major, n_rows * n_cols entries: the last row and the last column take every count from n_rows - 1, n_cols - 1
+ * on.  Row 0 holds the keys of `b` alone, column 0 those of `a` alone; out[0][0] is 0 (n_rows, n_cols >= 2).  The sum of all entries is the
+ * number of keys in U, the sums of rows i >= 1 are the clipped covest_kmer_histogram of `a`, those of columns j >= 1
+ * that of `b`.  The two tables may be of different sizes; either may be empty.  The key covest_kmer_add counts for a
+ * read shorter than k is a key like any other.  The counts are integers: the same result on every run.
+ * Device form: asynchronous on `stream`; d_out aligned to 8 bytes and ZEROED BY THE CALL on `stream` before anything is
+ * counted (it may hold anything); nothing outside its n_rows * n_cols entries is written.  The call must be ORDERED
+ * AFTER the adds into BOTH counters that it is to see -- the same stream, or the caller's own synchronisation -- and
+ * never looks at an overflow flag.
+ * Host form: waits for the device, joins, waits, and answers COVEST_E_NOMEM if an add into either counter overflowed
+ * (sticky until that counter's covest_kmer_clear: the counts are then partial); then copies the matrix to `out`.
+ * Both counters' locks are held for the call, taken together: a join of (a, b) on one thread and of (b, a) on another
+ * cannot wait for each other.
+ * COVEST_E_UNSUPPORTED: k > 31 on either side.  COVEST_E_INVALID: a null counter, the same counter twice, counters
+ * that differ in k, in the canonical flag or in their device, n_rows < 1, n_cols < 1, n_rows * n_cols > 2^22, a null
+ * output, a d_out that is not aligned to 8 bytes, or a counter that holds a covest_kmer_count_reads_device result (its
+ * keys are not in the table). */
+int covest_kmer_join_histogram_device(covest_kmer *a, covest_kmer *b, int64_t n_rows, int64_t n_cols, int64_t *d_out,
+                                      void *stream);
+int covest_kmer_join_histogram(covest_kmer *a, covest_kmer *b, int64_t n_rows, int64_t n_cols, int64_t *out);
 /* The first two moments of n rows of q doubles about `centre` (1 <= q <= 9), with d_r = rows[r] - centre:
  *   sum[k] = sum_r d_r[k];   cross[k q - k (k - 1) / 2 + (l - k)] = sum_r d_r[k] d_r[l] for k <= l
  * (the packed upper triangle, row by row: q (q + 1) / 2 entries).  No floating-point atomic: the shape of the reduction
