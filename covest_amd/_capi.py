@@ -36,6 +36,8 @@ EXPORTS = (
     "covest_kmer_scatter_rate", "covest_kmer_lookup_reads", "covest_kmer_lookup_reads_device",
     "covest_kmer_correct_reads", "covest_kmer_correct_reads_device",
     "covest_kmer_join_histogram", "covest_kmer_join_histogram_device",
+    "covest_kmer_remove", "covest_kmer_remove_device", "covest_kmer_remove_weighted", "covest_kmer_remove_weighted_device",
+    "covest_kmer_occupancy", "covest_kmer_compact",
     "covest_kmer_read_influence", "covest_kmer_read_influence_device", "covest_rows_moments", "covest_rows_moments_device",
     "covest_reads_open", "covest_reads_close", "covest_reads_next", "covest_reads_bytes",
     "covest_thin_histogram", "covest_thin_histogram_timed",
@@ -202,6 +204,18 @@ def lib():
     L.covest_kmer_add_weighted.argtypes = [vp, vp, vp, i64, vp]
     L.covest_kmer_add_weighted_device.restype = ctypes.c_int
     L.covest_kmer_add_weighted_device.argtypes = [vp, vp, vp, i64, i64, vp, vp]
+    L.covest_kmer_remove.restype = ctypes.c_int
+    L.covest_kmer_remove.argtypes = [vp, vp, vp, i64]
+    L.covest_kmer_remove_device.restype = ctypes.c_int
+    L.covest_kmer_remove_device.argtypes = [vp, vp, vp, i64, i64, vp]
+    L.covest_kmer_remove_weighted.restype = ctypes.c_int
+    L.covest_kmer_remove_weighted.argtypes = [vp, vp, vp, i64, vp]
+    L.covest_kmer_remove_weighted_device.restype = ctypes.c_int
+    L.covest_kmer_remove_weighted_device.argtypes = [vp, vp, vp, i64, i64, vp, vp]
+    L.covest_kmer_occupancy.restype = ctypes.c_int
+    L.covest_kmer_occupancy.argtypes = [vp, i64p]
+    L.covest_kmer_compact.restype = ctypes.c_int
+    L.covest_kmer_compact.argtypes = [vp]
     L.covest_kmer_count_reads_device.restype = ctypes.c_int
     L.covest_kmer_count_reads_device.argtypes = [vp, vp, vp, i64, i64, i64, vp]
     L.covest_kmer_partition_info.restype = ctypes.c_int

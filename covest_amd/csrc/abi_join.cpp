@@ -32,9 +32,9 @@ int check_join(const std::string &name, const covest_kmer *a, const covest_kmer 
     return fail_if(check_table_holds_keys(name, 0, a->bulk || b->bulk));
 }
 
-int read_flag(const covest_kmer *c, int *flag)
+int read_flag(const covest_kmer *c, int *flag) // flag[kKmerStickyWords]: the overflow word and the underflow word
 {
-    HIP_TRY(hipMemcpy(flag, c->flag.ptr, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flag, c->flag.ptr, kKmerStickyWords * sizeof(int), hipMemcpyDeviceToHost));
     return COVEST_OK;
 }
 
@@ -69,12 +69,14 @@ int covest_kmer_join_histogram(covest_kmer *a, covest_kmer *b, int64_t n_rows, i
     HIP_TRY(hipDeviceSynchronize()); // the adds may run on a caller's non-blocking stream, the join on the null stream
     HIP_TRY(launch_kmer_join(a->table, b->table, n_rows, n_cols, d_out.as<int64_t>(), nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    int flag_a = 0, flag_b = 0;
-    COVEST_TRY(read_flag(a, &flag_a));
-    COVEST_TRY(read_flag(b, &flag_b));
-    if (flag_a || flag_b)
+    int flag_a[kKmerStickyWords] = {0, 0}, flag_b[kKmerStickyWords] = {0, 0};
+    COVEST_TRY(read_flag(a, flag_a));
+    COVEST_TRY(read_flag(b, flag_b));
+    if (flag_a[kKmerOverflowWord] || flag_b[kKmerOverflowWord])
         return fail(COVEST_E_NOMEM, name + ": k-mer table overflow, the counts are partial: covest_kmer_clear and recount "
                                            "with more slots");
+    if (flag_a[kKmerUnderflowWord] || flag_b[kKmerUnderflowWord])
+        return fail(COVEST_E_INVALID, kmer_underflow_text(name.c_str()));
     HIP_TRY(hipMemcpy(out, d_out.ptr, bytes, hipMemcpyDeviceToHost));
     return COVEST_OK;
 }

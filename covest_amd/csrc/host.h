@@ -377,10 +377,15 @@ struct covest_kmer {
     KmerWideTable wtable{};
     KmerTable table{};
     DevBuf slots, flag, stats, hist, ws_bases, ws_offsets, ws_weights; // (ws_weights: covest_kmer_add_weighted's)
+    // flag: kKmerStickyWords ints, sticky until covest_kmer_clear -- the adds' overflow and the removals' underflow, a
+    // word each so that neither erases the other; stats: kKmerStatsWords words {max count, keys held, slots occupied}
     bool bulk = false; // the counter holds the result of covest_kmer_count_reads_device (until covest_kmer_clear)
     BulkState part;
     std::mutex lock;
 };
+
+constexpr int kKmerOverflowWord = 0, kKmerUnderflowWord = 1, kKmerStickyWords = 2; // of covest_kmer::flag
+constexpr int kKmerStatsWords = 3;                                                   // of covest_kmer::stats
 
 constexpr unsigned long long kBulkHistLen = 1ull << 20; // dense count-of-counts bins of the partitioned path
 constexpr unsigned long long kBulkBigCap = 4096;        // counts beyond them, listed one by one
@@ -408,6 +413,12 @@ int64_t launch_record_text(const LaunchRecord &r, char *buf, int64_t cap); // (k
 // recursive); close(), of the forms that only read the table, waits for the device and reads the sticky overflow flag
 // (set: COVEST_E_NOMEM, the counts `reader` saw are partial; the add words its own); the caller copies back.  The lock is
 // held until the object goes away: no other thread stages into ws_bases / ws_offsets under a kernel or that copy back.
+// close() and kmer_check_overflow read both sticky words, the overflow first (COVEST_E_NOMEM, as ever), then the underflow
+// of a removal (COVEST_E_INVALID, kmer_underflow_text: "underflow" and `who`, the call's name).
+int kmer_check_overflow(covest_kmer *c, const char *who); // (after the caller has waited for the device)
+std::string kmer_underflow_text(const char *who);
+int kmer_check_weights(const char *who, const uint32_t *weights, int64_t n_reads); // a weight a read (the weighted forms)
+int kmer_rehash_locked(covest_kmer *c, int64_t min_slots, const char *who);        // (kmer_host.cpp; the lock is held)
 class KmerHostCall {
   public:
     explicit KmerHostCall(covest_kmer *c) : c(c), lock_(c->lock), dev_(c->device) {}

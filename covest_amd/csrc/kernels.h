@@ -220,6 +220,13 @@ hipError_t launch_kmer_fill_empty(const KmerTable &t, hipStream_t stream);
 hipError_t launch_kmer_count(const unsigned char *bases, const int64_t *offsets, int64_t n_reads,
                              int64_t fixed_len, int k, int canonical, const KmerTable &t, int *overflow,
                              hipStream_t stream, const uint32_t *weights = nullptr);
+// kmer_remove.hip: launch_kmer_count's inverse on the same arguments -- every occurrence of read r is taken out once, or
+// weights[r] times; no key is created or cleared.  *underflow (a word of its own, not the overflow word) is set to 1 where
+// a key occupies no slot or its count was smaller than what was subtracted.
+hipError_t launch_kmer_remove(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t fixed_len, int k,
+                              int canonical, const KmerTable &t, int *underflow, hipStream_t stream,
+                              const uint32_t *weights = nullptr);
+// rehash: the keys HELD by src (kmer_table.h) into dst; stats: {max count, keys held, slots occupied}
 hipError_t launch_kmer_rehash(const KmerTable &src, const KmerTable &dst, int *overflow, hipStream_t stream);
 hipError_t launch_kmer_stats(const KmerTable &t, unsigned long long *stats, hipStream_t stream);
 hipError_t launch_kmer_histogram(const KmerTable &t, unsigned long long *hist, unsigned long long hist_len,

@@ -129,14 +129,15 @@ __global__ __launch_bounds__(256) void kmer_count_fixed_weighted_kernel(const un
     count_numbered_window<true>(bases, n_reads, len, k, canonical, t, overflow, weights);
 }
 
-// Re-insert every entry of `src` into the (larger) `dst` table.
+// Re-insert every HELD key of `src` (kmer_table.h) into the `dst` table -- a larger one, or one of the same size
+// (covest_kmer_compact): a key whose count a removal brought to 0 does not travel.
 __global__ __launch_bounds__(256) void kmer_rehash_kernel(const KmerTable src, const KmerTable dst, int *overflow)
 {
     const unsigned long long n = src.mask + 1;
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (unsigned long long)gridDim.x * blockDim.x) {
         const KmerSlot e = src.slots[i];
-        if (e.key != kEmptyKey)
+        if (slot_held(e.key, e.count))
             table_add(dst, e.key, revcomp_code(e.key, dst.k), e.count, overflow);
     }
 }
@@ -148,23 +149,43 @@ __global__ __launch_bounds__(256) void kmer_fill_empty_kernel(KmerSlot *slots, u
         slots[i] = KmerSlot{kEmptyKey, 0ull}; // one 16-byte store per lane: coalesced streaming write
 }
 
-// stats[0] = max count, stats[1] = distinct keys
+// stats[0] = max count, stats[1] = distinct keys: the keys HELD (kmer_table.h), stats[2] = the slots occupied
 __global__ __launch_bounds__(256) void kmer_stats_kernel(const KmerTable t, unsigned long long *stats)
 {
     const unsigned long long n = t.mask + 1;
-    unsigned long long distinct = 0, mx = 0;
+    unsigned long long distinct = 0, mx = 0, occupied = 0;
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (unsigned long long)gridDim.x * blockDim.x) {
         const KmerSlot e = t.slots[i];
-        if (e.key != kEmptyKey) {
-            ++distinct;
-            mx = e.count > mx ? e.count : mx;
+        if (slot_occupied(e.key)) {
+            ++occupied;
+            distinct += slot_held(e.key, e.count) ? 1ull : 0ull;
+            mx = e.count > mx ? e.count : mx; // (a count of 0 raises no maximum)
         }
     }
     wave_fold_distinct_max(distinct, mx);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+        occupied += __shfl_xor(occupied, off, kWave);
+    // The three words share a line, and every atomic on it queues behind the others: a workgroup folds its four waves in
+    // LDS first and sends three atomics, where a wave each sending its own would be twelve (the parent's kernel sent eight).
+    __shared__ unsigned long long part[3][256 / kWave];
+    const int wave = threadIdx.x / kWave;
     if ((threadIdx.x & (kWave - 1)) == 0) {
+        part[0][wave] = mx;
+        part[1][wave] = distinct;
+        part[2][wave] = occupied;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 256 / kWave; ++w) {
+            mx = part[0][w] > mx ? part[0][w] : mx;
+            distinct += part[1][w];
+            occupied += part[2][w];
+        }
         atomicMax(&stats[0], mx);
         atomicAdd(&stats[1], distinct);
+        atomicAdd(&stats[2], occupied);
     }
 }
 
@@ -182,7 +203,7 @@ __global__ __launch_bounds__(256) void kmer_histogram_kernel(const KmerTable t, 
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (unsigned long long)gridDim.x * blockDim.x) {
         const KmerSlot e = t.slots[i];
-        if (e.key != kEmptyKey) {
+        if (slot_held(e.key, e.count)) { // (a key of count 0 is not counted: hist[0] stays 0)
             const unsigned long long c = e.count;
             if (c < (unsigned long long)kLdsBins)
                 atomicAdd(&bins[c], 1u);

@@ -61,15 +61,6 @@ hipError_t table_scan(const covest_kmer *c, unsigned long long need)
                    : launch_kmer_histogram(c->table, hist, need, nullptr);
 }
 
-int kmer_check_overflow(covest_kmer *c)
-{
-    int flag = 0;
-    HIP_TRY(hipMemcpy(&flag, c->flag.ptr, sizeof(int), hipMemcpyDeviceToHost));
-    if (flag)
-        return fail(COVEST_E_NOMEM, "k-mer table overflow: call covest_kmer_reserve with more slots");
-    return COVEST_OK;
-}
-
 // ---- covest_kmer_count_reads_device, stage by stage -----------------------------------------------------
 // One call: the reads as the layout stage left them, the plan, the device blocks, what the passes reported.
 struct BulkCall {
@@ -285,7 +276,7 @@ int hand_back(BulkCall &b)
     HIP_TRY(launch_kmer_to_table(b.p, b.n_overflowed > 0, c->table, c->flag.as<int>(), b.lists->to_table,
                                  b.lists->to_table_list(b.n_buckets), b.st));
     HIP_TRY(hipStreamSynchronize(b.st));
-    return kmer_check_overflow(c);
+    return kmer_check_overflow(c, "covest_kmer_count_reads_device");
 }
 
 // the passes' times, what covest_kmer_partition_info reports; the counter holds the result from here on
@@ -325,13 +316,75 @@ int KmerHostCall::open(const uint8_t *bases, const int64_t *offsets, int64_t n_r
     return COVEST_OK;
 }
 
+// the two sticky words (host.h), the overflow first: an overflow set before an underflow is still reported
+int kmer_check_overflow(covest_kmer *c, const char *who)
+{
+    int flag[kKmerStickyWords] = {0, 0};
+    HIP_TRY(hipMemcpy(flag, c->flag.ptr, sizeof(flag), hipMemcpyDeviceToHost));
+    if (flag[kKmerOverflowWord])
+        return fail(COVEST_E_NOMEM, "k-mer table overflow: call covest_kmer_reserve with more slots");
+    if (flag[kKmerUnderflowWord])
+        return fail(COVEST_E_INVALID, kmer_underflow_text(who));
+    return COVEST_OK;
+}
+
 int KmerHostCall::close(const char *reader)
 {
     HIP_TRY(hipDeviceSynchronize());
-    int flag = 0;
-    HIP_TRY(hipMemcpy(&flag, c->flag.ptr, sizeof(int), hipMemcpyDeviceToHost));
-    return !flag ? COVEST_OK : fail(COVEST_E_NOMEM, std::string(reader) + ": k-mer table overflow, the counts are partial: "
-                                                                          "covest_kmer_clear and recount with more slots");
+    int flag[kKmerStickyWords] = {0, 0};
+    HIP_TRY(hipMemcpy(flag, c->flag.ptr, sizeof(flag), hipMemcpyDeviceToHost));
+    if (flag[kKmerOverflowWord])
+        return fail(COVEST_E_NOMEM, std::string(reader) + ": k-mer table overflow, the counts are partial: "
+                                                          "covest_kmer_clear and recount with more slots");
+    return !flag[kKmerUnderflowWord] ? COVEST_OK : fail(COVEST_E_INVALID, kmer_underflow_text(reader));
+}
+
+std::string kmer_underflow_text(const char *who)
+{
+    return std::string(who) + ": k-mer table underflow, a removal took out more than the table held and the counts are "
+                              "unspecified: covest_kmer_clear and recount";
+}
+
+// a weight a read: there with the reads, and where a uint32 can lie
+int kmer_check_weights(const char *who, const uint32_t *weights, int64_t n_reads)
+{
+    if (n_reads > 0 && !weights)
+        return fail(COVEST_E_INVALID, std::string(who) + ": null weights");
+    if (reinterpret_cast<uintptr_t>(weights) % alignof(uint32_t) != 0)
+        return fail(COVEST_E_INVALID, std::string(who) + ": the weights must be aligned to 4 bytes");
+    return COVEST_OK;
+}
+
+// covest_kmer_reserve's rehash (into a table of more slots) and covest_kmer_compact's (abi_remove.cpp: into one of as
+// many): a fresh table of at least min_slots slots takes the counter's place; the keys HELD travel, by table_add, keys whose count
+// a removal brought to 0 stay behind (kmer_table.h).  The counter's lock is held and its device is current.
+int kmer_rehash_locked(covest_kmer *c, int64_t min_slots, const char *who)
+{
+    // An overflow of an earlier covest_kmer_add_device (asynchronous: it never looks at the flag itself) is STICKY
+    // until covest_kmer_clear: its batch is partly counted, and a rehash of a table with k-mers missing must not make
+    // the next covest_kmer_histogram look clean; an underflow of a removal likewise.  So: everything in flight on this
+    // device first (the adds may run on a caller's non-blocking stream, the rehash runs on the null stream), then the
+    // flags.
+    HIP_TRY(hipDeviceSynchronize());
+    COVEST_TRY(kmer_check_overflow(c, who));
+    KmerTable bigger{};
+    KmerWideTable wbigger{};
+    DevBuf slots;
+    int rc = table_alloc(c, min_slots, bigger, wbigger, slots);
+    hipError_t e = hipSuccess;
+    if (rc == COVEST_OK) { // (the flags are known to be clean here: whatever they hold afterwards is the rehash's)
+        e = table_rehash(c, bigger, wbigger);
+        if (e == hipSuccess)
+            e = hipDeviceSynchronize();
+        if (e != hipSuccess)
+            rc = fail_hip(e, (std::string(who) + ": rehash").c_str());
+    }
+    if (rc != COVEST_OK)
+        return rc; // (the new table goes with `slots`)
+    c->slots = std::move(slots);
+    c->table = bigger;
+    c->wtable = wbigger;
+    return kmer_check_overflow(c, who);
 }
 
 } // namespace covest
@@ -363,11 +416,11 @@ int covest_kmer_create(int32_t k, int32_t canonical, int64_t min_slots, int32_t 
     if (rc == COVEST_OK)
         rc = table_alloc(c, min_slots, c->table, c->wtable, c->slots);
     if (rc == COVEST_OK) {
-        e = c->flag.reserve(sizeof(int));
+        e = c->flag.reserve(kKmerStickyWords * sizeof(int));
         if (e == hipSuccess)
-            e = hipMemset(c->flag.ptr, 0, sizeof(int));
+            e = hipMemset(c->flag.ptr, 0, kKmerStickyWords * sizeof(int));
         if (e == hipSuccess)
-            e = c->stats.reserve(2 * sizeof(unsigned long long));
+            e = c->stats.reserve(kKmerStatsWords * sizeof(unsigned long long));
         if (e != hipSuccess)
             rc = fail_hip(e, "covest_kmer_create: allocation");
     }
@@ -407,7 +460,7 @@ int covest_kmer_clear(covest_kmer *c, void *stream)
     if (dev_guard.status() != COVEST_OK)
         return dev_guard.status();
     HIP_TRY(table_clear(c, static_cast<hipStream_t>(stream)));
-    HIP_TRY(hipMemsetAsync(c->flag.ptr, 0, sizeof(int), static_cast<hipStream_t>(stream)));
+    HIP_TRY(hipMemsetAsync(c->flag.ptr, 0, kKmerStickyWords * sizeof(int), static_cast<hipStream_t>(stream)));
     // what the partitioned path kept for its next call -- the buckets' records are gigabytes -- goes with the counts,
     // whether its last call succeeded or not (a call that failed after its reserve left `bulk` false and the records
     // allocated: the table path the caller falls back to needs that memory).  covest_kmer_count_reads_device has
@@ -439,34 +492,7 @@ int covest_kmer_reserve(covest_kmer *c, int64_t min_slots)
     DeviceGuard dev_guard(c->device);
     if (dev_guard.status() != COVEST_OK)
         return dev_guard.status();
-    // An overflow of an earlier covest_kmer_add_device (asynchronous: it never looks at the flag itself) is STICKY
-    // until covest_kmer_clear: its batch is partly counted, and a rehash of a table with k-mers missing must not make
-    // the next covest_kmer_histogram look clean.  So: everything in flight on this device first (the adds may run
-    // on a caller's non-blocking stream, the rehash runs on the null stream), then the flag.
-    HIP_TRY(hipDeviceSynchronize());
-    {
-        const int rc = kmer_check_overflow(c);
-        if (rc != COVEST_OK)
-            return rc;
-    }
-    KmerTable bigger{};
-    KmerWideTable wbigger{};
-    DevBuf slots;
-    int rc = table_alloc(c, min_slots, bigger, wbigger, slots);
-    hipError_t e = hipSuccess;
-    if (rc == COVEST_OK) { // (the flag is known to be clean here: whatever it holds afterwards is the rehash's)
-        e = table_rehash(c, bigger, wbigger);
-        if (e == hipSuccess)
-            e = hipDeviceSynchronize();
-        if (e != hipSuccess)
-            rc = fail_hip(e, "covest_kmer_reserve: rehash");
-    }
-    if (rc != COVEST_OK)
-        return rc; // (the new table goes with `slots`)
-    c->slots = std::move(slots);
-    c->table = bigger;
-    c->wtable = wbigger;
-    return kmer_check_overflow(c);
+    return kmer_rehash_locked(c, min_slots, "covest_kmer_reserve");
 }
 
 // covest_kmer_add_device (d_weights null) and covest_kmer_add_weighted_device with the counter's lock held (the host
@@ -478,16 +504,6 @@ static int add_device_locked(const char *who, covest_kmer *c, const uint8_t *d_b
     DeviceGuard dev_guard(c->device);
     COVEST_TRY(dev_guard.status());
     HIP_TRY(table_count(c, d_bases, d_offsets, n_reads, read_len, d_weights, static_cast<hipStream_t>(stream)));
-    return COVEST_OK;
-}
-
-// a weight a read: there with the reads, and where a uint32 can lie
-static int check_weights(const char *who, const uint32_t *weights, int64_t n_reads)
-{
-    if (n_reads > 0 && !weights)
-        return fail(COVEST_E_INVALID, std::string(who) + ": null weights");
-    if (reinterpret_cast<uintptr_t>(weights) % alignof(uint32_t) != 0)
-        return fail(COVEST_E_INVALID, std::string(who) + ": the weights must be aligned to 4 bytes");
     return COVEST_OK;
 }
 
@@ -505,7 +521,7 @@ int covest_kmer_add_weighted_device(covest_kmer *c, const uint8_t *d_bases, cons
 {
     if (!c || n_reads < 0 || (n_reads > 0 && !d_bases) || (!d_offsets && read_len < 0))
         return fail(COVEST_E_INVALID, "covest_kmer_add_weighted_device: bad argument");
-    COVEST_TRY(check_weights("covest_kmer_add_weighted_device", d_weights, n_reads));
+    COVEST_TRY(kmer_check_weights("covest_kmer_add_weighted_device", d_weights, n_reads));
     std::lock_guard<std::mutex> guard(c->lock);
     return add_device_locked("covest_kmer_add_weighted_device", c, d_bases, d_offsets, n_reads, read_len, d_weights, stream);
 }
@@ -524,7 +540,7 @@ int covest_kmer_add(covest_kmer *c, const uint8_t *bases, const int64_t *offsets
     COVEST_TRY(add_device_locked("covest_kmer_add_device", c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(), n_reads,
                                  0, nullptr, nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    return kmer_check_overflow(c); // (the add's own words, not close()'s: the batch is partly counted, the table can grow)
+    return kmer_check_overflow(c, "covest_kmer_add"); // (the add's own words, not close()'s: the batch is partly counted, the table can grow)
 }
 
 int covest_kmer_add_weighted(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
@@ -532,7 +548,7 @@ int covest_kmer_add_weighted(covest_kmer *c, const uint8_t *bases, const int64_t
 {
     if (!c || n_reads < 0 || (n_reads > 0 && !offsets))
         return fail(COVEST_E_INVALID, "covest_kmer_add_weighted: bad argument");
-    COVEST_TRY(check_weights("covest_kmer_add_weighted", weights, n_reads));
+    COVEST_TRY(kmer_check_weights("covest_kmer_add_weighted", weights, n_reads));
     if (n_reads == 0)
         return COVEST_OK;
     const int64_t n_bytes = offsets[n_reads] - offsets[0];
@@ -545,7 +561,7 @@ int covest_kmer_add_weighted(covest_kmer *c, const uint8_t *bases, const int64_t
     COVEST_TRY(add_device_locked("covest_kmer_add_weighted_device", c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(),
                                  n_reads, 0, c->ws_weights.as<uint32_t>(), nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    return kmer_check_overflow(c); // (as covest_kmer_add: the batch is partly counted, the table can grow)
+    return kmer_check_overflow(c, "covest_kmer_add_weighted"); // (as covest_kmer_add: the batch is partly counted, the table can grow)
 }
 
 int covest_kmer_histogram(covest_kmer *c, int64_t *out, int64_t out_len, int64_t *needed_len,
@@ -558,10 +574,10 @@ int covest_kmer_histogram(covest_kmer *c, int64_t *out, int64_t out_len, int64_t
     if (dev_guard.status() != COVEST_OK)
         return dev_guard.status();
     HIP_TRY(hipDeviceSynchronize());
-    int rc = kmer_check_overflow(c);
+    int rc = kmer_check_overflow(c, "covest_kmer_histogram");
     if (rc != COVEST_OK)
         return rc;
-    unsigned long long stats[2] = {0, 0};
+    unsigned long long stats[kKmerStatsWords] = {0, 0, 0}; // (max count, keys held; the slots occupied: abi_remove.cpp)
     const bool table_in_use = !c->bulk || c->part.table_used; // (a partitioned count may leave nothing in the table)
     if (table_in_use) {
         HIP_TRY(hipMemset(c->stats.ptr, 0, sizeof(stats)));

@@ -7,7 +7,9 @@
 //      kmer_rehash_kernel derives it -- and counts into cell (clip a, clip b);
 //   2. over B's slots: a held key probes A and counts into row 0 only when A holds none.
 // A key of both tables is met in both sweeps and counted in the first alone; a key of one table is met once: no key is
-// counted twice and none is missed.  Each table is walked and probed with its own log2_slots (first_slot, slot_of);
+// counted twice and none is missed.  Held is kmer_table.h's: a slot whose count a removal (kmer_remove.hip) brought to 0
+// is passed over in both sweeps, and table_find answers 0 for it, so a key held by neither table is in no cell and cell
+// (0, 0) stays 0.  Each table is walked and probed with its own log2_slots (first_slot, slot_of);
 // has_first_slot is a function of k and of the probed table's size.
 //
 // The cells i < kLdsRows, j < kLdsCols are counted in workgroup-private bins in LDS and flushed once per workgroup; the
@@ -48,13 +50,13 @@ __global__ __launch_bounds__(256) void kmer_join_kernel(const KmerTable a, const
     const unsigned long long n_a = a.mask + 1, n_b = b.mask + 1;
     for (unsigned long long s = first; s < n_a; s += stride) {
         const ulonglong2 e = slot_load(a, s);
-        if (e.x != kEmptyKey)
+        if (slot_held(e.x, e.y))
             count_cell(bins, out, kmer_join::clip(e.y, n_rows),
                        kmer_join::clip(table_find(b, e.x, revcomp_code(e.x, b.k)), n_cols), n_cols);
     }
     for (unsigned long long s = first; s < n_b; s += stride) {
         const ulonglong2 e = slot_load(b, s);
-        if (e.x != kEmptyKey && table_find(a, e.x, revcomp_code(e.x, a.k)) == 0ull)
+        if (slot_held(e.x, e.y) && table_find(a, e.x, revcomp_code(e.x, a.k)) == 0ull)
             count_cell(bins, out, 0u, kmer_join::clip(e.y, n_cols), n_cols);
     }
     __syncthreads();

@@ -1,7 +1,8 @@
 // kmer_table.h -- the open-addressing k-mer table of K-kmer (k <= 31) as device functions: shared by
 // kmer_count.hip (every occurrence goes to the table), kmer_bulk.hip (only what its LDS path hands back does), and
 // kmer_lookup.hip, kmer_correct.hip and kmer_influence.hip (which only read it: table_find; a wave a read: wave_read.h),
-// and kmer_join.hip (which reads two: every key of one table looked up in the other).
+// kmer_join.hip (which reads two: every key of one table looked up in the other), and kmer_remove.hip (which lowers
+// counts and never clears a key: "held" and "occupied" below).
 // See kmer_count.hip for the reference it restates and for why a key's first slot is a function of its minimizer.
 // The arithmetic on the codes themselves: kmer_codes.h.
 #pragma once
@@ -120,11 +121,61 @@ __device__ __forceinline__ ulonglong2 slot_load(const KmerTable &t, unsigned lon
     return *reinterpret_cast<const ulonglong2 *>(t.slots + h);
 }
 
-// The count the table holds for `key` (0: it holds none), without a store.  It replays table_add's decisions: the
-// first slot holds the key (its count), is empty (0: the key would have been put there) or holds another key; then
-// from the plain hash on, a slot with the key gives its count and an empty one 0; after kMaxProbe probes 0 -- the add
-// would have overflowed.  Slots never change their key and nothing is deleted, so every slot an add of `key` passed
-// over still holds the key it held then: exact for every key, also after a rehash (it inserts by table_add).
+// ---- held and occupied ------------------------------------------------------------------------
+// A slot is OCCUPIED if it carries a key at all; a key is HELD if its slot carries it with a count of at least 1.  On a
+// table that was only added to the two coincide.  A removal (kmer_remove.hip) lowers a count and never clears a key: a
+// count may reach 0 while the key stays where every probe chain expects it, so table_add and table_find keep replaying
+// the same decisions, also past keys whose count is 0.  Every scan of this table -- the stats, the histogram, the join,
+// the rehash -- speaks of held keys through slot_held; the stats also count the occupied slots, which is what bounds
+// how full the table is.
+__device__ __forceinline__ bool slot_occupied(unsigned long long key)
+{
+    return key != kEmptyKey;
+}
+
+__device__ __forceinline__ bool slot_held(unsigned long long key, unsigned long long count)
+{
+    return slot_occupied(key) && count != 0ull;
+}
+
+// The slot that carries `key` (kNoSlot: none does) and, in `count`, the count loaded with it, without a store.  It
+// replays table_add's decisions: the first slot carries the key, is empty (the key would have been put there: none) or
+// carries another key; then from the plain hash on, a slot with the key is the one and an empty one ends the walk;
+// after kMaxProbe probes none -- the add would have overflowed.  Slots never change their key and no key is ever
+// cleared, so every slot an add of `key` passed over still carries the key it carried then: exact for every key, also
+// after a rehash (it inserts by table_add) and past keys whose count a removal has brought to 0.
+constexpr unsigned long long kNoSlot = ~0ull;
+__device__ __forceinline__ unsigned long long table_locate(const KmerTable &t, unsigned long long key, unsigned long long rc,
+                                                           unsigned long long &count)
+{
+    if (has_first_slot(t)) {
+        const unsigned long long h = first_slot(key, rc, t);
+        const ulonglong2 e = slot_load(t, h);
+        if (e.x == key) {
+            count = e.y;
+            return h;
+        }
+        if (e.x == kEmptyKey)
+            return kNoSlot;
+    }
+    unsigned long long h = slot_of(key, t.log2_slots);
+    for (int probe = 0; probe < kMaxProbe; ++probe) {
+        const ulonglong2 e = slot_load(t, h);
+        if (e.x == key) {
+            count = e.y;
+            return h;
+        }
+        if (e.x == kEmptyKey)
+            return kNoSlot;
+        h = (h + 1) & t.mask;
+    }
+    return kNoSlot;
+}
+
+// The count the table holds for `key` (0: it holds none -- no slot carries it, or one does with a count of 0), without
+// a store: table_locate's walk, written out.  (Built over table_locate the readers' kernels -- kmer_lookup.hip,
+// kmer_correct.hip, kmer_influence.hip -- came out as other code; the two walks stand side by side instead, and
+// tests/test_gpu_remove.py holds them to the same answers.)
 __device__ __forceinline__ unsigned long long table_find(const KmerTable &t, unsigned long long key, unsigned long long rc)
 {
     if (has_first_slot(t)) {

@@ -23,7 +23,20 @@ from .read_sets import (REFITS, ResidentReads, _cut, _hist_dict, _occurrences, c
 from .sample import MAX_GROUPS, _check_split, split_reads_device
 
 
-def leave_group_out_histograms(reads, k, groups, seed=0, canonical=False, device=-1):
+ROUTES = ("recount", "remove")
+MAX_REMOVE_K = 31  # the removal takes keys of one word (covest_kmer_remove_device)
+
+
+def _check_route(route, k):
+    """The rule of `route` before the library is asked (ValueError): one of ROUTES, and "remove" only at k <= 31."""
+    if route not in ROUTES:
+        raise ValueError('route must be "recount" or "remove"')
+    if route == "remove" and k > MAX_REMOVE_K:
+        raise ValueError('route="remove" takes k <= %d (keys of one word); use route="recount"' % MAX_REMOVE_K)
+    return route
+
+
+def leave_group_out_histograms(reads, k, groups, seed=0, canonical=False, device=-1, route="recount"):
     """(hist_full, [hist_g for g in range(groups)], occurrences) of `reads` -- a SimulatedReads, an (n, L) uint8 array
     or a pair (bases, offsets) in the packed layout --: hist_g the k-mer histogram {abundance: k-mers} of the reads
     outside group g of covest_split_reads(groups, seed), hist_full that of all reads, occurrences[g] = sum i hist_g[i].
@@ -32,14 +45,21 @@ def leave_group_out_histograms(reads, k, groups, seed=0, canonical=False, device
     reserved once for the whole set: clear, add_device on the ranks before the group, add_device on the ranks behind it,
     histogram.  The sub-ranges address the same buffer (ragged reads: offsets + first; reads of one length: bases + first
     * read_len).  The buffers live on the calling thread's current device, which `device` has to name (or -1).  Reads
-    that do not fit the device together with their copy raise CovestHipError; streaming a file in passes is not built."""
-    return _leave_group_out(reads, k, groups, seed, canonical, device)[:3]
+    that do not fit the device together with their copy raise CovestHipError; streaming a file in passes is not built.
+
+    `route`: "recount" is the loop above, G + 1 counts of the read set.  "remove" (k <= 31) counts all
+    reads ONCE and, per group, takes the ranks of group g out of the table again (ResidentReads.uncount), takes the
+    histogram and counts them back in: about three counts' worth of atomics in all and no clear of the table per group.
+    The histograms are exact integers either way: the two routes return the same dicts, and after the loop the counter
+    holds all reads again."""
+    return _leave_group_out(reads, k, groups, seed, canonical, device, route)[:3]
 
 
-def _leave_group_out(reads, k, groups, seed, canonical, device):
+def _leave_group_out(reads, k, groups, seed, canonical, device, route="recount"):
     """leave_group_out_histograms, and the split's group_first behind its three results."""
     groups = check_sets("groups", groups, "jackknife", MAX_GROUPS, MAX_GROUPS)
     groups, seed, _ = _check_split(groups, seed, 0)
+    _check_route(route, k)
     with ResidentReads(reads, k, canonical, device, "leave_group_out_histograms", "their copy in group order") as rs:
         d_out = rs.reserve("out", rs.n_bases)
         d_out_off = rs.reserve("out_offsets", 8 * (rs.n + 1)) if rs.offsets is not None else None
@@ -58,10 +78,17 @@ def _leave_group_out(reads, k, groups, seed, canonical, device):
         hist_full = rs.histogram()
         hists = []
         for g in range(groups):
-            rs.clear()
-            add(0, int(first[g]))
-            add(int(first[g + 1]), rs.n)
-            hists.append(rs.histogram())
+            lo, hi = int(first[g]), int(first[g + 1])
+            if route == "remove":
+                if hi > lo:
+                    rs.uncount(d_out, d_out_off, lo, hi)
+                hists.append(rs.histogram())
+                add(lo, hi)
+            else:
+                rs.clear()
+                add(0, lo)
+                add(hi, rs.n)
+                hists.append(rs.histogram())
         return hist_full, hists, [_occurrences(h) for h in hists], first
 
 
@@ -104,7 +131,7 @@ def summarize_jackknife(estimates, success, full, occurrences, occurrences_full,
 
 
 def read_jackknife(model, estimate, reads, groups=32, seed=0, fix=None, level=0.95, trim=None, refit="lockstep-gradient",
-                   sample_factor=1, canonical=False, **estimator_options):
+                   sample_factor=1, canonical=False, route="recount", **estimator_options):
     """The delete-a-group jackknife of `estimate` (of `model`, whose histogram is that of `reads` at k = model.k,
     `canonical` as it was counted) over `groups` seeded groups of the reads.
 
@@ -115,7 +142,9 @@ def read_jackknife(model, estimate, reads, groups=32, seed=0, fix=None, level=0.
     Student t with G' - 1 degrees of freedom, G' the leave-out refits that succeeded: G, not the number of reads,
     limits how well the variance itself is known.
 
-    HOW.  leave_group_out_histograms gives the G + 1 histograms.  Each is cut as the model's was: keys below `trim` are
+    HOW.  leave_group_out_histograms gives the G + 1 histograms, by `route` ("recount", or "remove" at k <= 31: the same
+    histograms, so the same estimates and standard errors bit for bit; the returned dict records a route other than the
+    default as 'route', which print_output passes on as jackknife_route).  Each is cut as the model's was: keys below `trim` are
     kept and the mass at and above goes to the tail (hist_steps.trim_hist); trim=None with model.tail == 0 means no cut,
     trim=None with a tail takes max(model.hist) + 1.  The G + 1 histograms are put on ONE key set -- the model's keys and
     behind them, ascending, the keys any of the histograms has beyond those; zero counts kept -- on a twin of the model
@@ -134,10 +163,13 @@ def read_jackknife(model, estimate, reads, groups=32, seed=0, fix=None, level=0.
     have), params, estimate, level, groups, seed, refit."""
     groups = check_sets("groups", groups, "jackknife", MAX_GROUPS, MAX_GROUPS)
     _check_split(groups, seed, 0)
+    _check_route(route, model.k)
     estimate, names = check_refit_request("read_jackknife", model, estimate, refit, estimator_options, level, fix, trim,
                                           sample_factor, REFITS)
-    hist_full, hists, _, group_first = _leave_group_out(reads, model.k, groups, seed, canonical, model.device)
+    hist_full, hists, _, group_first = _leave_group_out(reads, model.k, groups, seed, canonical, model.device, route)
     out = {'groups': groups}
+    if route != "recount":  # (the default leaves the dict as it always was)
+        out['route'] = route
     out.update(refit_histogram_set(model, estimate, hists, hist_full, seed, fix, level, trim, refit, estimator_options))
     out['group_sizes'] = np.diff(group_first).tolist()
     out.update(summarize_jackknife(out['estimates'], out['success'], out['full_estimate'], out['occurrences'],

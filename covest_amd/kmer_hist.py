@@ -222,8 +222,9 @@ class KmerCounts:
     def __init__(self, k=20, canonical=False, device=-1, min_slots=1 << 16):
         self.k = int(k)
         self.canonical = bool(canonical)
-        self._distinct = 0  # distinct k-mers in the table when last measured
-        self._added = 0     # k-mer occurrences inserted since: _distinct + _added bounds the distinct count
+        self._distinct = 0  # slots OCCUPIED when last measured (the distinct k-mers, until something is removed)
+        self._added = 0     # k-mer occurrences inserted since: _distinct + _added bounds the occupied slots
+        self._partitioned = False  # the counter holds a count_reads_device result (no table to ask for its occupancy)
         h = ctypes.c_void_p()
         _capi.check(_capi.lib().covest_kmer_create(self.k, 1 if canonical else 0, int(min_slots),
                                                    int(device), ctypes.byref(h)), "covest_kmer_create")
@@ -244,17 +245,33 @@ class KmerCounts:
     def slots(self):
         return int(_capi.lib().covest_kmer_slots(self._handle))
 
+    def _measure(self):
+        """(keys held, slots occupied) as the table has them now.  Only a removal makes the two differ, and only the
+        one-word table (k <= 31) can be removed from: elsewhere both are the distinct count."""
+        if self.k > 31 or self._partitioned:
+            distinct = self.stats()[1]
+            return distinct, distinct
+        return self.occupancy()
+
     def _reserve_for(self, n_new):
-        """Keep the table at most half full of DISTINCT k-mers.  The distinct count is bounded by what was
-        measured last plus every occurrence inserted since; only when that bound no longer fits is the table
-        asked (one small kernel), and it grows for the measured count plus the batch about to be added --
-        never for the cumulative number of occurrences (10 Gbp of reads of a 100 Mbp genome need a table for
-        ~1e8 k-mers, not 1e10)."""
+        """Keep the table at most half full of OCCUPIED slots -- of distinct k-mers, as long as nothing was removed; a
+        key whose count a removal brought to 0 still takes its slot.  The occupied slots are bounded by what was
+        measured last plus every occurrence inserted since; only when that bound no longer fits is the table asked
+        (one small kernel).  Where the slots occupied now and the batch fit, nothing happens.  Else the keys of count
+        0 are let go: by compact() where the keys HELD and the batch fit the table as it is, else by a reserve for the
+        keys held plus the batch about to be added (its rehash takes the held keys alone) -- never for the cumulative
+        number of occurrences (10 Gbp of reads of a 100 Mbp genome need a table for ~1e8 k-mers, not 1e10)."""
         n_new = int(n_new)
         if 2 * (self._distinct + self._added + n_new) + 1024 > self.slots:
-            self._distinct, self._added = self.stats()[1], 0
-            _capi.check(_capi.lib().covest_kmer_reserve(self._handle, 2 * (self._distinct + n_new) + 1024),
-                        "covest_kmer_reserve")
+            held, occupied = self._measure()
+            self._distinct, self._added = occupied, 0
+            if 2 * (occupied + n_new) + 1024 > self.slots:
+                if held < occupied and 2 * (held + n_new) + 1024 <= self.slots:
+                    _capi.check(_capi.lib().covest_kmer_compact(self._handle), "covest_kmer_compact")
+                else:
+                    _capi.check(_capi.lib().covest_kmer_reserve(self._handle, 2 * (held + n_new) + 1024),
+                                "covest_kmer_reserve")
+                self._distinct = held
         self._added += n_new
 
     def add_reads(self, reads):
@@ -332,6 +349,86 @@ class KmerCounts:
             ctypes.c_void_p(d_weights_ptr or 0), ctypes.c_void_p(stream or 0)), "covest_kmer_add_weighted_device")
         return self
 
+    def remove(self, reads):
+        """Take the k-mers of `reads` -- what lookup takes -- out of the table again (covest_kmer_remove; k <= 31):
+        add_reads' inverse.  No key is cleared: a key nothing supports any more keeps its slot with a count of 0, is no
+        longer held (stats(), len(), histogram(), lookup) and still occupied (occupancy()).  Removing what was never
+        added is an UNDERFLOW: this call, and every later histogram() and host-form call until clear(), raises
+        CovestHipError with "underflow"; the counts are then unspecified."""
+        blob, offsets = _packed_reads(reads)
+        n = offsets.size - 1
+        if n:
+            _capi.check(_capi.lib().covest_kmer_remove(
+                self._handle, ctypes.c_void_p(blob.ctypes.data), ctypes.c_void_p(offsets.ctypes.data), n),
+                "covest_kmer_remove")
+        return self
+
+    def remove_weighted(self, reads, weights):
+        """remove with every occurrence of read r taken out weights[r] times (covest_kmer_remove_weighted):
+        add_weighted's inverse.  A weight of 0 takes nothing out, also of a read that was never added."""
+        blob, offsets = _packed_reads(reads)
+        n = offsets.size - 1
+        weights = _read_weights(weights, n)
+        if n:
+            _capi.check(_capi.lib().covest_kmer_remove_weighted(
+                self._handle, ctypes.c_void_p(blob.ctypes.data), ctypes.c_void_p(offsets.ctypes.data), n,
+                ctypes.c_void_p(weights.ctypes.data)), "covest_kmer_remove_weighted")
+        return self
+
+    def remove_device(self, d_bases_ptr, n_reads, read_len, d_offsets_ptr=None, stream=None):
+        """add_device's inverse for reads resident in HBM (raw device pointers; covest_kmer_remove_device): asynchronous
+        on `stream`, which must be the stream of the adds it takes back (or ordered after them by the caller).  It does
+        not look at the underflow state: the next histogram() reports it."""
+        _capi.require_shared_runtime("KmerCounts.remove_device")
+        _capi.check(_capi.lib().covest_kmer_remove_device(
+            self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0), int(n_reads), int(read_len),
+            ctypes.c_void_p(stream or 0)), "covest_kmer_remove_device")
+        return self
+
+    def remove_weighted_device(self, d_bases_ptr, n_reads, read_len, d_weights_ptr, d_offsets_ptr=None, stream=None):
+        """remove_device with a weight per read resident in HBM (`d_weights_ptr`: n_reads uint32, aligned to 4 bytes;
+        covest_kmer_remove_weighted_device): the weights are read on `stream`."""
+        _capi.require_shared_runtime("KmerCounts.remove_weighted_device")
+        _capi.check(_capi.lib().covest_kmer_remove_weighted_device(
+            self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0), int(n_reads), int(read_len),
+            ctypes.c_void_p(d_weights_ptr or 0), ctypes.c_void_p(stream or 0)), "covest_kmer_remove_weighted_device")
+        return self
+
+    def replace_reads(self, before, after, changed):
+        """The reads `before` replaced by `after` in the table, where `changed` flags them: two read sets of equal shape
+        (as many reads, each as long as its partner; what lookup takes) and one flag (0 / 1, or bool) per read.  It is
+        remove_weighted(before, changed), then add_weighted(after, changed): where the two sets differ in the flagged
+        reads only, the table then equals a fresh count of `after`.  correct()'s output and its per-read `corrected`
+        > 0 feed it directly.  ValueError, before the library is asked, for sets of different shape and for flags that
+        are not one 0 / 1 per read."""
+        blob_b, off_b = _packed_reads(before)
+        blob_a, off_a = _packed_reads(after)
+        if off_b.size != off_a.size or (np.diff(off_b) != np.diff(off_a)).any():
+            raise ValueError("replace_reads: before and after must be read sets of equal shape")
+        flags = np.asarray(changed)
+        if flags.dtype == np.bool_:
+            flags = flags.astype(np.uint32)
+        flags = _read_weights(flags, off_b.size - 1)
+        if flags.size and int(flags.max()) > 1:
+            raise ValueError("replace_reads: changed must be one flag (0 or 1) per read")
+        self.remove_weighted((blob_b, off_b), flags)
+        return self.add_weighted((blob_a, off_a), flags)
+
+    def occupancy(self):
+        """(keys held, slots occupied) (covest_kmer_occupancy; k <= 31): held = with a count of at least 1, what
+        stats() and len() speak of; occupied = slots that carry a key at all, what bounds how full the table is.  They
+        differ only after a removal."""
+        out = (ctypes.c_int64 * 2)()
+        _capi.check(_capi.lib().covest_kmer_occupancy(self._handle, out), "covest_kmer_occupancy")
+        return int(out[0]), int(out[1])
+
+    def compact(self):
+        """Rehash into a table of the same size (covest_kmer_compact; k <= 31): the keys of count 0 go, occupied ==
+        held afterwards."""
+        _capi.check(_capi.lib().covest_kmer_compact(self._handle), "covest_kmer_compact")
+        self._distinct, self._added = self.occupancy()[1], 0
+        return self
+
     def count_reads_device(self, d_bases_ptr, n_reads, read_len, d_offsets_ptr=None, n_bases=None, stream=None):
         """ALL the k-mers of reads resident in HBM into this (emptied) counter -- the loop of main,
         bin/kmer_hist.py:77-89 -- by the partitioned path where it applies (covest_kmer_count_reads_device: k = 19..31,
@@ -345,6 +442,7 @@ class KmerCounts:
             n_bases, ctypes.c_void_p(stream or 0))
         if rc == 0:
             self._distinct = self._added = 0
+            self._partitioned = True
             return "partitioned"
         if rc not in (_capi.COVEST_E_UNSUPPORTED, _capi.COVEST_E_NOMEM):
             _capi.check(rc, "covest_kmer_count_reads_device")
@@ -515,11 +613,12 @@ class KmerCounts:
     def clear(self, stream=None):
         """Drop every count but keep the table (a fresh `defaultdict(int)` of the same size)."""
         self._distinct = self._added = 0
+        self._partitioned = False
         _capi.check(_capi.lib().covest_kmer_clear(self._handle, ctypes.c_void_p(stream or 0)),
                     "covest_kmer_clear")
 
     def stats(self):
-        """(max count + 1, distinct k-mers)."""
+        """(max count + 1, distinct k-mers): the keys HELD -- with a count of at least 1 (occupancy())."""
         need, distinct = ctypes.c_int64(), ctypes.c_int64()
         _capi.check(_capi.lib().covest_kmer_histogram(self._handle, None, 0, ctypes.byref(need),
                                                       ctypes.byref(distinct)), "covest_kmer_histogram")

@@ -105,6 +105,14 @@ class ResidentReads:
         else:
             self.counts.add_weighted_device(*where, d_weights + 4 * lo, d_offsets_ptr=d_offsets, reserve=False)
 
+    def uncount(self, d_bases, d_offsets, lo, hi):
+        """Take the reads at ranks [lo, hi) of (`d_bases`, `d_offsets`) out of the counter again (k <= 31): count's
+        inverse on the same sub-range.  The keys stay in their slots with a count of 0 where nothing else supports them,
+        so the table reserved by open_counter stays large enough for counting them back in."""
+        ragged = self.offsets is not None
+        where = (d_bases, hi - lo, 0) if ragged else (d_bases + lo * self.read_len, hi - lo, self.read_len)
+        self.counts.remove_device(*where, d_offsets_ptr=d_offsets + 8 * lo if ragged else None)
+
     def clear(self):
         self.counts.clear()
 

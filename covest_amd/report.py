@@ -48,8 +48,9 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
     `jackknife`: the dict covest_amd.jackknife.read_jackknife returns (sample factor 1 by its own rule, so nothing is
     scaled); the record then carries jackknife_groups, jackknife_used, jackknife_failed, jackknife_level and, per free
     parameter and for genome_size, jackknife_se_<name>, jackknife_bias_<name> and jackknife_interval_<name>: the
-    delete-a-group jackknife over READS, which sees the dependence between the k-mers of one read.
-    Without it the record is unchanged.
+    delete-a-group jackknife over READS, which sees the dependence between the k-mers of one read, and
+    where the dict carries 'route' (read_jackknife sets it for a route other than its default, "recount"), jackknife_route:
+    how the leave-out histograms were made (the numbers are the same).  Without it the record is unchanged.
     `posterior`: the PosteriorClasses covest_amd.posterior.posterior_classes returns; the record then carries
     posterior_error_cutoff (error_cutoff at level 0.5, None where there is none), posterior_erroneous_kmers,
     posterior_error_free_kmers, one posterior_copies_* per copy column (expected_kmers), posterior_undefined_kmers and
@@ -192,6 +193,8 @@ def print_output(hist_orig, model, success, sample_factor, estimated=None, guess
             record['bootstrap_t_interval_genome_size'] = [float(v) for v in size['t_interval']]
     if jackknife is not None:
         resampled('jackknife', jackknife, 'groups')
+        if jackknife.get('route') is not None:
+            record['jackknife_route'] = str(jackknife['route'])
     if posterior is not None:
         cutoff = posterior.error_cutoff()
         record['posterior_error_cutoff'] = None if cutoff is None else int(cutoff)

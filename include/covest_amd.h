@@ -374,9 +374,45 @@ int covest_kmer_add_weighted_device(covest_kmer *c, const uint8_t *d_bases, cons
                                     int64_t read_len, const uint32_t *d_weights, void *stream);
 int covest_kmer_add_weighted(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
                              const uint32_t *weights);
+/* The INVERSE of the four adds (k <= 31; no reference counterpart): every k-mer occurrence of
+ * read r is taken out of the table once, or weights[r] times.  Same arguments, same read layout, same weight rules as
+ * covest_kmer_add_device / _add_weighted_device / _add / _add_weighted: a read of weight 0 takes nothing out (also
+ * where it was never added), a read shorter than k takes out the one key the add adds for it, an empty read k-mer 0.
+ *   HELD and OCCUPIED.  A removal lowers a count and never clears a key.  A key is HELD if its slot carries it with a
+ * count of at least 1; a slot is OCCUPIED if it carries a key at all.  covest_kmer_histogram (its distinct count, its
+ * histogram: out[0] stays 0), covest_kmer_join_histogram* (a key held by neither table is in no cell) and the lookups
+ * (0 already means "holds none") speak of held keys; how FULL the table is, is a matter of occupied slots:
+ * covest_kmer_occupancy gives both, and the caller's reserve rule reads "slots >= 2 * (slots OCCUPIED + keys the next
+ * batch can add)".  covest_kmer_reserve, when it rehashes, and covest_kmer_compact leave the keys of count 0 behind.
+ *   UNDERFLOW.  A window whose key occupies no slot, or whose count was smaller than what is subtracted, sets a sticky
+ * underflow state on the counter, separate from the overflow state (neither erases the other).  After it the counts
+ * are unspecified.  Until covest_kmer_clear, every call that answers COVEST_E_NOMEM for a sticky overflow --
+ * covest_kmer_histogram, covest_kmer_reserve when it would rehash, covest_kmer_compact, the host forms of the adds, the
+ * removals, the lookups, the correction, the influence and the join -- answers COVEST_E_INVALID with "underflow" and
+ * its own name in the message (an overflow, where both are set, is reported first).
+ *   The _device forms are asynchronous on `stream`, which must be the stream of the adds whose counts they take back
+ * (or ordered after them by the caller), read d_weights there, and never look at either state.  The host forms copy,
+ * wait and report an underflow themselves.
+ *   COVEST_E_UNSUPPORTED for k > 31: in the wide table the state word IS the count and 0 means empty, so a key cannot
+ * survive a count of 0 there.  COVEST_E_INVALID on a counter that holds a covest_kmer_count_reads_device result, for
+ * NULL weights with n_reads > 0 and for a weights pointer that is not aligned to 4 bytes.  Removal frees no slot. */
+int covest_kmer_remove_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                              int64_t read_len, void *stream);
+int covest_kmer_remove_weighted_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                                       int64_t read_len, const uint32_t *d_weights, void *stream);
+int covest_kmer_remove(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads);
+int covest_kmer_remove_weighted(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
+                                const uint32_t *weights);
+/* out[0] = the keys held, out[1] = the slots occupied (k <= 31, not a partitioned result).  Waits for the device. */
+int covest_kmer_occupancy(covest_kmer *c, int64_t out[2]);
+/* Rehash into a fresh table of the same size: the keys of count 0 go, occupied == held afterwards (k <= 31, not a
+ * partitioned result).  Waits for the device; the sticky states as covest_kmer_reserve. */
+int covest_kmer_compact(covest_kmer *c);
 /* compute_histogram(counts) (bin/kmer_hist.py:57-64): out[i] = number of distinct k-mers seen i
  * times, i = 0 .. max count.  Call with out == NULL to learn needed_len (= max count + 1) and the
- * number of distinct k-mers; fails with COVEST_E_NOMEM-like status if the table overflowed. */
+ * number of distinct k-mers; fails with COVEST_E_NOMEM-like status if the table overflowed.  After removals
+ * (covest_kmer_remove*) "distinct" are the keys HELD, and a removal that underflowed makes it fail with
+ * COVEST_E_INVALID. */
 int covest_kmer_histogram(covest_kmer *c, int64_t *out, int64_t out_len, int64_t *needed_len,
                           int64_t *distinct);
 /* The WHOLE counting loop of main (bin/kmer_hist.py:77-89: compute_counts over every read) for reads resident in
