@@ -35,6 +35,7 @@ SOURCES = [("host_common.cpp", (), "host_common"), ("tiles_host.cpp", (), "tiles
            ("abi_posterior.cpp", (), "abi_posterior"), ("posterior.hip", (), "posterior"),
            ("abi_lookup.cpp", (), "abi_lookup"), ("kmer_lookup.hip", (), "kmer_lookup"),
            ("abi_join.cpp", (), "abi_join"), ("kmer_join.hip", (), "kmer_join"),
+           ("abi_update.cpp", (), "abi_update"),
            ("abi_remove.cpp", (), "abi_remove"), ("kmer_remove.hip", (), "kmer_remove"),
            ("abi_correct.cpp", (), "abi_correct"), ("kmer_correct.hip", (), "kmer_correct"),
            ("abi_influence.cpp", (), "abi_influence"), ("kmer_influence.hip", (), "kmer_influence"),

@@ -406,7 +406,7 @@ double lgamma_of_factorial(int64_t j);
 
 int64_t launch_record_text(const LaunchRecord &r, char *buf, int64_t cap); // (kernels.h)
 
-// ---- kmer_host.cpp: a host form over the counter's table as a scope (covest_kmer_add, abi_lookup.cpp, abi_correct.cpp,
+// ---- kmer_host.cpp: a host form over the counter's table as a scope (abi_update.cpp, abi_lookup.cpp, abi_correct.cpp,
 // abi_influence.cpp), after the form's own checks: the counter's lock, then its device; open() stages the reads of bases
 // / offsets[n_reads + 1] (n_reads > 0, offsets[n_reads] >= offsets[0]) into c->ws_bases and, counted from 0,
 // c->ws_offsets; the caller reserves its outputs and launches (the *_locked body of its device form: the lock is not
@@ -419,6 +419,8 @@ int kmer_check_overflow(covest_kmer *c, const char *who); // (after the caller h
 std::string kmer_underflow_text(const char *who);
 int kmer_check_weights(const char *who, const uint32_t *weights, int64_t n_reads); // a weight a read (the weighted forms)
 int kmer_rehash_locked(covest_kmer *c, int64_t min_slots, const char *who);        // (kmer_host.cpp; the lock is held)
+hipError_t table_count(const covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads, int64_t read_len,
+                       const uint32_t *d_weights, hipStream_t st); // the adds into the table of either key width (abi_update.cpp)
 class KmerHostCall {
   public:
     explicit KmerHostCall(covest_kmer *c) : c(c), lock_(c->lock), dev_(c->device) {}

@@ -19,7 +19,7 @@
 #include <algorithm>
 
 #include "kernels.h"
-#include "wave_read.h"
+#include "kmer_update.h"
 
 namespace covest {
 
@@ -27,58 +27,15 @@ namespace {
 
 using namespace kmer;
 
-// One window of a read: its 2k-bit code (hash_kmer / rehash, bin/kmer_hist.py:18-31), the reverse complement's, the
-// canonical choice, the table.  `add`: 1, or the read's weight (covest_kmer_add_weighted*).
-__device__ __forceinline__ void count_window(const unsigned char *__restrict__ seq, int64_t s, int64_t len, int k,
-                                             int canonical, const KmerTable &t, int *overflow, unsigned long long add)
-{
-    unsigned long long h, rc;
-    window_key(seq, s, len, k, canonical, h, rc);
-    table_add(t, h, rc, add, overflow);
-}
-
-// A wave a read.  kWeighted: every occurrence is added weights[read] times in its one atomic add; the weight is
-// wave-uniform, and a wave whose read has weight 0 leaves before it touches the bases.  The unweighted instantiation is
-// the kernel as it was: `add` is the constant 1 and `weights` is not looked at.
-template <bool kWeighted>
-__device__ __forceinline__ void count_read(const unsigned char *__restrict__ bases, const int64_t *__restrict__ offsets,
-                                           int64_t n_reads, int64_t fixed_len, int k, int canonical, const KmerTable &t,
-                                           int *overflow, const uint32_t *__restrict__ weights)
-{
-    WaveRead w;
-    if (!wave_read(bases, offsets, n_reads, fixed_len, k, w))
-        return;
-    unsigned long long add = 1ull;
-    if (kWeighted) {
-        add = weights[w.r];
-        if (add == 0)
-            return;
-    }
-    if (w.len < k) {
-        // hash_kmer(seq[:k]) of a read shorter than k: the hash of what there is, counted once;
-        // an empty read counts k-mer 0 (bin/kmer_hist.py:36-37)
-        if (w.lane == 0) {
-            unsigned long long h = 0, rc = 0;
-            for (int i = 0; i < (int)w.len; ++i) {
-                const unsigned long long c = base_code(w.seq[i]);
-                h = (h << 2) | c;
-            }
-            rc = revcomp_code(h, k);
-            canonical_pair(h, rc, canonical);
-            table_add(t, h, rc, add, overflow);
-        }
-        return;
-    }
-    for (int64_t s = w.lane; s < w.len - k + 1; s += kWave) // (len >= k: w.n_windows without its clamp, which costs 0.5 %)
-        count_window(w.seq, s, w.len, k, canonical, t, overflow, add);
-}
-
+// The four adding kernels: kmer_update.h's walk with the add as its operation.  A wave a read,
+// plain and weighted (every occurrence is added weights[read] times in its one atomic add); reads of ONE length, the
+// windows numbered through, plain and weighted.
 __global__ __launch_bounds__(256) void kmer_count_kernel(const unsigned char *__restrict__ bases,
                                                          const int64_t *__restrict__ offsets,
                                                          int64_t n_reads, int64_t fixed_len, int k,
                                                          int canonical, const KmerTable t, int *overflow)
 {
-    count_read<false>(bases, offsets, n_reads, fixed_len, k, canonical, t, overflow, nullptr);
+    update_read<false>(bases, offsets, n_reads, fixed_len, k, canonical, t, TableAdd{overflow}, nullptr);
 }
 
 __global__ __launch_bounds__(256) void kmer_count_weighted_kernel(const unsigned char *__restrict__ bases,
@@ -87,38 +44,14 @@ __global__ __launch_bounds__(256) void kmer_count_weighted_kernel(const unsigned
                                                                   const KmerTable t, int *overflow,
                                                                   const uint32_t *__restrict__ weights)
 {
-    count_read<true>(bases, offsets, n_reads, fixed_len, k, canonical, t, overflow, weights);
-}
-
-// Reads of ONE length (what a sequencing run's FASTQ holds, and config 5's synthetic reads): the windows of all reads
-// are numbered through -- read = index / windows per read -- and a wave takes 64 consecutive ones, so that no lane
-// idles in a read's last 64-window round (100-base reads have 80 windows: 64 + 16 lanes, 37 % of the slots empty).
-// kWeighted: the lane takes its read's weight, and a weight of 0 returns before the bases are read.
-template <bool kWeighted>
-__device__ __forceinline__ void count_numbered_window(const unsigned char *__restrict__ bases, int64_t n_reads, int64_t len,
-                                                      int k, int canonical, const KmerTable &t, int *overflow,
-                                                      const uint32_t *__restrict__ weights)
-{
-    const int64_t n_windows = len - k + 1; // (the host sends reads shorter than k to kmer_count_kernel)
-    const int64_t total = n_reads * n_windows;
-    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= total)
-        return;
-    const int64_t r = w / n_windows;
-    unsigned long long add = 1ull;
-    if (kWeighted) {
-        add = weights[r];
-        if (add == 0)
-            return;
-    }
-    count_window(bases + r * len, w - r * n_windows, len, k, canonical, t, overflow, add);
+    update_read<true>(bases, offsets, n_reads, fixed_len, k, canonical, t, TableAdd{overflow}, weights);
 }
 
 __global__ __launch_bounds__(256) void kmer_count_fixed_kernel(const unsigned char *__restrict__ bases, int64_t n_reads,
                                                                int64_t len, int k, int canonical, const KmerTable t,
                                                                int *overflow)
 {
-    count_numbered_window<false>(bases, n_reads, len, k, canonical, t, overflow, nullptr);
+    update_numbered_window<false>(bases, n_reads, len, k, canonical, t, TableAdd{overflow}, nullptr);
 }
 
 __global__ __launch_bounds__(256) void kmer_count_fixed_weighted_kernel(const unsigned char *__restrict__ bases,
@@ -126,7 +59,7 @@ __global__ __launch_bounds__(256) void kmer_count_fixed_weighted_kernel(const un
                                                                         const KmerTable t, int *overflow,
                                                                         const uint32_t *__restrict__ weights)
 {
-    count_numbered_window<true>(bases, n_reads, len, k, canonical, t, overflow, weights);
+    update_numbered_window<true>(bases, n_reads, len, k, canonical, t, TableAdd{overflow}, weights);
 }
 
 // Re-insert every HELD key of `src` (kmer_table.h) into the `dst` table -- a larger one, or one of the same size
@@ -226,43 +159,14 @@ hipError_t launch_kmer_fill_empty(const KmerTable &t, hipStream_t stream)
     return hipGetLastError();
 }
 
-// weights == nullptr: the unweighted kernels, launched as they always were; else a weight a read, which goes with the
-// launch's first read (kmer_plan.h weights_at, window_weights_at)
+// weights == nullptr: the unweighted kernels; else a weight a read (kmer_update.h launch_update)
 hipError_t launch_kmer_count(const unsigned char *bases, const int64_t *offsets, int64_t n_reads,
                              int64_t fixed_len, int k, int canonical, const KmerTable &t, int *overflow,
                              hipStream_t stream, const uint32_t *weights)
 {
-    if (n_reads <= 0)
-        return hipSuccess;
-    if (!offsets && fixed_len >= k) {
-        // reads of one length: 64 consecutive windows per wave (kmer_count_fixed_kernel), at most 2^23 workgroups
-        // of 256 windows per launch, cut at whole reads
-        const int64_t n_windows = fixed_len - k + 1;
-        const int64_t reads_per_launch = kmer_plan::window_reads_per_launch(n_windows);
-        for (int64_t first = 0; first < n_reads; first += reads_per_launch) {
-            const int64_t n = kmer_plan::reads_of_launch(first, n_reads, reads_per_launch);
-            const int64_t total = n * n_windows;
-            const dim3 grid((unsigned)((total + 255) / 256));
-            if (weights)
-                hipLaunchKernelGGL(kmer_count_fixed_weighted_kernel, grid, dim3(256), 0, stream, bases + first * fixed_len, n,
-                                   fixed_len, k, canonical, t, overflow, weights + kmer_plan::window_weights_at(first));
-            else
-                hipLaunchKernelGGL(kmer_count_fixed_kernel, grid, dim3(256), 0, stream, bases + first * fixed_len, n,
-                                   fixed_len, k, canonical, t, overflow);
-        }
-        return hipGetLastError();
-    }
-    kmer_plan::for_each_wave_launch(n_reads, fixed_len, offsets != nullptr, kWaveReadsPerBlock, [&](const kmer_plan::WaveLaunch &l) {
-        const dim3 grid((unsigned)l.blocks), block(kWaveReadsPerBlock * kWave);
-        const int64_t *offs = offsets ? offsets + l.first : nullptr;
-        if (weights)
-            hipLaunchKernelGGL(kmer_count_weighted_kernel, grid, block, 0, stream, bases + l.byte_at, offs, l.n, fixed_len, k,
-                               canonical, t, overflow, weights + kmer_plan::weights_at(l));
-        else
-            hipLaunchKernelGGL(kmer_count_kernel, grid, block, 0, stream, bases + l.byte_at, offs, l.n, fixed_len, k,
-                               canonical, t, overflow);
-    });
-    return hipGetLastError();
+    return kmer::launch_update(kmer_count_kernel, kmer_count_weighted_kernel, kmer_count_fixed_kernel,
+                               kmer_count_fixed_weighted_kernel, bases, offsets, n_reads, fixed_len, k, canonical, t, overflow,
+                               stream, weights);
 }
 
 hipError_t launch_kmer_rehash(const KmerTable &src, const KmerTable &dst, int *overflow, hipStream_t stream)

@@ -35,16 +35,6 @@ hipError_t table_clear(const covest_kmer *c, hipStream_t st)
     return c->wide ? launch_kmer_wide_clear(c->wtable, st) : launch_kmer_fill_empty(c->table, st);
 }
 
-// d_weights null: every occurrence counts once; else a weight a read (covest_kmer_add_weighted*)
-hipError_t table_count(const covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
-                       int64_t read_len, const uint32_t *d_weights, hipStream_t st)
-{
-    int *flag = c->flag.as<int>();
-    return c->wide ? launch_kmer_wide_count(d_bases, d_offsets, n_reads, read_len, c->canonical, c->wtable, flag, st, d_weights)
-                   : launch_kmer_count(d_bases, d_offsets, n_reads, read_len, c->k, c->canonical, c->table, flag, st,
-                                       d_weights);
-}
-
 hipError_t table_rehash(const covest_kmer *c, const KmerTable &bigger, const KmerWideTable &wbigger)
 {
     return c->wide ? launch_kmer_wide_rehash(c->wtable, wbigger, c->flag.as<int>(), nullptr)
@@ -301,6 +291,17 @@ int finish(BulkCall &b)
 
 namespace covest {
 
+// The adds' way into the table of either key width (abi_update.cpp).  d_weights null: every occurrence counts once;
+// else a weight a read (covest_kmer_add_weighted*)
+hipError_t table_count(const covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
+                       int64_t read_len, const uint32_t *d_weights, hipStream_t st)
+{
+    int *flag = c->flag.as<int>();
+    return c->wide ? launch_kmer_wide_count(d_bases, d_offsets, n_reads, read_len, c->canonical, c->wtable, flag, st, d_weights)
+                   : launch_kmer_count(d_bases, d_offsets, n_reads, read_len, c->k, c->canonical, c->table, flag, st,
+                                       d_weights);
+}
+
 int KmerHostCall::open(const uint8_t *bases, const int64_t *offsets, int64_t n_reads)
 {
     COVEST_TRY(dev_.status());
@@ -493,75 +494,6 @@ int covest_kmer_reserve(covest_kmer *c, int64_t min_slots)
     if (dev_guard.status() != COVEST_OK)
         return dev_guard.status();
     return kmer_rehash_locked(c, min_slots, "covest_kmer_reserve");
-}
-
-// covest_kmer_add_device (d_weights null) and covest_kmer_add_weighted_device with the counter's lock held (the host
-// forms hold it for their whole call: host.h KmerHostCall)
-static int add_device_locked(const char *who, covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets,
-                             int64_t n_reads, int64_t read_len, const uint32_t *d_weights, void *stream)
-{
-    COVEST_TRY(fail_if(check_table_holds_keys(who, 0, c->bulk))); // (keys of any width are added)
-    DeviceGuard dev_guard(c->device);
-    COVEST_TRY(dev_guard.status());
-    HIP_TRY(table_count(c, d_bases, d_offsets, n_reads, read_len, d_weights, static_cast<hipStream_t>(stream)));
-    return COVEST_OK;
-}
-
-int covest_kmer_add_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets,
-                           int64_t n_reads, int64_t read_len, void *stream)
-{
-    if (!c || n_reads < 0 || (n_reads > 0 && !d_bases) || (!d_offsets && read_len < 0))
-        return fail(COVEST_E_INVALID, "covest_kmer_add_device: bad argument");
-    std::lock_guard<std::mutex> guard(c->lock);
-    return add_device_locked("covest_kmer_add_device", c, d_bases, d_offsets, n_reads, read_len, nullptr, stream);
-}
-
-int covest_kmer_add_weighted_device(covest_kmer *c, const uint8_t *d_bases, const int64_t *d_offsets, int64_t n_reads,
-                                    int64_t read_len, const uint32_t *d_weights, void *stream)
-{
-    if (!c || n_reads < 0 || (n_reads > 0 && !d_bases) || (!d_offsets && read_len < 0))
-        return fail(COVEST_E_INVALID, "covest_kmer_add_weighted_device: bad argument");
-    COVEST_TRY(kmer_check_weights("covest_kmer_add_weighted_device", d_weights, n_reads));
-    std::lock_guard<std::mutex> guard(c->lock);
-    return add_device_locked("covest_kmer_add_weighted_device", c, d_bases, d_offsets, n_reads, read_len, d_weights, stream);
-}
-
-int covest_kmer_add(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads)
-{
-    if (!c || n_reads < 0 || (n_reads > 0 && !offsets))
-        return fail(COVEST_E_INVALID, "covest_kmer_add: bad argument");
-    if (n_reads == 0)
-        return COVEST_OK;
-    const int64_t n_bytes = offsets[n_reads] - offsets[0];
-    if (n_bytes < 0 || (n_bytes > 0 && !bases))
-        return fail(COVEST_E_INVALID, "covest_kmer_add: bad offsets");
-    KmerHostCall call(c);
-    COVEST_TRY(call.open(bases, offsets, n_reads));
-    COVEST_TRY(add_device_locked("covest_kmer_add_device", c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(), n_reads,
-                                 0, nullptr, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    return kmer_check_overflow(c, "covest_kmer_add"); // (the add's own words, not close()'s: the batch is partly counted, the table can grow)
-}
-
-int covest_kmer_add_weighted(covest_kmer *c, const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
-                             const uint32_t *weights)
-{
-    if (!c || n_reads < 0 || (n_reads > 0 && !offsets))
-        return fail(COVEST_E_INVALID, "covest_kmer_add_weighted: bad argument");
-    COVEST_TRY(kmer_check_weights("covest_kmer_add_weighted", weights, n_reads));
-    if (n_reads == 0)
-        return COVEST_OK;
-    const int64_t n_bytes = offsets[n_reads] - offsets[0];
-    if (n_bytes < 0 || (n_bytes > 0 && !bases))
-        return fail(COVEST_E_INVALID, "covest_kmer_add_weighted: bad offsets");
-    KmerHostCall call(c);
-    COVEST_TRY(call.open(bases, offsets, n_reads));
-    HIP_TRY(c->ws_weights.reserve((size_t)n_reads * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(c->ws_weights.ptr, weights, (size_t)n_reads * sizeof(uint32_t), hipMemcpyHostToDevice));
-    COVEST_TRY(add_device_locked("covest_kmer_add_weighted_device", c, c->ws_bases.as<uint8_t>(), c->ws_offsets.as<int64_t>(),
-                                 n_reads, 0, c->ws_weights.as<uint32_t>(), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    return kmer_check_overflow(c, "covest_kmer_add_weighted"); // (as covest_kmer_add: the batch is partly counted, the table can grow)
 }
 
 int covest_kmer_histogram(covest_kmer *c, int64_t *out, int64_t out_len, int64_t *needed_len,

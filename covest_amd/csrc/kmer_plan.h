@@ -1,6 +1,7 @@
 // kmer_plan.h -- the arithmetic of the partitioned k-mer counter (kmer_host.cpp, kmer_bulk.hip) in plain C++: table
-// sizes, the tile geometry, the launch cuts (and the walk over the launches of a wave a read, for_each_wave_launch), the
-// plan of a call, the sizes that follow from pass 0.  No HIP in it: tests/kmer_plan_check.cpp and, for the launch cuts
+// sizes, the tile geometry, the launch cuts (and the walk over the launches of a wave a read, for_each_wave_launch; the
+// launchers of the adds and removals over both: kmer_update.h launch_update), the plan of a call, the sizes that follow
+// from pass 0.  No HIP in it: tests/kmer_plan_check.cpp and, for the launch cuts
 // and the walk, tests/kmer_stages_check.cpp run it under the host compiler's sanitizers.
 #pragma once
 #include <algorithm>
@@ -34,7 +35,7 @@ inline int kmer_wide_words(int k)
     return k <= 31 ? 0 : k <= 63 ? 2 : k <= 127 ? 4 : 8;
 }
 
-// ---- the table paths' launches (kmer_count.hip, kmer_wide.hip): whole reads, `per` of them a launch ---------------------
+// ---- the table paths' launches (kmer_update.h, for kmer_count.hip, kmer_remove.hip, kmer_wide.hip): whole reads, `per` a launch ----
 // A wave a read, reads_per_block reads a workgroup: HIP wraps a grid of more than 2^32 threads silently, so at most
 // 2^23 workgroups of 256 threads a launch (called by for_each_wave_launch below alone).
 inline int64_t wave_reads_per_launch(int reads_per_block)

@@ -2,7 +2,8 @@
 // kmer_count.hip (every occurrence goes to the table), kmer_bulk.hip (only what its LDS path hands back does), and
 // kmer_lookup.hip, kmer_correct.hip and kmer_influence.hip (which only read it: table_find; a wave a read: wave_read.h),
 // kmer_join.hip (which reads two: every key of one table looked up in the other), and kmer_remove.hip (which lowers
-// counts and never clears a key: "held" and "occupied" below).
+// counts and never clears a key: "held" and "occupied" below).  The walk over the reads that kmer_count.hip and
+// kmer_remove.hip share, with table_add or table_locate and a returning atomic as its operation: kmer_update.h.
 // See kmer_count.hip for the reference it restates and for why a key's first slot is a function of its minimizer.
 // The arithmetic on the codes themselves: kmer_codes.h.
 #pragma once

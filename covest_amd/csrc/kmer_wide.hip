@@ -24,7 +24,7 @@
 #include <algorithm>
 
 #include "kernels.h"
-#include "wave_read.h"
+#include "kmer_update.h"
 
 namespace covest {
 
@@ -288,16 +288,9 @@ template <int W>
 hipError_t count_w(const unsigned char *bases, const int64_t *offsets, int64_t n_reads, int64_t fixed_len, int canonical,
                    const KmerWideTable &t, int *overflow, hipStream_t stream, const uint32_t *weights)
 {
-    kmer_plan::for_each_wave_launch(n_reads, fixed_len, offsets != nullptr, kmer::kWaveReadsPerBlock, [&](const kmer_plan::WaveLaunch &l) {
-        const dim3 grid((unsigned)l.blocks), block(kmer::kWaveReadsPerBlock * kWave);
-        const int64_t *offs = offsets ? offsets + l.first : nullptr;
-        if (weights) // a weight a read: it goes with the launch's first read (kmer_plan.h weights_at)
-            hipLaunchKernelGGL((kmer_wide_count_weighted_kernel<W>), grid, block, 0, stream, bases + l.byte_at, offs, l.n,
-                               fixed_len, canonical, t, overflow, weights + kmer_plan::weights_at(l));
-        else
-            hipLaunchKernelGGL((kmer_wide_count_kernel<W>), grid, block, 0, stream, bases + l.byte_at, offs, l.n, fixed_len,
-                               canonical, t, overflow);
-    });
+    // a wave a read, whatever the reads' lengths: no numbered kernels here (kmer_update.h)
+    kmer::launch_wave_reads(kmer_wide_count_weighted_kernel<W>, kmer_wide_count_kernel<W>, bases, offsets, n_reads, fixed_len,
+                            weights, stream, canonical, t, overflow);
     return hipGetLastError();
 }
 

@@ -62,6 +62,26 @@ inline ArgCheck check_table_holds_keys(const std::string &name, int wide, bool b
                                     "table); covest_kmer_clear first") : ArgCheck{};
 }
 
+// The eight forms that change a counter's table, covest_kmer_{add,remove}[_weighted][_device] (abi_update.cpp): what a
+// form is given, as flags.  A device form needs its bases where it has reads and a length where it has no offsets; a
+// host form needs its offsets where it has reads, and -- once it has read them: n_bytes = offsets[n_reads] - offsets[0]
+// -- bytes that do not descend, with bases where there are any.
+inline ArgCheck check_update_device_args(const std::string &name, bool has_counter, bool has_bases, bool has_offsets,
+                                         int64_t n_reads, int64_t read_len)
+{
+    const bool bad = !has_counter || n_reads < 0 || (n_reads > 0 && !has_bases) || (!has_offsets && read_len < 0);
+    return bad ? arg_invalid(name, "bad argument") : ArgCheck{};
+}
+inline ArgCheck check_update_host_args(const std::string &name, bool has_counter, bool has_offsets, int64_t n_reads)
+{
+    const bool bad = !has_counter || n_reads < 0 || (n_reads > 0 && !has_offsets);
+    return bad ? arg_invalid(name, "bad argument") : ArgCheck{};
+}
+inline ArgCheck check_update_host_bytes(const std::string &name, int64_t n_bytes, bool has_bases)
+{
+    return n_bytes < 0 || (n_bytes > 0 && !has_bases) ? arg_invalid(name, "bad offsets") : ArgCheck{};
+}
+
 // Of the host form: offsets[0 .. n_reads] (or nullptr) start at no negative byte and never descend.
 inline ArgCheck check_ascending_offsets(const std::string &name, const int64_t *offsets, int64_t n_reads)
 {

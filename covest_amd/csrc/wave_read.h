@@ -1,5 +1,6 @@
 // wave_read.h -- a wave64 a read, kWaveReadsPerBlock reads a workgroup: how the kernels that walk packed reads against
 // the k-mer table open a read, and a window's key.  Their launches: kmer_plan::for_each_wave_launch.
+// The kernels that change the table walk a read by kmer_update.h, which stands on this file.
 #pragma once
 #include "kmer_table.h"
 

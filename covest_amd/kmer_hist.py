@@ -274,6 +274,27 @@ class KmerCounts:
                 self._distinct = held
         self._added += n_new
 
+    def _update_host(self, name, blob, offsets, weights=None):
+        """A host form of covest_kmer_{add,remove}[_weighted] by its C name: packed reads (_packed_reads), and a uint32
+        weight a read (_read_weights) where the form is weighted."""
+        u8p, i64p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int64)   # (covest_kmer_add's prototype is typed)
+        args = (self._handle, blob.ctypes.data_as(u8p), offsets.ctypes.data_as(i64p), offsets.size - 1)
+        if weights is not None:
+            args += (ctypes.c_void_p(weights.ctypes.data),)
+        _capi.check(getattr(_capi.lib(), name)(*args), name)
+        return self
+
+    def _update_device(self, name, d_bases_ptr, n_reads, read_len, d_offsets_ptr, stream, d_weights_ptr=None, weighted=False):
+        """A device form of covest_kmer_{add,remove}[_weighted]_device by its C name: raw device pointers, asynchronous
+        on `stream`.  `weighted` says whether the C function takes weights at all; a weighted form is handed a null
+        `d_weights_ptr` as it comes (the library refuses it by name), so the pointer cannot stand in for the flag."""
+        _capi.require_shared_runtime("KmerCounts." + name[len("covest_kmer_"):])
+        args = (self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0), int(n_reads), int(read_len))
+        if weighted:
+            args += (ctypes.c_void_p(d_weights_ptr or 0),)
+        _capi.check(getattr(_capi.lib(), name)(*args, ctypes.c_void_p(stream or 0)), name)
+        return self
+
     def add_reads(self, reads):
         """Count the k-mers of preprocessed reads (only a/c/g/t, either case) in one launch."""
         reads = [r if isinstance(r, str) else str(r) for r in reads]
@@ -286,11 +307,7 @@ class KmerCounts:
         if blob.size and not _VALID[blob].all():
             raise KeyError("base outside acgt")  # single_hash raises KeyError (bin/kmer_hist.py:15)
         self._reserve_for(int(np.maximum(lens - self.k + 1, 1).sum()))
-        blob = np.ascontiguousarray(blob)
-        _capi.check(_capi.lib().covest_kmer_add(
-            self._handle, blob.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-            offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(reads)), "covest_kmer_add")
-        return self
+        return self._update_host("covest_kmer_add", np.ascontiguousarray(blob), offsets)
 
     def add_packed(self, bases, offsets, n_reads, n_bases):
         """Preprocessed reads in the packed host layout of covest_kmer_add (ctypes pointers: the bases back to
@@ -311,11 +328,7 @@ class KmerCounts:
             self._reserve_for(n_new)
         else:  # still occurrences inserted since the last measurement: later batches must see them in the bound
             self._added += n_new
-        _capi.require_shared_runtime("KmerCounts.add_device")
-        _capi.check(_capi.lib().covest_kmer_add_device(
-            self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0),
-            int(n_reads), int(read_len), ctypes.c_void_p(stream or 0)), "covest_kmer_add_device")
-        return self
+        return self._update_device("covest_kmer_add_device", d_bases_ptr, n_reads, read_len, d_offsets_ptr, stream)
 
     def add_weighted(self, reads, weights):
         """Count the k-mers of `reads` -- what lookup takes: a list of preprocessed strings, a pair (bases, offsets), an
@@ -328,10 +341,7 @@ class KmerCounts:
         if not n:
             return self
         self._reserve_for(int(np.maximum(np.diff(offsets) - self.k + 1, 1).sum()))
-        _capi.check(_capi.lib().covest_kmer_add_weighted(
-            self._handle, ctypes.c_void_p(blob.ctypes.data), ctypes.c_void_p(offsets.ctypes.data), n,
-            ctypes.c_void_p(weights.ctypes.data)), "covest_kmer_add_weighted")
-        return self
+        return self._update_host("covest_kmer_add_weighted", blob, offsets, weights)
 
     def add_weighted_device(self, d_bases_ptr, n_reads, read_len, d_weights_ptr, d_offsets_ptr=None, stream=None,
                             reserve=True):
@@ -343,11 +353,8 @@ class KmerCounts:
             self._reserve_for(n_new)
         else:
             self._added += n_new
-        _capi.require_shared_runtime("KmerCounts.add_weighted_device")
-        _capi.check(_capi.lib().covest_kmer_add_weighted_device(
-            self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0), int(n_reads), int(read_len),
-            ctypes.c_void_p(d_weights_ptr or 0), ctypes.c_void_p(stream or 0)), "covest_kmer_add_weighted_device")
-        return self
+        return self._update_device("covest_kmer_add_weighted_device", d_bases_ptr, n_reads, read_len, d_offsets_ptr, stream,
+                                   d_weights_ptr, weighted=True)
 
     def remove(self, reads):
         """Take the k-mers of `reads` -- what lookup takes -- out of the table again (covest_kmer_remove; k <= 31):
@@ -356,43 +363,26 @@ class KmerCounts:
         added is an UNDERFLOW: this call, and every later histogram() and host-form call until clear(), raises
         CovestHipError with "underflow"; the counts are then unspecified."""
         blob, offsets = _packed_reads(reads)
-        n = offsets.size - 1
-        if n:
-            _capi.check(_capi.lib().covest_kmer_remove(
-                self._handle, ctypes.c_void_p(blob.ctypes.data), ctypes.c_void_p(offsets.ctypes.data), n),
-                "covest_kmer_remove")
-        return self
+        return self._update_host("covest_kmer_remove", blob, offsets) if offsets.size > 1 else self
 
     def remove_weighted(self, reads, weights):
         """remove with every occurrence of read r taken out weights[r] times (covest_kmer_remove_weighted):
         add_weighted's inverse.  A weight of 0 takes nothing out, also of a read that was never added."""
         blob, offsets = _packed_reads(reads)
-        n = offsets.size - 1
-        weights = _read_weights(weights, n)
-        if n:
-            _capi.check(_capi.lib().covest_kmer_remove_weighted(
-                self._handle, ctypes.c_void_p(blob.ctypes.data), ctypes.c_void_p(offsets.ctypes.data), n,
-                ctypes.c_void_p(weights.ctypes.data)), "covest_kmer_remove_weighted")
-        return self
+        weights = _read_weights(weights, offsets.size - 1)
+        return self._update_host("covest_kmer_remove_weighted", blob, offsets, weights) if offsets.size > 1 else self
 
     def remove_device(self, d_bases_ptr, n_reads, read_len, d_offsets_ptr=None, stream=None):
         """add_device's inverse for reads resident in HBM (raw device pointers; covest_kmer_remove_device): asynchronous
         on `stream`, which must be the stream of the adds it takes back (or ordered after them by the caller).  It does
         not look at the underflow state: the next histogram() reports it."""
-        _capi.require_shared_runtime("KmerCounts.remove_device")
-        _capi.check(_capi.lib().covest_kmer_remove_device(
-            self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0), int(n_reads), int(read_len),
-            ctypes.c_void_p(stream or 0)), "covest_kmer_remove_device")
-        return self
+        return self._update_device("covest_kmer_remove_device", d_bases_ptr, n_reads, read_len, d_offsets_ptr, stream)
 
     def remove_weighted_device(self, d_bases_ptr, n_reads, read_len, d_weights_ptr, d_offsets_ptr=None, stream=None):
         """remove_device with a weight per read resident in HBM (`d_weights_ptr`: n_reads uint32, aligned to 4 bytes;
         covest_kmer_remove_weighted_device): the weights are read on `stream`."""
-        _capi.require_shared_runtime("KmerCounts.remove_weighted_device")
-        _capi.check(_capi.lib().covest_kmer_remove_weighted_device(
-            self._handle, ctypes.c_void_p(d_bases_ptr), ctypes.c_void_p(d_offsets_ptr or 0), int(n_reads), int(read_len),
-            ctypes.c_void_p(d_weights_ptr or 0), ctypes.c_void_p(stream or 0)), "covest_kmer_remove_weighted_device")
-        return self
+        return self._update_device("covest_kmer_remove_weighted_device", d_bases_ptr, n_reads, read_len, d_offsets_ptr, stream,
+                                   d_weights_ptr, weighted=True)
 
     def replace_reads(self, before, after, changed):
         """The reads `before` replaced by `after` in the table, where `changed` flags them: two read sets of equal shape

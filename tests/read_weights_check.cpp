@@ -58,7 +58,7 @@ static void wave_walk()
         }
 }
 
-// 2. the windows of reads of one length numbered through: the loop of launch_kmer_count
+// 2. the windows of reads of one length numbered through: the loop of kmer_update.h launch_update
 static void window_walk()
 {
     for (const int64_t n_windows : {1, 2, 80, 81}) {

@@ -122,12 +122,50 @@ static void check_table_forms()
     }
 }
 
+// The eight forms that change a counter's table (abi_update.cpp): every flag and size of the device forms' and the host
+// forms' first check on its own and at 0 | 1 reads, and the host forms' bytes either side of 0.
+static void check_update_forms()
+{
+    static const char *kArgument = "bad argument", *kBytes = "bad offsets";
+    //                                    counter bases offsets n_reads read_len
+    OK(check_update_device_args("who", true, true, true, 1, 100));
+    OK(check_update_device_args("who", true, true, false, kMax, 0));      // reads of no bases, no offsets
+    OK(check_update_device_args("who", true, false, false, 0, 0));        // no reads: no bases needed
+    OK(check_update_device_args("who", true, false, true, 0, -1));        // read_len is not looked at beside offsets
+    OK(check_update_device_args("who", true, true, true, kMax, kMax));
+    INVALID(check_update_device_args("who", false, true, true, 1, 100), kArgument);
+    INVALID(check_update_device_args("who", false, false, false, 0, 0), kArgument);
+    INVALID(check_update_device_args("who", true, true, true, -1, 100), kArgument);
+    INVALID(check_update_device_args("who", true, false, true, 1, 100), kArgument);   // one read and no bases
+    INVALID(check_update_device_args("who", true, true, false, 1, -1), kArgument);
+    INVALID(check_update_device_args("who", true, false, false, 0, -1), kArgument);   // ... also with no reads
+    //                                  counter offsets n_reads
+    OK(check_update_host_args("who", true, true, 1));
+    OK(check_update_host_args("who", true, false, 0));                    // no reads: no offsets needed
+    OK(check_update_host_args("who", true, true, kMax));
+    INVALID(check_update_host_args("who", false, true, 1), kArgument);
+    INVALID(check_update_host_args("who", false, false, 0), kArgument);
+    INVALID(check_update_host_args("who", true, true, -1), kArgument);
+    INVALID(check_update_host_args("who", true, false, 1), kArgument);
+    INVALID(check_update_host_args("who", true, false, -1), kArgument);
+    //                                   n_bytes bases
+    OK(check_update_host_bytes("who", 0, false));                         // reads that are all empty: no bases needed
+    OK(check_update_host_bytes("who", 0, true));
+    OK(check_update_host_bytes("who", 1, true));
+    OK(check_update_host_bytes("who", kMax, true));
+    INVALID(check_update_host_bytes("who", 1, false), kBytes);
+    INVALID(check_update_host_bytes("who", -1, true), kBytes);            // offsets[n_reads] below offsets[0]
+    INVALID(check_update_host_bytes("who", -1, false), kBytes);
+    INVALID(check_update_host_bytes("who", -kMax - 1, true), kBytes);
+}
+
 int main()
 {
     check_reach();
     check_args();
     check_offsets();
     check_table_forms();
+    check_update_forms();
     // a name is taken as it comes
     expect(check_reads_reach("covest_sample_reads_device", kMax, 1, 0), COVEST_E_INVALID,
            "covest_sample_reads_device: more reads than 64-bit offsets reach", __LINE__);

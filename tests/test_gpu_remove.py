@@ -23,6 +23,7 @@ from test_gpu_join import add_without_reserve
 pytestmark = pytest.mark.gpu
 
 WEIGHTS = (0, 1, 13, 70000)
+COVEST_OK = 0   # include/covest_amd.h
 
 
 class Device:
@@ -431,6 +432,158 @@ def test_refusals_name_their_call(hip_lib, dev):
     finally:
         for c in (wide, bulk, plain):
             c.close()
+
+
+def _add_calls(lib, handle, d_bases=0, d_weights=0, bases="blob", offsets=(0, 100), weights="ones", n_reads=1):
+    """The four add forms on one read of 100 bases, by name.  bases / weights None: a null pointer; weights "odd": a
+    pointer that is no multiple of 4.  The arrays live as long as the lambdas do."""
+    blob = np.frombuffer(b"ACGT" * 25, dtype=np.uint8).copy()
+    offs = None if offsets is None else np.array(offsets, dtype=np.int64)
+    ones = np.ones(2, dtype=np.uint32)
+    vp = ctypes.c_void_p
+    h_bases = vp(blob.ctypes.data) if bases is not None else None
+    h_offs = vp(offs.ctypes.data) if offs is not None else None
+    h_w = {None: None, "ones": vp(ones.ctypes.data), "odd": vp(ones.ctypes.data + 1)}[weights]
+    d_b = vp(d_bases) if bases is not None else None
+    d_w = {None: None, "ones": vp(d_weights), "odd": vp(d_weights + 2)}[weights]
+    keep = (blob, offs, ones)
+    u8p, i64p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int64)   # (covest_kmer_add's prototype is typed)
+    return {
+        "covest_kmer_add": lambda keep=keep: lib.covest_kmer_add(handle, h_bases and ctypes.cast(h_bases, u8p),
+                                                                 h_offs and ctypes.cast(h_offs, i64p), n_reads),
+        "covest_kmer_add_weighted": lambda keep=keep: lib.covest_kmer_add_weighted(handle, h_bases, h_offs, n_reads, h_w),
+        "covest_kmer_add_device": lambda: lib.covest_kmer_add_device(handle, d_b, None, n_reads, 100, None),
+        "covest_kmer_add_weighted_device": lambda: lib.covest_kmer_add_weighted_device(handle, d_b, None, n_reads, 100, d_w,
+                                                                                       None),
+    }
+
+
+ADD_FORMS = ("covest_kmer_add", "covest_kmer_add_weighted", "covest_kmer_add_device", "covest_kmer_add_weighted_device")
+HOST_ADDS, WEIGHTED_ADDS = ADD_FORMS[:2], ADD_FORMS[1::2]
+BULK_TEXT = (": the counter holds a covest_kmer_count_reads_device result (its keys are not in the table); "
+             "covest_kmer_clear first")
+
+
+def test_refusals_of_the_add_forms(hip_lib, dev):
+    """Return code and the whole covest_last_error text of the four add forms under every refusal they have, as the
+    forms stood before they went over one host path: the host forms report a partitioned result
+    under the name of their device form; the host forms call null bases "bad offsets", the device forms "bad argument".
+    Keys of two words are added by all four; no reads is no work and no error."""
+    from covest_amd import _capi
+    from covest_amd.kmer_hist import KmerCounts
+    blob, _ = fixed_reads(300, 8)
+    d_bases, d_w = dev.up(blob), dev.up(np.ones(300, dtype=np.uint32))
+    wide, bulk, plain = KmerCounts(32), KmerCounts(21, canonical=True), KmerCounts(21)
+    invalid = _capi.COVEST_E_INVALID
+
+    def refused(calls, texts):
+        for name, text in texts.items():
+            assert calls[name]() == invalid, name
+            assert _capi.last_error() == text, name
+
+    try:
+        refused(_add_calls(hip_lib, None, d_bases, d_w), {name: name + ": bad argument" for name in ADD_FORMS})
+        assert bulk.count_reads_device(d_bases, 300, 100) == "partitioned"
+        device_form = {"covest_kmer_add": "covest_kmer_add_device", "covest_kmer_add_weighted": "covest_kmer_add_weighted_device"}
+        refused(_add_calls(hip_lib, bulk._handle, d_bases, d_w),
+                {name: device_form.get(name, name) + BULK_TEXT for name in ADD_FORMS})
+        h = plain._handle
+        refused(_add_calls(hip_lib, h, d_bases, d_w, bases=None),                       # null bases, one read
+                {name: name + (": bad offsets" if name in HOST_ADDS else ": bad argument") for name in ADD_FORMS})
+        refused(_add_calls(hip_lib, h, d_bases, d_w, offsets=None), {name: name + ": bad argument" for name in HOST_ADDS})
+        refused(_add_calls(hip_lib, h, d_bases, d_w, weights=None), {name: name + ": null weights" for name in WEIGHTED_ADDS})
+        refused(_add_calls(hip_lib, h, d_bases, d_w, weights="odd"),
+                {name: name + ": the weights must be aligned to 4 bytes" for name in WEIGHTED_ADDS})
+        refused(_add_calls(hip_lib, h, d_bases, d_w, offsets=(100, 0)), {name: name + ": bad offsets" for name in HOST_ADDS})
+        assert plain.histogram() == [0]   # none of the refused calls touched the counter
+        # no reads: nothing to look at, whatever the pointers
+        for kwargs in ({}, {"bases": None, "offsets": None, "weights": None}):
+            for name, call in _add_calls(hip_lib, h, d_bases, d_w, n_reads=0, **kwargs).items():
+                assert call() == COVEST_OK, (name, kwargs)
+        assert plain.histogram() == [0]
+        # k = 32: all four forms add
+        for name, call in _add_calls(hip_lib, wide._handle, d_bases, d_w).items():
+            assert call() == COVEST_OK, (name, _capi.last_error())
+        on_host, on_device = "ACGT" * 25, blob[0].tobytes().decode()
+        assert wide.histogram() == kr.histogram([on_host, on_host, on_device, on_device], 32)[0]
+    finally:
+        for c in (wide, bulk, plain):
+            c.close()
+
+
+# ---- 9b: add and removal through every branch of the walk they share ---------------------------------------------------------
+WALK_GENOME = 400   # bases: a few hundred keys, so that 2^10 slots hold the ragged and the one-length reads together
+
+
+def walk_reads(k):
+    """(ragged, fixed): three reads of each of the lengths 0, 1, k - 1, k, k + 1, k + 63, k + 64, k + 65 -- the
+    short-read key, one window, and both sides of a lane's second round -- and as many reads of k + 64 bases, all from
+    the first WALK_GENOME bases of the genome."""
+    rng = np.random.default_rng(400 + k)
+    g = jr.genome(0)[:WALK_GENOME]
+
+    def cut(length):
+        at = int(rng.integers(0, len(g) - length + 1))
+        return g[at:at + length]
+
+    lengths = [0, 1, k - 1, k, k + 1, k + 63, k + 64, k + 65] * 3
+    return [cut(n) for n in lengths], [cut(k + 64) for _ in lengths]
+
+
+def _host_call(fn, name, handle, reads, weights=None):
+    from covest_amd import _capi
+    blob = np.frombuffer("".join(reads).encode(), dtype=np.uint8).copy()
+    offsets = np.zeros(len(reads) + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in reads], out=offsets[1:])
+    args = (handle, blob.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+            len(reads))
+    if weights is not None:
+        args += (ctypes.c_void_p(weights.ctypes.data),)
+    _capi.check(fn(*args), name)
+
+
+@pytest.mark.parametrize("k", [12, 13, 31])
+def test_add_and_removal_through_every_branch_of_the_walk(hip_lib, dev, k):
+    """One table of 2^10 slots, canonical; k = 12 | 13 is where has_first_slot switches, 31 the top of one word.
+    Weighted add, weighted removal of the same, unweighted add: the histogram of the unweighted reads -- on ragged
+    reads through the host forms (a wave a read: empty, shorter than k, one window, a lane's second round) and on reads
+    of one length through the (n, L) device forms (the windows numbered through).  Weights 0, 1, 2, ...; the read of
+    weight 0 of the removal is one the table never saw.  Then everything removed: no key held, every slot still
+    occupied.  No underflow anywhere: every host form would say so."""
+    from covest_amd.kmer_hist import KmerCounts
+    lib = hip_lib
+    ragged, fixed = walk_reads(k)
+    n, length = len(fixed), k + 64
+    stranger = jr.genome(1)[:k + 65]
+    w = np.arange(n, dtype=np.uint32)
+    assert w[0] == 0 and not set(kr.count([stranger], k, True)) & set(kr.count(ragged + fixed, k, True))
+    fixed_blob = np.frombuffer("".join(fixed).encode(), dtype=np.uint8).reshape(n, length).copy()
+    stranger_blob = fixed_blob.copy()
+    stranger_blob[0] = np.frombuffer(stranger[:length].encode(), dtype=np.uint8)
+    d_fixed, d_stranger, d_w = dev.up(fixed_blob), dev.up(stranger_blob), dev.up(w)
+    counts = KmerCounts(k, canonical=True, min_slots=1 << 10)
+    try:
+        h = counts._handle
+        _host_call(lib.covest_kmer_add_weighted, "covest_kmer_add_weighted", h, ragged, w)
+        _host_call(lib.covest_kmer_remove_weighted, "covest_kmer_remove_weighted", h, [stranger] + ragged[1:], w)
+        _host_call(lib.covest_kmer_add, "covest_kmer_add", h, ragged)
+        want = kr.histogram(ragged, k, True)
+        assert counts.histogram() == want[0]
+        held, occupied = counts.occupancy()
+        assert held == want[1] and occupied >= held
+        counts.add_weighted_device(d_fixed, n, length, d_w, reserve=False)
+        counts.remove_weighted_device(d_stranger, n, length, d_w)
+        counts.add_device(d_fixed, n, length, reserve=False)
+        want = kr.histogram(ragged + fixed, k, True)
+        assert counts.histogram() == want[0]
+        held, occupied = counts.occupancy()
+        assert held == want[1] and occupied >= held
+        counts.remove_device(d_fixed, n, length)
+        _host_call(lib.covest_kmer_remove, "covest_kmer_remove", h, ragged)
+        assert counts.stats() == (1, 0) and counts.histogram() == [0]
+        assert counts.occupancy() == (0, occupied) and counts.slots == 1 << 10
+    finally:
+        counts.close()
 
 
 # ---- 10: replace_reads -----------------------------------------------------------------------------------------------------
