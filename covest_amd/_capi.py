@@ -54,7 +54,17 @@ EXPORTS = (
     "covest_batch_eval_cross_grad", "covest_batch_eval_pairs_grad", "covest_batch_score_table",
     "covest_batch_eval_cross_hess", "covest_batch_eval_pairs_hess", "covest_batch_score_table2",
     "covest_posterior_classes", "covest_posterior_classes_chunked",
+    "covest_math_probe",
 )
+
+# covest_math_probe's `fn` (include/covest_amd.h, csrc/math_probe.hip): a diagnostic for the tests, not a model call
+MATH_PROBE_FN = {
+    "exp_fast": 0, "exp_scaled": 1, "exp_library": 2, "exp_neg_rn": 3, "fast_log": 4, "fast_log_n4": 5,
+    "log_bits_1_5_basic": 6, "log_bits_4_5_scale": 7, "log_bits_4_3_scale_raw": 8, "log_bits_4_4_scale": 9,
+    "log_trunc_norm": 10, "log_trunc_norm_table": 11, "trunc_norm_dlog": 12, "trunc_norm_dlog2_first": 13,
+    "trunc_norm_dlog2_second": 14, "rate_pow": 15, "rate_mul_8": 16, "rate_mul_16": 17, "rates_8": 18, "rates_16": 19,
+    "weight_pow": 20, "weight_squaring": 21,
+}
 
 
 class CovestHipError(RuntimeError):
@@ -334,6 +344,8 @@ def lib():
     L.covest_posterior_classes.argtypes = [vp, i64, dp, i32, i32, dp, dp, dp, dp]
     L.covest_posterior_classes_chunked.restype = ctypes.c_int
     L.covest_posterior_classes_chunked.argtypes = [vp, i64, dp, i32, i32, i64, dp, dp, dp, dp]
+    L.covest_math_probe.restype = ctypes.c_int
+    L.covest_math_probe.argtypes = [i32, i32, i64, vp, vp, vp, vp, i32, i32, vp]
     L.covest_batch_info.restype = ctypes.c_int
     L.covest_batch_info.argtypes = [vp, i64p]
     L.covest_batch_destroy.restype = None
@@ -419,6 +431,23 @@ def parse_launch_record(text):
         elif kind == "plan":
             plans.append({k: int(v) for k, v in (f.split("=") for f in rest.split())})
     return {"launches": launches, "plans": plans}
+
+
+def math_probe(name, x, y=None, z=None, iarg=None, k=0, r=0, device=-1):
+    """covest_math_probe: the primitive MATH_PROBE_FN[name] at every element, as a numpy array of doubles (a
+    diagnostic for the tests; one launch, at most 65 536 elements)."""
+    import numpy as np
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    cols = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (y, z)]
+    ia = None if iarg is None else np.ascontiguousarray(iarg, dtype=np.int32)
+    for a in cols + [ia]:
+        if a is not None and a.shape != x.shape:
+            raise ValueError("math_probe: arrays of different lengths")
+    out = np.empty(x.shape, dtype=np.float64)
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    check(lib().covest_math_probe(device, MATH_PROBE_FN[name], x.size, ptr(x), ptr(cols[0]), ptr(cols[1]), ptr(ia), k, r,
+                                  ptr(out)), "covest_math_probe(%s)" % name)
+    return out
 
 
 def compiled_variants():

@@ -39,7 +39,8 @@ SOURCES = [("host_common.cpp", (), "host_common"), ("tiles_host.cpp", (), "tiles
            ("abi_remove.cpp", (), "abi_remove"), ("kmer_remove.hip", (), "kmer_remove"),
            ("abi_correct.cpp", (), "abi_correct"), ("kmer_correct.hip", (), "kmer_correct"),
            ("abi_influence.cpp", (), "abi_influence"), ("kmer_influence.hip", (), "kmer_influence"),
-           ("abi_bootstrap.cpp", (), "abi_bootstrap"), ("bootstrap_weights.hip", (), "bootstrap_weights")]
+           ("abi_bootstrap.cpp", (), "abi_bootstrap"), ("bootstrap_weights.hip", (), "bootstrap_weights"),
+           ("math_probe.hip", (), "math_probe")]
 # (the rows of the table, from the one place that counts them)
 FACTORED_VARIANTS = int(re.search(r"kFactoredVariants = (\d+)", open(os.path.join(CSRC, "kernels.h")).read()).group(1))
 SOURCES += [("ll_factored.hip", ("-DCOVEST_FACTORED_VARIANT=%d" % v,), "ll_factored_v%d" % v) for v in range(FACTORED_VARIANTS)]

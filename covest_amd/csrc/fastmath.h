@@ -6,8 +6,14 @@
 // 1e-16 (it is summed with weights h_j into a total whose terms all have the same
 // sign), so: exponent/mantissa split (v_frexp_*), a 256-entry table {1/c, log c'}
 // in LDS (4 KB) indexed by the top 8 mantissa bits, r = fma(m, 1/c, -1) with |r| <= 2^-9,
-// and log1p(r) to r^5 (a 64-entry table needs r^7: two more FMAs per log).  ~16 instructions,
-// absolute error < 2e-16 (relative < 2e-16 for |log x| > 1) for x in (0, 1].
+// and log1p(r) to r^5 (a 64-entry table needs r^7: two more FMAs per log).  ~16 instructions.
+// Error, for every finite x > 0 with binary exponent e (derived in tests/math_reference.py, held on the device by
+// tests/test_gpu_math.py, which also holds every bit to a restatement in exact arithmetic):
+//     |fast_log(x) - log x| <= 2^-54 / 6 + 2^-52 |log x| + |fl(ln 2) - ln 2| |e| + 2^-53
+// -- the truncation r^6 / 6, the two roundings at the result's magnitude, the constant's own error (2.3e-17) once per
+// unit of the exponent, the table entry's rounding: 1.2e-16 near x = 1, 3.5e-16 at x = 0.5, 2.2e-16 |log x| + 2.3e-17 |e|
+// where |log x| is large (1.3e-13 at x = 2^-1000, 1.9e-16 of the value).  The "absolute 2e-16" this header used to
+// state holds for |log x| <= 0.4 only.  Measured worst share of that bar: 0.82 (profiles/math_primitives.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,7 +59,23 @@ __device__ __forceinline__ double fma_vvv(double a, double b, double c)
 // every coefficient is a scalar operand of a three-address v_fma_f64 (the scalar unit re-creates it with two s_mov).
 // The power of two is applied by the final v_ldexp_f64 -- exactly, one rounding in all, where the result is a normal
 // double -- so a caller that wants exp(x) 2^540 (streams.h) no longer adds ln 2^540 to the argument or scales twice.
-// x = -inf gives 0, NaN propagates, results beyond the doubles' range are +inf / 0 as v_ldexp_f64 rounds them.
+// x = -inf gives +0 and NaN propagates.  For |x| <= 1e15 a result beyond the doubles' range is +inf, one below it +0
+// (with that sign), and a subnormal one is rounded once more by v_ldexp_f64 onto the 4.9e-324 grid: up to there the
+// remainder t = x - dn ln 2 stays within ln 2 / 2 + 2.3e-16 |x| <= 0.58, where the polynomial is positive, and the
+// ldexp decides alone.  The library's range guards are NOT here, so beyond that t is no longer small and the
+// polynomial's sign and size decide: exp_scaled(-1e20) = -0.0 (a zero of the wrong sign), exp_scaled(1e300) = -inf,
+// exp_scaled(-1e300) = +inf, exp_scaled(+inf) = NaN -- pinned by tests/test_gpu_math.py, bit-equal to the restatement
+// in tests/math_reference.py.  What callers can reach: exp_scaled(a0, kScaleBits) is used only for a log-term inside
+// the window, -760 < a0, and a0 is the log of a mixture term, far below 709.78 - 374.3 (streams.h enter_tile_n; the
+// lanes whose result is discarded may pass anything, -inf included); exp_fast(-xr) of log_trunc_norm has xr in [1, 200];
+// exp_neg_rn(x) has x = o lambda_s with o <= 16384 and lambda_s <= the coverage, which the basic model bounds by
+// max_cov and the repeats model by nothing (clamp_point) -- but the normaliser the same x goes through is defined up
+// to x = 200 x 2^53 = 1.8e18 only (log_trunc_norm; covest_truncated_poisson accepts any rate), and the reference does
+// not return beyond 2^61.  Between 1e15 and 1.8e18 the one deviation is the -0.0 above, and exp_neg_rn's callers form
+// 1.0 - exp_neg_rn(x) or products with it, which cannot see the sign of a zero.  So nothing here is guarded: the two
+// selects would cost every anchor of every recurrence kernel two compares for arguments no defined result depends on.
+// Accuracy inside the range: 0.78 ulp at sc = 0 and 0.71 ulp at sc = kScaleBits over the inputs of tests/test_gpu_math.py,
+// the device library's own exp 0.78 and 0.71 ulp on the same inputs (profiles/math_primitives.txt).
 __device__ __forceinline__ double exp_scaled(double x, int sc)
 {
 
@@ -75,7 +97,8 @@ __device__ __forceinline__ double exp_scaled(double x, int sc)
     p = fma_vvs(t, p, 0x1.000000000000bp-1);
     p = fma(t, p, 1.0);
     p = fma(t, p, 1.0);
-    // (|x| beyond 1100: the result is 0 or +inf whatever the polynomial says; keeps n + sc inside the ints)
+    // (keeps n + sc inside the ints; |dn| beyond 4096 means |x| beyond 2839, where p 2^(+-4096 + sc) is 0 or +-inf
+    // for any finite p != 0 -- the SIGN is p's, see above)
     const int n = (int)fmin(fmax(dn, -4096.0), 4096.0);
     const double z = ldexp(p, n + sc);
     return x == -INFINITY ? 0.0 : z;
@@ -160,14 +183,19 @@ __device__ __forceinline__ void fast_log_n(const double (&x)[N], double (&out)[N
 // arithmetic -- the exponent comes off the bits with a shift and an add (two half-rate integer instructions, the
 // price of v_frexp_exp_i32_f64 alone), so the scale costs nothing; x must be a NORMAL double (the callers clamp).
 // (Taking the mantissa off the bits too -- and, or -- was tried: the compiler copies the low word into a fresh
-// register pair for it, v_frexp_mant_f64 is cheaper.)  DEG: log1p(r) to r^DEG, |r| <= 2^-9: 5 -> truncation 9e-18
-// (as fast_log); 4 -> r^5 / 5 <= 5.7e-15, zero-mean over the mantissa (odd in r) -- one FMA less per log; 3 (round 5,
-// dense grids: ll_factored.hip) -> another FMA less: r - (1/2 + d) r^2 + r^3 / 3 with d = 0.2071 x 2^-18 chosen so
-// that d r^2 - r^4 / 4 equioscillates over |r| <= 2^-9 -- an absolute 6.2e-13 at most (3.6e-12 for the plain Taylor
-// cubic), against sums whose terms are |log p_j| >= 1 and a parity bar of 1e-9.
-// RAW (DEG 3 only): the exponent is not un-biased -- the result is log(x 2^-SC) + kLogRawBias(SC), one integer
-// subtract less per log; the caller takes the constant off once per SUM (h_j kLogRawBias summed over the counted keys
-// is a constant of the histogram).
+// register pair for it, v_frexp_mant_f64 is cheaper.)  DEG: log1p(r) to r^DEG, |r| <= 2^-9.  The error is fast_log's
+// bound with log(x 2^-SC) for log x, the exponent e that multiplies ln 2 here, and the truncation T_DEG for 2^-54 / 6:
+// 5 -> T_5 = 2^-54 / 6 = 9.3e-18 (as fast_log); 4 -> T_4 = 2^-45 / 5 + T_5 = 5.69e-15, zero-mean over the mantissa (odd
+// in r) -- one FMA less per log (no kernel instantiates it; the test does); 3 (round 5, dense grids: ll_factored.hip)
+// -> another FMA less: r - (1/2 + d) r^2 + r^3 / 3 with d = 0.2071 x 2^-18 chosen so that d r^2 - r^4 / 4
+// equioscillates over |r| <= 2^-9 -- T_3 = (1/4 - 0.2071) 2^-36 + 2^-45 / 5 + T_5 = 6.30e-13 (the restatement in exact
+// arithmetic reaches 6.25e-13 on [0.5, 1); 3.6e-12 for the plain Taylor cubic), against sums whose terms are
+// |log p_j| >= 1 and a parity bar of 1e-9.  Measured worst shares of these bars: 0.87 (5), 0.85 (4), 0.97 (3).
+// RAW (DEG 3 only): the exponent is not un-biased -- the result is log(x 2^-SC) + (1022 + SC) ln 2, one integer
+// subtract less per log, with the same bound (e is then the biased exponent, up to 2046).  The caller takes the
+// constant kLogRawBias<SC> off once per SUM (h_j kLogRawBias summed over the counted keys is a constant of the
+// histogram); that double is off the real (1022 + SC) ln 2 by its own rounding and 1562 times fl(ln 2)'s error:
+// 6.97e-14 at SC = 540 (bound 1.5e-13), the same for every key, so 7e-14 relative to a sum of |log p_j| >= 1.
 template <int SC>
 constexpr double kLogRawBias = (double)(1022 + SC) * 0.693147180559945309417232121458;
 template <int N, int DEG, int SC, bool RAW = false>

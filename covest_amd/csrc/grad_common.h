@@ -31,7 +31,8 @@ __device__ __forceinline__ double trunc_norm_dlog(double x)
 
 // The first AND the second derivative, piece by piece as above: L' = 1 / x, L'' = -1 / x^2 on the two branches that
 // divide by x itself; L' = 1 / (1 - exp(-xr)), L'' = -exp(-xr) / (1 - exp(-xr))^2 of the residual otherwise.  d1 is
-// trunc_norm_dlog(x), the same expressions.
+// trunc_norm_dlog(x), the same expressions (bit for bit: tests/test_gpu_math.py, which holds both to the 50-digit
+// derivatives inside every piece -- relative errors in profiles/math_primitives.txt, all below 1e-15).
 __device__ __forceinline__ void trunc_norm_dlog2(double x, double &d1, double &d2)
 {
     double xr = x;
@@ -51,7 +52,10 @@ __device__ __forceinline__ void trunc_norm_dlog2(double x, double &d1, double &d
     } else {
         const double em = expm1(-xr); // -(1 - exp(-xr))
         d1 = -1.0 / em;
-        d2 = -(em + 1.0) * d1 * d1;
+        // exp(-xr): em + 1 carries an ABSOLUTE 1.1e-16, which is all of exp(-xr) from xr = 37 on (L'' came out as 0 at
+        // xr = 199.9, and 2e-12 off at xr = 10: tests/test_gpu_math.py) -- from 1 on the exponential itself
+        const double ex = xr >= 1.0 ? exp_fast(-xr) : em + 1.0;
+        d2 = -ex * d1 * d1;
     }
 }
 

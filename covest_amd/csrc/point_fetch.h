@@ -66,7 +66,8 @@ __device__ __forceinline__ double error_class_rate(const DevModel &m, double c, 
 
 // ONE class's rate by multiplication, for a kernel whose lanes are classes (ll_fix_basic_packed_kernel, ll_fix.hip): the products of
 // error_class_rates<S> below in the same order -- (1 - e)^max(k - S + 1, 0) by squaring, one more factor a class down to
-// s, e^s factor by factor -- so the strict re-evaluation of a K-basic point works with the very rates K-basic had.
+// s, e^s factor by factor -- so the strict re-evaluation of a K-basic point works with the very rates K-basic had
+// (bit for bit, every class of S = 8 and 16 at k = 1 .. 63: tests/test_gpu_math.py).
 __device__ __forceinline__ double error_class_rate_mul(const DevModel &m, double c, double err, int s, int S)
 {
     const double ck = c * (double)(m.r - m.k + 1) / (double)m.r;
@@ -91,8 +92,11 @@ __device__ __forceinline__ double error_class_rate_mul(const DevModel &m, double
 // (1 - e)^(k - s) and e^s by multiplication -- (1 - e)^(k - S + 1) by squaring, then one multiply a class -- instead of
 // two calls of pow a class.  Round 4: the device library's pow is 210 instructions, and sixteen of them were HALF of
 // K-basic's instruction count on C2.  The products differ from pow's by a few 1e-16 relative (the reference's own pow and
-// the device's differ by as much); the log-likelihood moves by less than 1e-12 of itself.  Classes beyond k (padding of
-// the class count to a multiple of 8: comb = 0, they weigh nothing) get the exponent 0.
+// the device's differ by as much); the log-likelihood moves by less than 1e-12 of itself.  Against the rate formed
+// exactly from the double 1 - e the test holds them to (2 ceil(log2 k) + S + 4) 2^-53 relative -- a count of the
+// multiplications, 2.7e-15 at k = 63, S = 8 -- and measures 1.2e-15 there at worst (profiles/math_primitives.txt; the
+// squarings double what they inherit, so the worst case over ALL e grows like k 2^-53, 7e-15 at k = 63).  Classes beyond
+// k (padding of the class count to a multiple of 8: comb = 0, they weigh nothing) get the exponent 0.
 template <int S>
 __device__ __forceinline__ void error_class_rates(const DevModel &m, double c, double err, double (&lam)[S])
 {
@@ -130,21 +134,61 @@ __device__ __forceinline__ double copy_number_weight(double q1, double q2, doubl
     return (1.0 - q1) * (1.0 - q2) * q * pow(1.0 - q, (double)(o - 3));
 }
 
-// The same weight with (1 - q)^(o - 3) by squaring (at most 14 squarings for o <= 16384: about 1e-15 relative) instead
-// of the device library's pow (210 instructions): for the strict re-evaluation of handed-back rows (ll_fix.hip), where
-// every lane of every lot wants one and the terms are rounded onto the 4.9e-324 grid anyway.
+// a * b, a + b and a - b each rounded on its own, behind asm: the compiler contracts a plain product into the sum or
+// difference that reads it (the rounded-multiply intrinsics included), which is exactly the rounding error the (hi, lo)
+// pairs below exist to catch -- with it fused away the pair was WORSE than plain doubles (2.4e-13, measured).
+__device__ __forceinline__ double mul_rn(double a, double b)
+{
+    double d;
+    asm("v_mul_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
+__device__ __forceinline__ double add_rn(double a, double b)
+{
+    double d;
+    asm("v_add_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
+__device__ __forceinline__ double sub_rn(double a, double b)
+{
+    double d;
+    asm("v_add_f64 %0, %1, -%2" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
+
+// The same weight with (1 - q)^(o - 3) by squaring (at most 14 squarings for o <= 16384) instead of the device library's
+// pow (210 instructions): for the strict re-evaluation of handed-back rows (ll_fix.hip), where every lane of every lot
+// wants one and the terms are rounded onto the 4.9e-324 grid anyway.  The squares and the running product are kept as
+// (hi, lo) pairs: in plain doubles every squaring DOUBLES the relative error it inherits, so the power carried about
+// (o - 3) 2^-53 -- 1.4e-13 at o = 16384, q = 0.01, not the "about 1e-15" this comment used to claim (found by
+// tests/test_gpu_math.py).  With the pairs the power is good to 2^-98 and the weight to the roundings of 1 - q1,
+// 1 - q2, 1 - q and the three products: within (2 * 14 + 4) 2^-53 = 3.6e-15 relative of the value formed from those
+// three differences, which is the bar the test holds it to (measured: profiles/math_primitives.txt).
 __device__ __forceinline__ double copy_number_weight_by_squaring(double q1, double q2, double q, int o)
 {
     if (o == 1)
         return q1;
     if (o == 2)
         return (1.0 - q1) * q2;
-    double pw = 1.0, sq = 1.0 - q;
+    // pw = the product of the squares sq = (1 - q)^(2^j) that the bits of o - 3 pick, both as (hi, lo) pairs: every
+    // operation below is explicit (an fma, or one of the three above), so the pair arithmetic is the same in every
+    // kernel that inlines it and tests/math_reference.py restates it bit for bit
+    double ph = 1.0, pl = 0.0, sh = 1.0 - q, sl = 0.0;
     for (unsigned n = (unsigned)(o - 3); n != 0; n >>= 1) {
-        pw = (n & 1u) ? pw * sq : pw;
-        sq *= sq;
+        {
+            const double h = mul_rn(ph, sh);
+            const double l = add_rn(fma(ph, sh, -h), fma(ph, sl, mul_rn(pl, sh)));
+            const double s = add_rn(h, l);
+            const double t = sub_rn(l, sub_rn(s, h));
+            ph = (n & 1u) ? s : ph;
+            pl = (n & 1u) ? t : pl;
+        }
+        const double h = mul_rn(sh, sh);
+        const double l = add_rn(fma(sh, sh, -h), mul_rn(add_rn(sh, sh), sl));
+        sh = add_rn(h, l);
+        sl = sub_rn(l, sub_rn(sh, h));
     }
-    return (1.0 - q1) * (1.0 - q2) * q * pw;
+    return (1.0 - q1) * (1.0 - q2) * q * ph;
 }
 
 // exp(-x), x >= 0, as the reference's libm returns it.  The mixture weights are
@@ -154,6 +198,9 @@ __device__ __forceinline__ double copy_number_weight_by_squaring(double q1, doub
 // within a 1e-8 ulp margin, so the correctly rounded value is computed here from
 // the Taylor series in double-double instead of trusting the device library's
 // last bit.  Above 2^-6 that sensitivity is < 1e-14 and the device exp is used.
+// Held on the device by tests/test_gpu_math.py: the correctly rounded exp(-x) (50 digits) at 0, 1e-300, every power of
+// two from 2^-60 to 2^-7, the neighbour of 2^-6 and 2 000 seeded arguments -- all 2 057 -- and exp_fast(-x)'s bits from
+// 2^-6 on; the polynomial below is plain C++, so the compiler's contraction is part of what that test covers.
 __device__ __forceinline__ double exp_neg_rn(double x)
 {
     if (!(x < 0.015625))
@@ -188,6 +235,12 @@ __device__ __forceinline__ double exp_neg_rn(double x)
 // so this is reproduced, together with its two small-argument branches: x <= 1e-8 divides by
 // x itself (:20,29), and a residual <= 1e-8 divides by the ORIGINAL x (:29-31).
 // `log_tab`: optional LDS copy of the fast_log table (fastmath.h) -- the two logs below need absolute accuracy.
+// Against that definition at 50 digits (tests/test_gpu_math.py, piece by piece; profiles/math_primitives.txt): without
+// the table within 2^-51 max(1, |value|) -- measured 4.9e-16 for xr in [2^-10, 1), 4.0e-16 from 1 on, half an ulp of
+// 200 n + ... behind a chunk (7e-13 at x = 11 400) --, with the table the same figures plus fast_log's bound for the one
+// log it replaces (5.1e-16 measured for xr in [2^-10, 1)); below 2^-10 both forms may differ from the definition by one
+// step of the 2^-63 grid, 2^-63 / expm1(xr) in the log (5e-12 at xr = 2e-8; 1.9e-13 measured at worst), because expm1
+// is rounded to a double before the rint and the grid rounding may fall either way.
 __device__ __forceinline__ double log_trunc_norm(double x, double log_x, const double *log_tab = nullptr)
 {
     if (x <= 1e-8)

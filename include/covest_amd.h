@@ -180,6 +180,25 @@ int covest_reference_overflow(const covest_model *m, int64_t n, const double *pa
 int covest_truncated_poisson(int32_t device, int64_t n, const double *l, const int64_t *j, int32_t mode, double *out);
 int covest_truncated_poisson_table(int32_t device, int64_t n_l, const double *l, int64_t n_j, const int64_t *j, double *out);
 
+/* ---- DIAGNOSTIC: the scalar primitives under the kernels, one element a thread (csrc/math_probe.hip) ----
+ * Not part of the model's interface: it exists so that tests can hold the hand-written device math (csrc/fastmath.h,
+ * point_fetch.h, grad_common.h) to a reference on its own.  out[i] = fn(x[i], y[i], z[i], iarg[i]) in one launch of
+ * 256-thread workgroups; HOST arrays of n elements, n <= 65536; an array `fn` does not read may be NULL.  `fn`:
+ *    0 exp_fast(x)                 1 exp_scaled(x, iarg), |iarg| <= 2048     2 the device library's exp(x)
+ *    3 exp_neg_rn(x)               4 fast_log(x)                             5 fast_log_n<4>(x)
+ *    6 fast_log_bits_n<1, 5, kBasicShift>(x)        7 fast_log_bits_n<4, 5, kScaleBits>(x)
+ *    8 fast_log_bits_n<4, 3, kScaleBits, RAW>(x)    9 fast_log_bits_n<4, 4, kScaleBits>(x)
+ *   10 log_trunc_norm(x, y), y = log x             11 the same with the log table
+ *   12 trunc_norm_dlog(x)         13, 14 the first and the second output of trunc_norm_dlog2(x)
+ *   15 error_class_rate(c = x, e = y, s = iarg)    16, 17 error_class_rate_mul(.., S = 8, 16)
+ *   18, 19 error_class_rates<8>, <16>(c = x, e = y)[s = iarg]   -- all five on a model of (k, r), 1 <= k <= 63, r >= k
+ *   20 copy_number_weight(q1 = x, q2 = y, q = z, o = iarg)      21 copy_number_weight_by_squaring, 1 <= o <= 16384
+ * In 5 and 7 .. 9 a thread takes four consecutive elements, as the kernels do.  k and r are read by 15 .. 19 only.
+ * COVEST_E_INVALID: an unknown fn, n outside 0 .. 65536, a NULL array that fn reads, an iarg outside the range above
+ * (a class: 0 .. S - 1; 15: 0 .. 63).  n == 0: COVEST_OK, nothing launched.  Enters no launch record. */
+int covest_math_probe(int32_t device, int32_t fn, int64_t n, const double *x, const double *y, const double *z,
+                      const int32_t *iarg, int32_t k, int32_t r, double *out);
+
 /* model.compute_probabilities(*params): models.py:81-98, :211-242.  out_p[n_keys]
  * in key order (host).  clamp != 0 applies fit_to_bounds first, which is how
  * compute_loglikelihood calls it (models.py:101-102); clamp == 0 is the raw
